@@ -7,19 +7,23 @@ One "step" = one calc_map_k-equivalent pass over packed codes already resident i
   -> [N>1: RCCL all-gather of histograms] -> pass 2 (ranks + AP sums) -> [N>1: all-reduce of the per-query sums] -> mean.
 N GPUs (default, "weak"): every rank holds its own R-row gallery shard (contiguous global index ranges), the query set is
 split over the ranks and all-gathered inside the timed step, like runners/base.py does after encoding.
-After the headline the N>1 run also measures the fixed-gallery ("strong") shapes of BASELINE configs[2] (NUS-WIDE-shaped
-mAP scan, Q 5000 x R 188 000 in total) and configs[4] (10 M x 256-bit top-k, shard top-k -> gather -> host merge) and
-reports them under "strong_scaling".
+With --full, after the headline the N>1 run also measures the fixed-gallery ("strong") shapes of BASELINE configs[2]
+(NUS-WIDE-shaped mAP scan, Q 5000 x R 188 000 in total) and configs[4] (10 M x 256-bit top-k, shard top-k -> gather -> host
+merge) and reports them under "strong_scaling".
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR writes what the last timed step
+computed (DIR/map.npy, and unsharded DIR/ap_sum.npy, DIR/cap.npy; float64) from inputs that are the same for the same arguments.
 
 N>1 may be launched either way: `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE
 in the environment), or plain `python bench.py --gpus N`, which re-executes itself under torch.distributed.run
 (rendezvous on 127.0.0.1, a free port) -- the reference's own entry script spawns its ranks the same way (main.py:38-51).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel of the step, a second
-roofline for the HBM-bound top-k regime (configs[4] shape, one GPU's share), the encoder leg and the CPU baselines (oracle
-ports of the reference's calc_map_k and CLIP forward) timed on this host.
+Prints ONE JSON line on rank 0 (contract in the task statement).  With --full the line also carries `roofline` for the
+dominant kernel of the step, a second roofline for the HBM-bound top-k regime (configs[4] shape, one GPU's share), the other
+shapes, the encoder legs, the build check and the CPU baselines (oracle ports of the reference's calc_map_k and CLIP forward)
+timed on this host.
 """
 import argparse
 import json
@@ -77,6 +81,23 @@ def build_info():
     bid = _lib.lib.xmh_build_id().decode()
     return {"lib": os.path.relpath(so, ROOT), "lib_bytes": os.path.getsize(so), "build_id": bid, "lib_is_a_build_of_these_sources": bid == h.hexdigest()[:16],
             "sources": len(files), "xmh_version": int(_lib.lib.xmh_version())}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what the last timed step handed its caller, as float64 DIR/<name>.npy -- map [1] and, unsharded, ap_sum [Q]
+    and cap [Q] (int32 counts, exact in float64).  Should the arrays pass 64 MB in all, ap_sum and cap keep the same seeded sample of
+    query rows."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {name: t.cpu().numpy().astype(np.float64) for name, t in zip(("map", "ap_sum", "cap"), res) if t is not None}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(1814).choice(arrays["ap_sum"].size, DUMP_LIMIT_BYTES // 16 - 1, replace=False))
+        arrays = {k: (a if k == "map" else a[keep]) for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def host_description():
@@ -201,7 +222,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-strong", action="store_true", help="N>1: skip the fixed-gallery legs (configs[2], configs[4])")
     ap.add_argument("--no-extra-configs", action="store_true", help="N=1: skip the configs[3] (K=128) and MITH encode legs")
     ap.add_argument("--force-sharded", action="store_true", help="use the multi-GPU exchange path even with one rank (RCCL smoke test)")
-    ap.add_argument("--force-strong", action="store_true", help="with --force-sharded: also run the N>1 fixed-gallery legs on the one rank")
+    ap.add_argument("--force-strong", action="store_true", help="with --full --force-sharded: also run the N>1 fixed-gallery legs on the one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else: roofline, HBM-regime top-k, other shapes and precisions, encoder "
+                         "and valid() legs, build check, CPU baselines, N>1 fixed-gallery legs (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64): map, and unsharded ap_sum and cap")
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST HOOK, never a measurement: every rank uses cuda:0 and the group is gloo (RCCL refuses two ranks on one device), "
                          "so the N>1 code path -- shard ops on device tensors, the collectives on workspace views, the fixed-gallery legs -- "
@@ -407,11 +433,12 @@ def main():
     sq = ShardedQueries(q, ql, world, rank) if use_dist else None
 
     def step():
+        """-> (map [1] f64, ap_sum [Q] f64, cap [Q] i32); the sharded form returns (map, None, None)"""
         if not use_dist:
             scan.histograms(False)
-            return scan.map_all(None)[0]
+            return scan.map_all(None)
         sq.gather()                                            # packed query codes + labels over RCCL, inside the timed step
-        return sharded.map_k_sharded(piped if piped is not None else ops, None, map_only=True)[0]
+        return sharded.map_k_sharded(piped if piped is not None else ops, None, map_only=True)
 
     def barrier():
         if use_dist:
@@ -419,9 +446,11 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(max(0, args.settle) + args.warmup):
-        m = step()
-    dt, m = timed(step, barrier, args.steps, use_dist)
-    map_value = float(m.item())
+        step()
+    dt, res = timed(step, barrier, args.steps, use_dist)
+    map_value = float(res[0].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # what the timed step really exchanged: the one-shot form runs map_k_sharded(map_only=True), whose default is the
     # all-to-all by query slice whenever the padded query count divides by the world size; query blocks pipeline the [Q] form
@@ -434,7 +463,6 @@ def main():
                        "all_to_all offset rows [world,K+2,qpad/world,2] u32", "all_reduce [1] f64"]
     else:
         collectives = ["all_gather packed query codes", "all_gather totals tables [K+1,qpad,2] u32", "all_reduce [1] f64"]
-    roofline = RL.scan_roofline(scan, Q, Rn, K, C, steps=max(args.steps, 10), step_s=None if use_dist else dt / args.steps)
 
     out = {
         "metric": "Hamming query x gallery pairs/sec (fused mAP@all pass, DCMHT COCO-shaped 64-bit)",
@@ -447,10 +475,13 @@ def main():
                    "query_blocks": nqb if use_dist else 1,
                    "collectives_in_step": collectives},
         "rccl_ranks": ranks_in_group, "launcher": ("torch.distributed.run" if world > 1 else "single process") + (" (--share-gpu: all ranks on cuda:0 over gloo, a code-path check and not a measurement)" if args.share_gpu else ""),
-        "mAP": map_value, "roofline": roofline, "build": build_info(),
+        "mAP": map_value,
     }
+    if args.full:
+        out["roofline"] = RL.scan_roofline(scan, Q, Rn, K, C, steps=max(args.steps, 10), step_s=None if use_dist else dt / args.steps)
+        out["build"] = build_info()
 
-    if rank == 0 and world == 1 and not args.no_hbm_regime:
+    if args.full and rank == 0 and world == 1 and not args.no_hbm_regime:
         import bench_topk
         # one try per leg: a failure (e.g. no room for 80 M rows) must not overwrite a leg already measured
         for key, kw in (("roofline_hbm_regime", dict(Q=1)), ("roofline_hbm_regime_q8", dict(Q=8)), ("roofline_hbm_regime_q64", dict(Q=64)),
@@ -477,7 +508,7 @@ def main():
             except Exception as exc:
                 out[key] = {"error": repr(exc)}
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # boundary-inclusive rate: the drop-in calc_map_k handed HOST fp32 [N,K] codes and int64 labels like the reference's
         # callers do (H2D over PCIe + pack + both passes + D2H of the scalar); reported next to `value`, never as `value`
         from xmh.common import calc_utils as cu
@@ -488,7 +519,7 @@ def main():
         t_host = (time.perf_counter() - t0) / 3
         out["boundary_inclusive"] = {"what": "xmh.common.calc_utils.calc_map_k on host fp32 codes / int64 labels (PCIe H2D + pack + scan + D2H)",
                                      "ms_per_call": t_host * 1e3, "pairs_per_s": Q * Rn / t_host, "mAP": float(m_host)}
-    if rank == 0 and world == 1 and not use_dist and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_extra_configs:
         # round 6: calc_map_k on un-quantised float "codes" (UMoED-style tanh outputs, reference runners/UMoED/runner.py:162-186) -- the
         # reference's own route, fp32 GEMM + one stable sort per query (xmh_gemm_f32_sort_map), Q 500 x R at the COCO shape
         try:
@@ -546,7 +577,7 @@ def main():
             except Exception as exc:
                 out[name] = {"error": repr(exc)}
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not use_dist and not args.no_encode:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_encode:
         try:
             import bench_encode
             out["encode"] = bench_encode.measure()
@@ -555,7 +586,7 @@ def main():
                 out["encode_mith_b400"] = bench_encode.measure_mith(batch=400, steps=5)      # the runner's fused evaluation batches (encode_fuse = 4)
         except Exception as exc:
             out["encode"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not use_dist and not args.no_encode and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_encode and not args.no_extra_configs:
         # the thing the reference runs: BaseTrainer.valid() at the configs[1] shape, end to end, with the encode / retrieve split
         try:
             import bench_valid
@@ -564,7 +595,7 @@ def main():
             out["valid_e2e"] = bench_valid.measure(Q=Q, Rn=Rn, K=K, C=C)
         except Exception as exc:
             out["valid_e2e"] = {"error": repr(exc)}
-    if use_dist and not args.no_encode:
+    if args.full and use_dist and not args.no_encode:
         # encode is data-parallel (every rank encodes its own shard of images / captions, no collective on the path): each rank
         # measures its own rate at the same time as the others, the job rate is the sum
         try:
@@ -582,7 +613,7 @@ def main():
                          "slowest_rank_captions_per_s": float(lo[1]), "n_gpus": world,
                          "config": {"workload": "CLIP ViT-B/32 + DCMHT 64-bit head, batch 100 per GPU, parity mode; one replica per GPU, "
                                                 "rates summed over ranks (measured concurrently)"}}
-    if (world > 1 or (args.force_sharded and args.force_strong)) and not args.no_strong:
+    if args.full and (world > 1 or (args.force_sharded and args.force_strong)) and not args.no_strong:
         del ops, scan, piped, sq
         torch.cuda.empty_cache()
         try:
@@ -593,7 +624,7 @@ def main():
             # destroy_process_group
             out["strong_scaling"] = {"error": repr(exc)}
             print("strong-scaling legs failed on rank %d: %r" % (rank, exc), file=sys.stderr)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def gpu_map(qsub):
             return R.map_k_packed(R.pack_sign(qB[:qsub].cuda()), r, R.pack_labels(qL[:qsub].cuda()), rl, C, None).item()
         out["cpu_baseline"] = cpu_baseline(qB, qL, rB, rL, args.cpu_seconds, gpu_map)

@@ -1,4 +1,4 @@
-"""Generate tests/golden/preprocess.npz with Pillow's own ``Image.resize(..., BICUBIC)`` (the arithmetic behind the
+"""Generate tests/golden/preprocess.npz (inputs, float stage) and preprocess_resized.npz (resized images) with Pillow's own ``Image.resize(..., BICUBIC)`` (the arithmetic behind the
 reference's eval transform, dataset/transformer_dataset.py:38-42) and torch's float32 ToTensor/Normalize formula.
 TEST INFRASTRUCTURE ONLY; runs in the build container.   python oracle/make_golden_preprocess.py"""
 import os
@@ -32,8 +32,11 @@ def main():
         out["resized%d" % n] = res
         if n == 0:                                     # the float stage is elementwise: one case pins it
             out["tensor%d" % n] = t.numpy()
+    # two files, each under the 1 MiB limit of a committed fixture; tests read them as one set
+    resized = {k: out.pop(k) for k in list(out) if k.startswith("resized")}
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "preprocess.npz"), **out)
-    print("wrote preprocess.npz", {k: getattr(v, "shape", None) for k, v in out.items()})
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "preprocess_resized.npz"), **resized)
+    print("wrote preprocess.npz + preprocess_resized.npz", {k: getattr(v, "shape", None) for k, v in {**out, **resized}.items()})
 
 
 if __name__ == "__main__":

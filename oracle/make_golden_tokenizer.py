@@ -57,5 +57,23 @@ def main():
     print("wrote tokenizer.npz", len(CAPTIONS), "captions; decode check:", tok.decode(ids[0].tolist()))
 
 
+VOCAB_FIXTURE = os.path.join(ROOT, "tests", "golden", "bpe_simple_vocab_16e6_clip.txt.gz")
+
+
+def write_vocab():
+    """tests/golden/bpe_simple_vocab_16e6_clip.txt.gz: the reference's BPE merge table cut to the header line and the 49152 - 256 - 2
+    merges CLIP's vocabulary uses (all that SimpleTokenizer and xmh.dataset.tokenizer read of it); the whole file is above the size
+    limit of a committed fixture.  Byte-reproducible (gzip mtime 0)."""
+    import gzip
+    src = os.path.join(_ref_import.REF, "models", "CLIP", "bpe_simple_vocab_16e6.txt.gz")
+    with gzip.open(src) as f:
+        lines = f.read().decode("utf-8").split("\n")
+    keep = "\n".join(lines[:49152 - 256 - 2 + 1]) + "\n"
+    with open(VOCAB_FIXTURE, "wb") as raw, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=raw, mtime=0) as f:
+        f.write(keep.encode("utf-8"))
+    print("wrote", VOCAB_FIXTURE, os.path.getsize(VOCAB_FIXTURE), "bytes")
+
+
 if __name__ == "__main__":
     main()
+    write_vocab()

@@ -10,7 +10,7 @@ dependencies that are not under /root/reference:
     22 fractional bits, accumulator started at 2^21, result ``>> 22`` and clipped to [0, 255] after EACH pass;
   * torchvision 0.10 (requirements.txt:14) -- ``ToTensor`` = HWC uint8 -> CHW float32 ``/ 255``; ``Normalize`` =
     ``(x - mean) / std`` in float32.
-This file restates that published algorithm; it is pinned by tests/golden/preprocess.npz, whose expected outputs were
+This file restates that published algorithm; it is pinned by tests/golden/preprocess{,_resized}.npz, whose expected outputs were
 produced by Pillow itself in the build container (oracle/make_golden_preprocess.py).
 """
 import numpy as np

@@ -20,7 +20,8 @@ def tf():
 
 
 def test_goldens_bit_exact(tf):
-    g = np.load(os.path.join(GOLDEN, "preprocess.npz"))
+    g = dict(np.load(os.path.join(GOLDEN, "preprocess.npz")))
+    g.update(np.load(os.path.join(GOLDEN, "preprocess_resized.npz")))
     n = 0
     while "img%d" % n in g:
         img = torch.from_numpy(g["img%d" % n])

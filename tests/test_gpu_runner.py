@@ -198,7 +198,7 @@ def test_bench_sharded_path_over_rccl_single_rank():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--Q", "300", "--R", "20000", "--no-cpu-baseline",
-            "--no-hbm-regime", "--no-encode"]
+            "--no-hbm-regime", "--no-encode", "--full"]
     a = json.loads(subprocess.run(base, capture_output=True, text=True, check=True, timeout=600).stdout.strip().splitlines()[-1])
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     b = json.loads(subprocess.run(base + ["--force-sharded"], capture_output=True, text=True, check=True, timeout=600, env=env).stdout.strip().splitlines()[-1])
@@ -211,6 +211,40 @@ def test_bench_sharded_path_over_rccl_single_rank():
     # the line on stdout is the compact contract line (bench_emit); the full object of the last run sits beside it
     detail = json.load(open(os.path.join(root, "gpurun_out", "bench_detail.json")))
     assert detail["roofline"]["hbm"]["bound"] == "hbm" and len(json.dumps(a)) < 4096
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """a plain `bench.py` run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes the last
+    step's (map, ap_sum, cap) as float64, equal to one scan of the same seeded inputs in this process"""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    Q, Rn = 300, 20000
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--Q", str(Q), "--R", str(Rn),
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "pairs/s"
+    assert not any(k in line for k in ("roofline", "cpu_baseline", "gpu_over_cpu", "build")) and line["summary"] == {}
+    got = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in ("map", "ap_sum", "cap")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["map"].shape == (1,) and got["ap_sum"].shape == (Q,) and got["cap"].shape == (Q,)
+    spec = importlib.util.spec_from_file_location("xmh_bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from xmh import retrieval as R
+    qB, qL, _, _ = bench.synth(Q, 8, 64, 80, seed=1814, p=0.04)
+    _, _, rB, rL = bench.synth(8, Rn, 64, 80, seed=1815, p=0.04)
+    whole = R.RankingScan(R.pack_sign(qB.cuda()), R.pack_labels(qL.cuda()), R.pack_sign(rB.cuda()), R.pack_labels(rL.cuda()), 80)
+    whole.histograms(False)
+    m, ap, cap = (t.cpu().numpy() for t in whole.map_all(None))
+    assert abs(got["map"][0] - m[0]) < 1e-9 and np.array_equal(got["cap"], cap.astype(np.float64))
+    assert np.allclose(got["ap_sum"], ap, rtol=1e-6, atol=1e-9)
 
 
 def test_bench_two_ranks_sharing_the_gpu():
@@ -228,7 +262,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     Q, Rn = 300, 20000
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--settle", "0", "--Q", str(Q),
-           "--R", str(Rn), "--no-cpu-baseline", "--no-hbm-regime", "--no-encode"]
+           "--R", str(Rn), "--no-cpu-baseline", "--no-hbm-regime", "--no-encode", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XMH_BENCH_CHILD")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -540,7 +574,7 @@ def test_bench_eight_ranks_sharing_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     world, Q, Rn = 8, 296, 9000
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--share-gpu", "--steps", "2", "--warmup", "1", "--settle", "0", "--Q", str(Q),
-           "--R", str(Rn), "--no-cpu-baseline", "--no-hbm-regime", "--no-encode"]
+           "--R", str(Rn), "--no-cpu-baseline", "--no-hbm-regime", "--no-encode", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XMH_BENCH_CHILD")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

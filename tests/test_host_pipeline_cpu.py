@@ -1,7 +1,7 @@
 """CPU: the host side of the evaluation input pipeline -- the CLIP BPE tokenizer against token ids produced by
 the reference's SimpleTokenizer (oracle/make_golden_tokenizer.py), and the .mat-driven dataset mirror on a tiny
-generated dataset.  The BPE merge table is a data file of the reference that this repository does not ship: the tokenizer
-tests run where it can be found (the build container) and skip elsewhere."""
+generated dataset.  The BPE merge table is the reference's, cut to the merges CLIP's vocabulary uses
+(tests/golden/bpe_simple_vocab_16e6_clip.txt.gz, oracle/make_golden_tokenizer.py)."""
 import os
 
 import numpy as np
@@ -10,16 +10,13 @@ import torch
 
 from conftest import GOLDEN
 
-VOCAB_CANDIDATES = [os.environ.get("XMH_BPE_VOCAB"), "/root/reference/models/CLIP/bpe_simple_vocab_16e6.txt.gz"]
+VOCAB = os.path.join(GOLDEN, "bpe_simple_vocab_16e6_clip.txt.gz")
 
 
 @pytest.fixture(scope="module")
 def tok():
     from xmh.dataset.tokenizer import ClipTokenizer
-    for c in VOCAB_CANDIDATES:
-        if c and os.path.isfile(c):
-            return ClipTokenizer(c)
-    pytest.skip("bpe_simple_vocab_16e6.txt.gz not available here")
+    return ClipTokenizer(VOCAB)
 
 
 def test_tokenizer_is_registered_like_the_reference(monkeypatch, tmp_path):

@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(GOLDEN, "preprocess.npz"))
+    g = dict(np.load(os.path.join(GOLDEN, "preprocess.npz")))
+    g.update(np.load(os.path.join(GOLDEN, "preprocess_resized.npz")))
+    return g
 
 
 def test_oracle_resize_is_pillow_bit_exact(gold):

@@ -4,7 +4,7 @@
 #   gpurun -- bash tools/pmc_scan_ab.sh      -> gpurun_out/scan_ab_pmc.txt
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp XMH_SCAN_M2_SELFCHECK=0
-CMD="python bench.py --no-encode --no-hbm-regime --no-extra-configs --no-cpu-baseline --steps 20 --warmup 3 --settle 10"
+CMD="python bench.py --full --no-encode --no-hbm-regime --no-extra-configs --no-cpu-baseline --steps 20 --warmup 3 --settle 10"
 OUT=/tmp/pmc_ab; rm -rf $OUT; mkdir -p $OUT gpurun_out
 for mode in 1 0; do
   export XMH_SCAN_AP_R2=$mode

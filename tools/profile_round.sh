@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/profile_$TAG
 rm -rf $OUT; mkdir -p $OUT
-CMD="python bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+CMD="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"
 # the counter passes leave the extra scan legs out: they launch some of the headline's kernel instances at OTHER shapes (k_scan_ap_c<false>
 # serves 16- and 64-bit codes alike), and a per-launch average over mixed shapes is nobody's number
 PMC_CMD="$CMD --no-extra-configs"

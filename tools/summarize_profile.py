@@ -81,7 +81,7 @@ for k, e in res["pmc"].items():
         e["hbm_bytes_per_launch"] = {"fetch_raw": f, "write_raw": w, "fetch_correction": corr, "total": f * corr + w}
 json.dump(res, open(os.path.join(out, "summary_%s.json" % tag), "w"), indent=1)
 with open(os.path.join(out, "summary_%s.md" % tag), "w") as md:
-    md.write("# rocprofv3 summary %s\n\ncommand: `python bench.py --steps 20 --warmup 3 --no-cpu-baseline` under `rocprofv3 --kernel-trace --stats` and separate `--pmc` passes\n\n" % tag)
+    md.write("# rocprofv3 summary %s\n\ncommand: `python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline` under `rocprofv3 --kernel-trace --stats` and separate `--pmc` passes\n\n" % tag)
     md.write("## kernel stats (top by total time; steady = mean of the last 20 launches)\n\n| kernel | calls | avg us | steady us | min us | max us | % |\n|---|---|---|---|---|---|---|\n")
     for r in res["kernel_stats"]:
         md.write("| %s | %d | %.2f | %.2f | %.2f | %.2f | %.2f |\n" % (r["name"], r["calls"], r["avg_ns"] / 1e3, r.get("steady_avg_ns", float("nan")) / 1e3,
