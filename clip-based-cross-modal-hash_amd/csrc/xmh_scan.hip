@@ -1122,9 +1122,12 @@ constexpr int slots_for(int W, bool tern, int counter_bytes) {
     while (S < cap && nbmax * (64 / S) * counter_bytes > budget) S *= 2;
     return S;
 }
+// code words of the instance a length runs on: 1, 2, 4, 8, 16, 32, 64 (retrieval.widened pads the others)
+inline int instance_words(int W) { return W <= 1 ? 1 : (W <= 2 ? 2 : (W <= 4 ? 4 : (W <= 8 ? 8 : (W <= 16 ? 16 : (W <= 32 ? 32 : 64))))); }
 // the pair cache of k_scan_hist_s: two code words, binary, four slots in both passes and both counter widths
+constexpr bool pair_cache_shape(int W, bool tern) { return !tern && (W == 1 || W == 2 || W == 4 || W == 8); }
 template <int W, bool TERN>
-constexpr bool kPairCacheShape = !TERN && (W == 1 || W == 2 || W == 4 || W == 8);
+constexpr bool kPairCacheShape = pair_cache_shape(W, TERN);
 // ... and the slots both passes run with when the cache is in use: 4 x 16 queries with one-byte entries up to 64 bits (for codes of at
 // most 32 bits that is NOT the geometry the uncached kernels pick, 2 x 32), 8 x 8 queries with two-byte entries beyond
 constexpr int cache_slots(int W) { return W <= 2 ? 4 : 8; }
@@ -1143,34 +1146,40 @@ struct WsLayout {
 //   binary, 65 .. 128      k_scan_hist_r2w           one-byte pair cache -> k_scan_ap_c<., 8, HALF>; a distance of 128 wraps: stand-in k_scan_ap_s
 //   binary, 129 .. 256     k_scan_hist_b             two-byte pair cache -> cached k_scan_ap_s
 //   anything else, more than 128 classes, XMH_SCAN_MFMA=0, a failed self-check or lane-order probe: k_scan_hist_s / k_scan_ap_s (VALU)
+// One function decides it for a call: scan_route (below), for both passes and for xmh_scan_describe; pass1_family is the part the plan
+// depends on.
 // k_scan_hist_r2 / r2w keep hazards the compiler cannot see apart by hand (s_nop counts, early-clobber operands, statement order: see
 // the kernel), each of which was a wrong result on hardware before it was a comment.  A hipcc or ROCm change could break one of them
 // silently, so the kernels have to EARN their place once per device and process: r2_selfcheck_ok runs a small scan (several chunks,
 // ties, every geometry) with and without them and compares histograms and divisors bit for bit, AP sums to float rounding; a mismatch
 // prints one line to stderr and every later plan of this process uses the VALU kernels, as XMH_SCAN_MFMA=0 does.
-// XMH_SCAN_M2_SELFCHECK=0 skips it, =2 runs it and pretends it failed (the test of the fallback); g_r2_force pins the answer while the
-// check itself runs.
-static thread_local int g_r2_force = -1;
+// XMH_SCAN_M2_SELFCHECK=0 skips it, =2 runs it and pretends it failed (the test of the fallback); its own evaluations pin the answer
+// with Overrides::mfma.
 bool r2_selfcheck_ok();
 inline bool mfma_env_on() {                              // read per call: the tests compare the two families in one process
     const char* e = getenv("XMH_SCAN_MFMA");
     return !(e && atoi(e) == 0);
 }
-inline bool r2_enabled() {
-    if (g_r2_force >= 0) return g_r2_force != 0;
-    return mfma_env_on() && r2_selfcheck_ok();
+struct Overrides {            // what internal callers pin instead of the environment, the self-check and the lane-order probe
+    int mfma = -1;            // -1: XMH_SCAN_MFMA and the self-check decide; 0: VALU pass 1 (and its plan); 1: the MFMA kernels unchecked (the self-check's own run)
+    bool masked = false;      // the kernels that do not rely on the lane order (xmh_scan_verify's re-derivation)
+    bool describe = false;    // xmh_scan_describe: lane order assumed (no probe), code words widened to an instance's count as retrieval.widened does
+};
+// Pass-1 kernel family of a shape.  k_scan_hist_b (xmh_scan_bits.hip, round 3): 129..256-bit binary codes build their MFMA operands from the
+// packed bits in registers; counters in the (all << 16 | relevant) form of k_scan_hist_r2.  Compiler-scheduled intrinsics: no hand-kept
+// hazard, no self-check.  Round 6: TERNARY codes (up to 256 bits: every length the zero planes exist for) on the same kernel
+// (k_scan_hist_b<., ., ., TERN>): the operand is the 2K-bit pair of planes [+1 | -1], 2K + 1 bucket rows, two-byte cache entries -- so
+// pass 2 is that of the 129..256-bit binary codes.  Before: the VALU kernels (one exact 0.0 among the code elements cost 2.7 x the binary
+// evaluation).
+enum class Family { kValu, kR2, kR2w, kBits, kTBits };
+Family pass1_family(int K, bool ternary, const Overrides& ov) {
+    if (ov.mfma == 0 || !mfma_env_on()) return Family::kValu;
+    if (ternary) return K <= 256 ? Family::kTBits : Family::kValu;
+    if (K > 128) return K <= 256 ? Family::kBits : Family::kValu;
+    if (ov.mfma < 0 && !r2_selfcheck_ok()) return Family::kValu;
+    return K <= 64 ? Family::kR2 : Family::kR2w;
 }
-inline bool r2_shape(int K, bool ternary) { return !ternary && K <= 64 && r2_enabled(); }
-inline bool r2w_shape(int K, bool ternary) { return !ternary && K > 64 && K <= 128 && r2_enabled(); }
-// k_scan_hist_b (xmh_scan_bits.hip, round 3): 129..256-bit binary codes build their MFMA operands from the packed bits in registers;
-// counters in the (all << 16 | relevant) form of k_scan_hist_r2.  Compiler-scheduled intrinsics: no hand-kept hazard, no self-check.
-inline bool bits_shape(int K, bool ternary) { return !ternary && K > 128 && K <= 256 && mfma_env_on() && g_r2_force != 0; }
-// Round 6: TERNARY codes (up to 256 bits: every length the zero planes exist for) on the same kernel (k_scan_hist_b<., ., ., TERN>): the operand is the 2K-bit pair of planes
-// [+1 | -1], 2K + 1 bucket rows, two-byte cache entries -- so pass 2 is that of the 129..256-bit binary codes.  Before: the VALU kernels
-// (one exact 0.0 among the code elements cost 2.7 x the binary evaluation).
-inline bool tbits_shape(int K, bool ternary) { return ternary && K <= 256 && mfma_env_on() && g_r2_force != 0; }
 inline int tbits_tiles(int K) { return K <= 64 ? 2 : (K <= 128 ? 4 : 8); }      // 64-bit tiles of the 2K-bit operand
-inline bool mfma_shape(int K, bool ternary) { return r2_shape(K, ternary) || r2w_shape(K, ternary) || bits_shape(K, ternary) || tbits_shape(K, ternary); }
 // k_scan_ap_r2 (round 5): pass 2 evaluates the pairs again on the MFMA from the packed words instead of reading a pair cache (binary codes
 // of at most 64 bits whose pass 1 is k_scan_hist_r2).  Measured at Q 5000 x R 117 218 x 64 bit: pass 1 without the cache stores 0.157 ->
 // 0.128 ms, pass 2 0.173 (k_scan_ap_c on the cache) -> 0.262 ms, step 0.361 -> 0.416 ms -- so it is the pass 2 of evaluations that HAVE no
@@ -1208,11 +1217,11 @@ inline bool ap_c_on() {                                  // XMH_SCAN_AP_C=0: the
     const char* e = getenv("XMH_SCAN_AP_C");
     return !(e && atoi(e) == 0);
 }
-size_t pair_cache_bytes(const xmh_scan_plan& p, int K, bool ternary) {
+size_t pair_cache_bytes(const xmh_scan_plan& p, int K, bool ternary, Family f) {
     const long long cap_mb = cache_cap_mb();
-    const bool tb = tbits_shape(K, ternary);                        // ternary on the MFMA: two-byte entries, 8 slots (as 129..256-bit binary codes)
-    if ((ternary && !tb) || K > 256 || cap_mb <= 0 || (!tb && K <= 32 && !r2_shape(K, ternary))) return 0;
-    if (r2_shape(K, ternary) && ap_r2_mode() == 1) return 0;        // k_scan_ap_r2 evaluates the pairs itself
+    const bool tb = f == Family::kTBits;                            // ternary on the MFMA: two-byte entries, 8 slots (as 129..256-bit binary codes)
+    if ((ternary && !tb) || K > 256 || cap_mb <= 0 || (!tb && K <= 32 && f != Family::kR2)) return 0;
+    if (f == Family::kR2 && ap_r2_mode() == 1) return 0;            // k_scan_ap_r2 evaluates the pairs itself
     const int S = tb ? 8 : (K <= 64 ? 4 : 8);                      // slots of the kernels that use it: 64 / S queries per wave
     // records of 64 lanes per (chunk, tile of 64 / S queries, batch of 64 items): 16 B per lane for one-byte entries (S = 4), 12 B per lane for the
     // 12-bit entries of longer and of ternary codes (S = 8; xmh_common.h) -- 65..128-bit codes whose one-byte entries k_scan_hist_r2w writes use
@@ -1246,23 +1255,23 @@ WsLayout ws_layout(const xmh_scan_plan& p, size_t cache_bytes) {
 // The cache a call may use given the workspace it was handed: the plan's, or none when the caller's buffer ends in front of it (a device
 // that has no room for Q x R bytes next to a resident encoder: xmh_scan_ws_bytes_nocache).  Both calls of a pair see the same ws_bytes
 // and so take the same decision -- no process-wide state (round 4 lowered XMH_SCAN_CACHE_MB in the environment for this: ADVICE r4).
-size_t cache_for_workspace(const xmh_scan_plan& p, int K, bool ternary, size_t ws_bytes) {
-    const size_t c = pair_cache_bytes(p, K, ternary);
+size_t cache_for_workspace(const xmh_scan_plan& p, int K, bool ternary, Family f, size_t ws_bytes) {
+    const size_t c = pair_cache_bytes(p, K, ternary, f);
     return c && ws_bytes < ws_layout(p, c).total ? 0 : c;
 }
 
-int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p) {
+int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p, const Overrides& ov = {}) {
     if (Q <= 0 || R <= 0 || K <= 0) return xmh::fail(XMH_EINVAL, "scan plan: bad shape Q=%lld R=%lld K=%d", (long long)Q, (long long)R, K);
     if (R >= (1ll << 24) || Q >= (1ll << 24)) return xmh::fail(XMH_ENOTSUP, "scan plan: shard too large (R=%lld, Q=%lld)", (long long)R, (long long)Q);
     const int64_t nb = ternary ? 2 * (int64_t)K + 1 : (int64_t)K + 1;
     const int Wd = (K + 31) / 32;
     if (Wd > 64 || (ternary && Wd > 8))
         return xmh::fail(XMH_ENOTSUP, "scan plan: K=%d%s (at most 2048 code bits, 256 with zero planes)", K, ternary ? " ternary" : "");
-    const int Wc = Wd <= 1 ? 1 : (Wd <= 2 ? 2 : (Wd <= 4 ? 4 : (Wd <= 8 ? 8 : (Wd <= 16 ? 16 : (Wd <= 32 ? 32 : 64)))));
-    const int S64 = slots_for(Wc, ternary != 0, 8);
+    const int S64 = slots_for(instance_words(Wd), ternary != 0, 8);
     const int64_t lds_ap = nb * (64 / S64) * 8;
     if (lds_ap > 150 * 1024) return xmh::fail(XMH_ENOTSUP, "scan plan: %lld distance buckets need %lld B of LDS per wave; K=%d%s", (long long)nb, (long long)lds_ap, K, ternary ? " ternary" : "");
-    const bool r2 = r2_shape(K, ternary != 0) || r2w_shape(K, ternary != 0);
+    const Family fam = pass1_family(K, ternary != 0, ov);
+    const bool r2 = fam == Family::kR2 || fam == Family::kR2w;
     int64_t nqt = xmh::ceil_div(Q, 64);
     const int r2q = r2_geom(K).queries();
     if (r2) {                                     // whole blocks of k_scan_hist_r2 AND whole 64-query tiles
@@ -1280,7 +1289,7 @@ int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p) {
     const int64_t rounds = nb <= 33 ? 3 : (nb <= 65 && !cache_shape ? 2 : 1);
     int64_t nchunk = rounds * slots / nqt;
     if (S64 > 8) nchunk = nchunk * 8 / S64;       // long codes: S waves per tile already fill the slots; fewer chunks = smaller tables
-    const bool mfma = mfma_shape(K, ternary != 0);
+    const bool mfma = fam != Family::kValu;
     if (mfma) {
         // k_scan_hist_b: 257 (513) bucket rows: three sets of blocks (COCO shape, sets 2 / 3 / 4 / 6: ternary 128 bit 0.93 / 0.78 / 0.83 / 0.83 ms, 256-bit
         // binary 0.85 / 0.73 / 0.75 / 0.76); ternary codes of at most 64 bits have 129 rows and smaller tables: six (0.65 -> 0.62 ms)
@@ -1314,20 +1323,18 @@ int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p) {
     p->nqtile = nqt;
     p->qpad = nqt * 64;
     p->nbuckets = nb;
-    p->ws_bytes = ws_layout(*p, pair_cache_bytes(*p, K, ternary != 0)).total;
+    p->ws_bytes = ws_layout(*p, pair_cache_bytes(*p, K, ternary != 0, fam)).total;
     return XMH_OK;
 }
 
 // 1 if same-address returning LDS adds of one instruction come back in ascending lane order on this device (probed once
 // per process with a 1-wave kernel and one blocking copy), 0 otherwise or when XMH_SCAN_MASKED is set
-static thread_local bool g_force_masked = false;      // xmh_scan_verify: the re-derivation runs the kernels that do not rely on the lane order
 int lane_order_ok(hipStream_t st) {
     static int cached[64];
     static bool have[64];
     static std::mutex mu;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (g_force_masked) return 0;
     if (getenv("XMH_SCAN_MASKED") != nullptr) return 0;           // read per call: the self-check test runs both paths in one process
     std::lock_guard<std::mutex> lock(mu);
     if (have[dev]) return cached[dev];
@@ -1367,92 +1374,7 @@ struct DevBuf {
     bool alloc(size_t n) { return hipMalloc(&p, n) == hipSuccess; }
     template <typename T> T* as() { return static_cast<T*>(p); }
 };
-// one (K, forced kernel choice) evaluation of the self-check scan into host vectors; false on any HIP / library error
-bool selfcheck_eval(int K, int force, const std::vector<uint32_t>& qb, const std::vector<uint32_t>& ql, const std::vector<uint32_t>& rb,
-                    const std::vector<uint32_t>& rl, int64_t Q, int64_t R, int C, std::vector<uint32_t>& hist, std::vector<double>& ap,
-                    std::vector<int32_t>& cap) {
-    g_r2_force = force;
-    bool ok = false;
-    do {
-        xmh_scan_plan p;
-        if (xmh_scan_plan_make(Q, R, K, 0, &p) != XMH_OK) break;
-        const size_t nb = (size_t)p.nbuckets;
-        DevBuf dq, dql, dr, drl, ws, dh, dap, dcap;
-        if (!dq.alloc(qb.size() * 4) || !dql.alloc(ql.size() * 4) || !dr.alloc(rb.size() * 4) || !drl.alloc(rl.size() * 4) || !ws.alloc(p.ws_bytes) ||
-            !dh.alloc(2 * Q * nb * 4) || !dap.alloc(Q * 8) || !dcap.alloc(Q * 4))
-            break;
-        if (hipMemcpy(dq.p, qb.data(), qb.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dql.p, ql.data(), ql.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dr.p, rb.data(), rb.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(drl.p, rl.data(), rl.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            break;
-        uint32_t* h = dh.as<uint32_t>();
-        if (xmh_hamming_hist(dq.as<uint32_t>(), nullptr, dql.as<uint32_t>(), dr.as<uint32_t>(), nullptr, drl.as<uint32_t>(), Q, R, K, C, ws.p, p.ws_bytes, h, h + Q * nb,
-                             nullptr) != XMH_OK)
-            break;
-        if (xmh_hamming_ap(dq.as<uint32_t>(), nullptr, dql.as<uint32_t>(), dr.as<uint32_t>(), nullptr, drl.as<uint32_t>(), Q, R, K, C, ws.p, p.ws_bytes, nullptr, nullptr,
-                           nullptr, 0, dap.as<double>(), dcap.as<int32_t>(), nullptr) != XMH_OK)
-            break;
-        hist.resize(2 * Q * nb); ap.resize(Q); cap.resize(Q);
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(hist.data(), dh.p, hist.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ap.data(), dap.p, Q * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(cap.data(), dcap.p, Q * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            break;
-        ok = true;
-    } while (false);
-    g_r2_force = -1;
-    return ok;
-}
 }  // namespace
-
-bool r2_selfcheck_ok() {
-    static int state[64];                                 // 0 unknown, 1 passed, 2 failed
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;     // no device: nothing can run, nothing to guard
-    const char* e = getenv("XMH_SCAN_M2_SELFCHECK");
-    if (e && atoi(e) == 0) return true;
-    std::lock_guard<std::mutex> lock(mu);
-    if (state[dev]) return state[dev] == 1;
-    state[dev] = 1;                                       // the evaluations below re-enter through g_r2_force only
-    const int64_t Q = 200, R = 9000;
-    const int C = 80, LW = 3;
-    bool same = true, ran = true;
-    for (int K : {64, 40, 16, 100}) {                     // two code words, one + a partial one, <= 32 bits (all k_scan_hist_r2), 65..128 bits (k_scan_hist_r2w)
-        const int W = (K + 31) / 32;
-        std::vector<uint32_t> qb(Q * W), ql(Q * LW), rb(R * W), rl(R * LW);
-        uint64_t x = 0x9E3779B97F4A7C15ull ^ (uint64_t)K;
-        auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (uint32_t)(x >> 16); };
-        const uint32_t last = K % 32 ? (1u << (K % 32)) - 1 : 0xffffffffu;
-        for (auto& v : qb) v = rnd();
-        for (int64_t i = 0; i < R; ++i)                   // a quarter of the gallery repeats earlier codes: ties inside and across chunks
-            for (int w = 0; w < W; ++w) rb[i * W + w] = (i > 64 && (rnd() & 3) == 0) ? rb[(rnd() % 64) * W + w] : rnd();
-        for (int64_t i = 0; i < Q; ++i) qb[i * W + W - 1] &= last;
-        for (int64_t i = 0; i < R; ++i) rb[i * W + W - 1] &= last;
-        for (int64_t i = 0; i < Q * LW; ++i) ql[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
-        for (int64_t i = 0; i < R * LW; ++i) rl[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
-        for (int64_t i = 0; i < Q; ++i) ql[i * LW] |= 1u;                            // every query has a relevant item
-        for (int64_t i = 0; i < R; i += 7) rl[i * LW] |= 1u;
-        std::vector<uint32_t> h1, h0;
-        std::vector<double> a1, a0;
-        std::vector<int32_t> c1, c0;
-        if (!selfcheck_eval(K, 1, qb, ql, rb, rl, Q, R, C, h1, a1, c1) || !selfcheck_eval(K, 0, qb, ql, rb, rl, Q, R, C, h0, a0, c0)) { ran = false; break; }
-        // histograms and divisors bit for bit; the two kernels chunk the gallery differently, so pass 2's per-chunk float partial sums
-        // add in another order: the AP sums to float rounding (a wrong pair moves one by >= 1 / R relative, far above it)
-        bool ap_close = true;
-        for (int64_t i = 0; i < Q; ++i) ap_close = ap_close && fabs(a1[i] - a0[i]) <= 4e-6 * fabs(a0[i]) + 1e-9;
-        if (h1 != h0 || c1 != c0 || !ap_close) { same = false; break; }
-    }
-    if (e && atoi(e) == 2) same = false;
-    if (!ran) {                                           // out of memory or a launch failure: no verdict, do not cache one
-        state[dev] = 0;
-        return true;
-    }
-    if (!same) {
-        state[dev] = 2;
-        fprintf(stderr, "xmh: k_scan_hist_r2 self-check FAILED on device %d (results differ from the VALU kernels): falling back to the VALU scan "
-                        "for this process.  Please report the hipcc / ROCm versions.\n", dev);
-    }
-    return state[dev] == 1;
-}
 
 template <bool TERN, typename F>
 int dispatch_shape(int W, int LW, F&& f) {
@@ -1473,6 +1395,152 @@ int dispatch_shape(int W, int LW, F&& f) {
 #undef XMH_CASE
     return xmh::fail(XMH_ENOTSUP, "scan: unsupported shape W=%d code words (K in {<=32,64,128,256}, binary also 512,1024,2048), Lw=%d label words (C<=128; binary codes up to 256 bits also exactly 8 words: 129..256 classes)%s",
                      W, LW, TERN ? ", ternary" : "");
+}
+
+// Width of the rank field of the packed 32-bit pass-2 counters for an UNSHARDED evaluation of this shape, 0 = only the 64-bit kernels
+// are launched.
+int packed_rank_bits(int K, int64_t R) {
+    // XMH_SCAN_PACK32: "0" = never, "all" = every code length (tests); default: from 65 bits on (measured at Q 5000 x R 117 218, sparse
+    // relevance, pass 2 packed / 64-bit: K=16 0.275 / 0.251 ms, K=32 0.278 / 0.253, K=64 0.199 / 0.195, K=128 0.274 / 0.286, K=256 0.347 / 0.412)
+    const char* e = getenv("XMH_SCAN_PACK32");
+    if (e && e[0] == '0') return 0;
+    if (!(K > 64 || (e && e[0] == 'a'))) return 0;
+    const int64_t rank_max = R + 2;
+    int rank_bits = 0;
+    while ((1ll << rank_bits) < rank_max) ++rank_bits;
+    return rank_bits > 24 ? 0 : rank_bits;
+}
+
+// ---- the route of a call: every kernel instance of both passes, decided in one place ---------------------------------------------
+// xmh_hamming_hist, hamming_ap_impl and xmh_scan_describe all read it: pass 2 reads a pair cache exactly when pass 1 wrote one, and the
+// kernel name the bench looks up in a profile is the kernel that ran (a separate mirror had drifted from the launches twice).
+// Mode: where pass 2's offsets come from -- k_scan_below of the same workspace (unsharded), the caller (xmh_hamming_ap's base_all), the
+// gathered totals tables of the shards (xmh_hamming_map_sharded), the all-to-all slices (xmh_hamming_map_sharded_offsets).
+enum class Mode { kUnsharded, kBaseAll, kTotals, kAllToAll };
+enum class Kern { kHistS, kHistR2, kHistR2w, kHistB, kApS, kApC, kApR2 };
+// device words that make a pass-2 launch return at once because another launch of the call takes the work
+enum Gate : unsigned {
+    kBySize = 1,     // the gallery size over all shards (word 2, from the offsets kernels): float-bit counters or the k_scan_ap_s behind them
+    kByWrap = 2,     // kGateWrapped: k_scan_hist_r2w wrapped a distance of 128 in a one-byte entry; k_scan_ap_c returns, its stand-in runs
+    kByWidth = 4,    // nrel_max against rank_bits: exactly one of the packed 32-bit and the 64-bit counter launches runs
+};
+struct Launch {                     // one kernel instance, template arguments as xmh_scan_describe prints them
+    Kern kern = Kern::kHistS;
+    int W = 0, LW = 0;              // code / label words the launch dispatches on (dispatch_shape)
+    bool tern = false, cache = false;
+    int S = 0, NW = 1;              // VALU kernels: slots, waves per block; k_scan_hist_r2 / r2w / ap_r2: query groups per wave, waves; k_scan_hist_b: code tiles
+    int nml = 0;                    // k_scan_hist_r2 / r2w / ap_r2: label tiles
+    int eb = 0; bool half = false;  // k_scan_ap_c: entry bits (8: one byte, 16: the 12-bit entries of the two-byte layout); 8 slots x 8 queries on one-byte entries
+    bool p32 = false, masked = false;
+    unsigned gate = 0;
+    bool stand_in = false;          // launched behind k_scan_ap_c for wrapped entries (it runs once in a blue moon): not described
+};
+struct ScanRoute {
+    Launch p1;
+    size_t cache_bytes = 0;         // the pair cache pass 1 writes and pass 2 reads; 0 = none
+    int rank_bits = 0;              // rank field of the packed pass-2 counters handed to the launches (0: 64-bit counters only)
+    Launch p2[3];                   // pass 2 in launch order
+    int n2 = 0;
+};
+
+ScanRoute scan_route(const xmh_scan_plan& p, int K, int C, bool tern, int64_t R, size_t ws_bytes, Mode mode, const Overrides& ov, hipStream_t st) {
+    ScanRoute r;
+    const Family fam = pass1_family(K, tern, ov);
+    const int W = ov.describe ? instance_words((K + 31) / 32) : (K + 31) / 32, LW = (C + 31) / 32;
+    const bool lane_ok = ov.describe || (!ov.masked && lane_order_ok(st));
+    r.cache_bytes = cache_for_workspace(p, K, tern, fam, ws_bytes);
+    const bool cache = r.cache_bytes != 0;
+    const bool mfma = fam != Family::kValu && LW <= 4 && lane_ok;          // pass 1 on the matrix cores
+    Launch& h = r.p1;
+    h.W = W; h.LW = LW; h.tern = tern; h.cache = cache; h.nml = LW <= 2 ? 1 : 2;
+    if (!mfma) {
+        h.cache = cache && pair_cache_shape(W, tern);
+        h.S = h.cache ? cache_slots(W) : slots_for(W, tern, 4);
+        h.NW = h.S == 64 ? waves_for(W, tern) : 1;
+    } else if (fam == Family::kBits || fam == Family::kTBits) {
+        h.kern = Kern::kHistB;
+        h.S = fam == Family::kTBits ? tbits_tiles(K) : 4;
+    } else {
+        const R2Geom g = r2_geom(K);
+        h.kern = fam == Family::kR2 ? Kern::kHistR2 : Kern::kHistR2w;
+        h.NW = g.nw; h.S = g.nq;
+    }
+    const bool sharded = mode != Mode::kUnsharded;
+    const bool masked = !lane_ok;
+    const int rank_bits = sharded || masked ? 0 : packed_rank_bits(K, R);   // (the masked fallback has 64-bit counters only)
+    const bool fits_fb = sharded || R <= kFloatBitsMaxItems;               // float-bit counters: sharded, the size word decides on the device
+    const bool apc_on = ap_c_on();
+    // 65..128-bit codes whose pass 1 left ONE-byte entries (k_scan_hist_r2w): k_scan_ap_c reads them like those of shorter codes, 8 slots x 8
+    // queries wide; the cached k_scan_ap_s cannot.  A distance of 128 does not fit a byte and wrapped; pass 1 raised a control word then,
+    // k_scan_ap_c returns at once and the kernel that evaluates the pairs from the codes (the stand-in, gated the other way) takes the call.
+    const bool byte128 = cache && mfma && fam == Family::kR2w;
+    // ternary codes whose pass 1 left two-byte entries: the cached pass-2 kernels read nothing but the entries and the tables, so the BINARY
+    // 256-bit instances serve (the bucket count comes from the plan)
+    const bool tb = cache && mfma && fam == Family::kTBits;
+    // k_scan_ap_c (float-bit counters): pair cache, 64-bit counters, lane order, and the gallery over ALL shards small enough; the caller-
+    // offsets form stays on k_scan_ap_s except on one-byte entries of 65..128-bit codes (k_scan_dpre leaves the largest rank in the word)
+    const bool apc = cache && apc_on && (byte128 || (K <= 64 && rank_bits == 0)) && !tern && !masked && (mode != Mode::kBaseAll || byte128) && fits_fb;
+    // k_scan_ap_r2: no pair cache, the pairs evaluated again on the MFMA from the packed words
+    const bool apr2 = !cache && mfma && fam == Family::kR2 && ap_r2_mode() != 0 && !masked && mode != Mode::kBaseAll && rank_bits == 0 && fits_fb;
+    // Round 6: 129..256-bit codes (two-byte entries) on k_scan_ap_c<., 16>, the 64-bit pass 2 of unsharded calls.  Where the shard is too large
+    // or too relevant for packed 32-bit counters -- configs[4]: a shard of 1.25 M rows, 150 k relevant items per query -- it replaced the
+    // integer-counter k_scan_ap_s (15 VALU instructions per pair; k_scan_ap_c: 9)
+    const bool apc16 = cache && apc_on && ((K > 128 && K <= 256 && !tern) || tb) && !masked && !sharded && R <= kFloatBitsMaxItems;
+    const unsigned size_gate = sharded && (apc || apr2) ? kBySize : 0u;
+    r.rank_bits = byte128 && apc ? 0 : rank_bits;                           // behind k_scan_ap_c<., 8, true> only the 64-bit stand-in
+    auto add = [&](Kern kern, unsigned gate) -> Launch& { Launch& l = r.p2[r.n2++]; l.kern = kern; l.gate = gate; return l; };
+    if (apc) {
+        Launch& l = add(Kern::kApC, size_gate | (byte128 ? kByWrap : 0u));
+        l.eb = 8; l.half = byte128;
+    }
+    if (apr2) {
+        Launch& l = add(Kern::kApR2, size_gate);
+        l.W = W; l.LW = LW; l.nml = h.nml; l.NW = kAp2Waves; l.S = kAp2Groups;
+    }
+    if (apc16) add(Kern::kApC, kByWidth).eb = 16;
+    if ((apc || apr2) && !size_gate && !byte128) return r;                  // k_scan_ap_c / k_scan_ap_r2 alone takes the call
+    Launch s;                                                               // k_scan_ap_s: both counter widths where packed ones apply
+    s.kern = Kern::kApS; s.W = tb ? 8 : W; s.LW = LW; s.tern = tern && !tb; s.masked = masked;
+    s.cache = cache && !byte128 && !masked && pair_cache_shape(s.W, s.tern);
+    s.stand_in = byte128 && apc;
+    s.gate = size_gate | (s.stand_in ? kByWrap : 0u) | (r.rank_bits ? kByWidth : 0u);
+    for (const bool p32 : {true, false}) {
+        if (p32 ? r.rank_bits == 0 : apc16) continue;                       // (k_scan_ap_c<., 16> is the 64-bit pass 2 of that shape)
+        s.p32 = p32;
+        s.S = s.cache ? cache_slots(s.W) : slots_for(s.W, s.tern, p32 ? 4 : 8);
+        s.NW = s.S == 64 ? waves_for(s.W, s.tern) : 1;
+        r.p2[r.n2++] = s;
+    }
+    return r;
+}
+
+// a launch of the route as rocprofv3 prints the instance (minus the namespace) for an uncapped call; XMH_ENOTSUP where dispatch_shape has none
+int describe_launch(const Launch& l, char* out, size_t n) {
+    static const char* const tf[2] = {"false", "true"};
+    auto exists = [&](auto tern_c) { return dispatch_shape<decltype(tern_c)::value>(l.W, l.LW, [](auto, auto) { return (int)XMH_OK; }); };
+    switch (l.kern) {
+    case Kern::kHistS:
+    case Kern::kApS:
+        if (const int rc = l.tern ? exists(std::true_type{}) : exists(std::false_type{})) return rc;
+        if (l.kern == Kern::kHistS) snprintf(out, n, "k_scan_hist_s<%d, %d, %s, %d, %d, %s>", l.W, l.LW, tf[l.tern], l.S, l.NW, tf[l.cache]);
+        else                                // the cached kernel reads no label word; the uncached ones exist in the capped form only
+            snprintf(out, n, "k_scan_ap_s<%d, %d, %s, %s, %d, %s, %s, %d, %s>", l.W, l.cache ? 1 : l.LW, tf[l.tern], tf[!l.cache], l.S, tf[l.p32], tf[l.masked],
+                     l.NW, tf[l.cache]);
+        break;
+    case Kern::kHistR2:
+    case Kern::kHistR2w:
+        snprintf(out, n, "k_scan_hist_%s<%d, %d, %d, %s>", l.kern == Kern::kHistR2 ? "r2" : "r2w", l.nml, l.NW, l.S, tf[l.cache]);
+        break;
+    case Kern::kHistB: {
+        int nsh, nqt;
+        xmh::scan_hist_bits_shape(l.S, l.tern, &nsh, &nqt);
+        snprintf(out, n, "k_scan_hist_b<%d, %d, %d, %d, %s, %s>", l.S, kMfmaWaves, nsh, nqt, tf[l.cache], tf[l.tern]);
+        break;
+    }
+    case Kern::kApC: snprintf(out, n, "k_scan_ap_c<false, %d, %s>", l.eb, tf[l.half]); break;
+    case Kern::kApR2: snprintf(out, n, "k_scan_ap_r2<%d, %d, %d, false>", l.nml, l.NW, l.S); break;
+    }
+    return XMH_OK;
 }
 
 int check_common(const char* who, const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
@@ -1519,61 +1587,35 @@ MfmaArgs r2_args(const uint32_t* qbits, const uint32_t* qlab, const uint32_t* rb
     return a;
 }
 
-// binary codes of at most 64 bits: k_scan_hist_r2 in the plan's geometry (r2_geom)
-template <int NML, int NW, int NQ>
-int hist_r2_t(const MfmaArgs& a, const xmh_scan_plan& p, uint32_t* chunk_hist, uint4* cache, hipStream_t st) {
-    const dim3 grid((unsigned)(8 * a.nqt * xmh::ceil_div(p.nchunk, 8)));
-    const size_t lds = (size_t)NW * NQ * p.nbuckets * 16 * 4;
-    xmh::ProfScope prof("scan_hist", st);
-    auto go = [&](auto kern) {
-        const int r2 = raise_lds(kern, lds, "xmh_hamming_hist");
-        if (r2) return r2;
-        hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, a, chunk_hist, cache);
-        return (int)XMH_OK;
-    };
-    return cache ? go(k_scan_hist_r2<NML, NW, NQ, true>) : go(k_scan_hist_r2<NML, NW, NQ, false>);
-}
-
-// 65..128 bits: k_scan_hist_r2w (4 waves x 2 query groups)
-template <int NML>
-int hist_r2w_t(const MfmaArgs& a, const xmh_scan_plan& p, char* base, const WsLayout& L, uint32_t* chunk_hist, uint4* cache, hipStream_t st) {
-    constexpr int NW = 4, NQ = 2;
-    const dim3 grid((unsigned)(8 * a.nqt * xmh::ceil_div(p.nchunk, 8)));
-    const size_t lds = (size_t)NW * NQ * p.nbuckets * 16 * 4;
+int mfma_hist(const Launch& h, const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits, const uint32_t* rzero,
+              const uint32_t* rlab, int64_t Q, int64_t R, int K, const xmh_scan_plan& p, char* base, const WsLayout& L, uint32_t* chunk_hist,
+              uint4* cache, hipStream_t st) {
+    if (h.kern == Kern::kHistB) {
+        XMH_HIP(hipMemsetAsync(base + L.tick, 0, L.gate + 256 - L.tick, st));       // the control words of the call
+        xmh::ScanBitsArgs a{rbits, rlab, qbits, qlab, (int)Q, (int)R, K, h.W, h.LW, (int)p.chunk, (int)p.nchunk, (int)(p.qpad / (16 * kMfmaWaves)),
+                            (int)p.nbuckets, (int)p.qpad};
+        a.rzero = rzero;                                             // ternary codes: the zero planes (null for binary ones)
+        a.qzero = qzero;
+        return xmh::launch_scan_hist_bits(a, h.S, chunk_hist, cache, st);
+    }
+    launch_touch(rbits, rlab, R, h.W, h.LW, p, base, L, st);
+    XMH_LAUNCH_CHECK("xmh_hamming_hist control words");
+    // k_scan_hist_r2 (at most 64 bits: 4 waves x 4 query groups) / k_scan_hist_r2w (65..128 bits: 4 x 2), the geometry of r2_geom
+    const MfmaArgs a = r2_args(qbits, qlab, rbits, rlab, Q, R, K, h.W, h.LW, p, h.NW * h.S * 16);
+    const size_t lds = (size_t)h.NW * h.S * p.nbuckets * 16 * 4;
     uint32_t* ovf = reinterpret_cast<uint32_t*>(base + L.gate) + kGateWrapped;
     xmh::ProfScope prof("scan_hist", st);
-    auto go = [&](auto kern) {
+    auto go = [&](auto kern, auto... wrap_word) {
         const int r2 = raise_lds(kern, lds, "xmh_hamming_hist");
         if (r2) return r2;
-        hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, a, chunk_hist, cache, ovf);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(8 * a.nqt * xmh::ceil_div(p.nchunk, 8))), dim3(64 * h.NW), lds, st, a, chunk_hist, cache, wrap_word...);
         return (int)XMH_OK;
     };
-    return cache ? go(k_scan_hist_r2w<NML, NW, NQ, true>) : go(k_scan_hist_r2w<NML, NW, NQ, false>);
-}
-
-int mfma_hist(const uint32_t* qbits, const uint32_t* qlab, const uint32_t* rbits, const uint32_t* rlab, int64_t Q, int64_t R, int K, int W, int LW,
-              const xmh_scan_plan& p, char* base, const WsLayout& L, uint32_t* chunk_hist, uint4* cache, hipStream_t st,
-              const uint32_t* qzero = nullptr, const uint32_t* rzero = nullptr) {
-    if (qzero) {                                                     // tbits_shape: ternary codes, K <= 256
-        XMH_HIP(hipMemsetAsync(base + L.tick, 0, L.gate + 256 - L.tick, st));       // the control words of the call
-        xmh::ScanBitsArgs a{rbits, rlab, qbits, qlab, (int)Q, (int)R, K, W, LW, (int)p.chunk, (int)p.nchunk, (int)(p.qpad / (16 * kMfmaWaves)),
-                            (int)p.nbuckets, (int)p.qpad};
-        a.rzero = rzero;
-        a.qzero = qzero;
-        return xmh::launch_scan_hist_bits(a, tbits_tiles(K), chunk_hist, cache, st);
-    }
-    if (bits_shape(K, false)) {
-        XMH_HIP(hipMemsetAsync(base + L.tick, 0, L.gate + 256 - L.tick, st));       // the control words of the call
-        const xmh::ScanBitsArgs a{rbits, rlab, qbits, qlab, (int)Q, (int)R, K, W, LW, (int)p.chunk, (int)p.nchunk, (int)(p.qpad / (16 * kMfmaWaves)),
-                                  (int)p.nbuckets, (int)p.qpad};
-        return xmh::launch_scan_hist_bits(a, 4, chunk_hist, cache, st);
-    }
-    launch_touch(rbits, rlab, R, W, LW, p, base, L, st);
-    XMH_LAUNCH_CHECK("xmh_hamming_hist control words");
-    const R2Geom g = r2_geom(K);
-    const MfmaArgs a = r2_args(qbits, qlab, rbits, rlab, Q, R, K, W, LW, p, g.queries());
-    if (K > 64) return LW <= 2 ? hist_r2w_t<1>(a, p, base, L, chunk_hist, cache, st) : hist_r2w_t<2>(a, p, base, L, chunk_hist, cache, st);
-    return LW <= 2 ? hist_r2_t<1, 4, 4>(a, p, chunk_hist, cache, st) : hist_r2_t<2, 4, 4>(a, p, chunk_hist, cache, st);
+    if (h.kern == Kern::kHistR2w)
+        return h.nml == 1 ? (cache ? go(k_scan_hist_r2w<1, 4, 2, true>, ovf) : go(k_scan_hist_r2w<1, 4, 2, false>, ovf))
+                          : (cache ? go(k_scan_hist_r2w<2, 4, 2, true>, ovf) : go(k_scan_hist_r2w<2, 4, 2, false>, ovf));
+    return h.nml == 1 ? (cache ? go(k_scan_hist_r2<1, 4, 4, true>) : go(k_scan_hist_r2<1, 4, 4, false>))
+                      : (cache ? go(k_scan_hist_r2<2, 4, 4, true>) : go(k_scan_hist_r2<2, 4, 4, false>));
 }
 
 }  // namespace
@@ -1586,13 +1628,13 @@ extern "C" int xmh_scan_plan_make(int64_t Q, int64_t R, int K, int ternary, xmh_
 extern "C" size_t xmh_scan_pair_cache_bytes(int64_t Q, int64_t R, int K, int ternary) {
     xmh_scan_plan p;
     if (make_plan(Q, R, K, ternary, &p)) return 0;
-    return pair_cache_bytes(p, K, ternary != 0);
+    return pair_cache_bytes(p, K, ternary != 0, pass1_family(K, ternary != 0, {}));
 }
 
 extern "C" size_t xmh_scan_pair_cache_offset(int64_t Q, int64_t R, int K, int ternary) {
     xmh_scan_plan p;
     if (make_plan(Q, R, K, ternary, &p)) return (size_t)-1;
-    return ws_layout(p, pair_cache_bytes(p, K, ternary != 0)).pair_cache;
+    return ws_layout(p, 0).pair_cache;                                  // (the cache is the last region: its size moves nothing)
 }
 
 // The workspace of the same plan WITHOUT the pair cache: a caller whose device has no room for xmh_scan_plan.ws_bytes (Q x R bytes of
@@ -1604,129 +1646,62 @@ extern "C" size_t xmh_scan_ws_bytes_nocache(int64_t Q, int64_t R, int K, int ter
     return ws_layout(p, 0).total;
 }
 
-// Width of the rank field of the packed 32-bit pass-2 counters for an UNSHARDED evaluation of this shape, 0 = only the 64-bit kernels
-// are launched.  One function for the launch path (hamming_ap_impl) and for xmh_scan_describe, so that the kernel name the bench looks
-// up in a profile is the kernel that ran (the two had drifted apart on XMH_SCAN_NO_PACK32).
-int packed_rank_bits(int K, int64_t R) {
-    // XMH_SCAN_PACK32: "0" = never, "all" = every code length (tests); default: from 65 bits on (measured at Q 5000 x R 117 218, sparse
-    // relevance, pass 2 packed / 64-bit: K=16 0.275 / 0.251 ms, K=64 0.199 / 0.195, K=128 0.274 / 0.286, K=256 0.347 / 0.412)
-    const char* e = getenv("XMH_SCAN_PACK32");
-    if (e && e[0] == '0') return 0;
-    if (!(K > 64 || (e && e[0] == 'a'))) return 0;
-    const int64_t rank_max = R + 2;
-    int rank_bits = 0;
-    while ((1ll << rank_bits) < rank_max) ++rank_bits;
-    return rank_bits > 24 ? 0 : rank_bits;
-}
-
 // Which kernel instances an UNSHARDED mAP@all evaluation of this shape launches for the two passes (as rocprofv3 prints them, minus
 // the namespace): bench_roofline.py picks the PMC rows of exactly these -- a prefix match once took the 128-bit kernel's row for
-// the 64-bit headline.  Mirrors the dispatch of xmh_hamming_hist / hamming_ap_impl (lane order assumed to hold).
+// the 64-bit headline.  The route of the launches themselves (lane order assumed to hold, the plan's whole workspace); where both
+// counter widths are launched, both names, packed first.
 extern "C" int xmh_scan_describe(int64_t Q, int64_t R, int K, int C, int ternary, char* out, size_t out_bytes) {
     if (!out || out_bytes < 64) return xmh::fail(XMH_EINVAL, "xmh_scan_describe: buffer too small");
     xmh_scan_plan p;
-    const int rc = make_plan(Q, R, K, ternary, &p);
-    if (rc) return rc;
-    const bool tern = ternary != 0;
-    const int Wd = (K + 31) / 32, LW = (C + 31) / 32;
-    const int Wc = Wd <= 1 ? 1 : (Wd <= 2 ? 2 : (Wd <= 4 ? 4 : (Wd <= 8 ? 8 : (Wd <= 16 ? 16 : (Wd <= 32 ? 32 : 64)))));
-    const size_t cache = pair_cache_bytes(p, K, tern);
-    const bool use_mfma = mfma_shape(K, tern) && LW <= 4;
-    char p1[160], p2[200];
-    const int NML = LW <= 2 ? 1 : 2;
-    const int S4 = slots_for(Wc, tern, 4), S8 = slots_for(Wc, tern, 8);
-    const R2Geom g = r2_geom(K);
-    if (use_mfma && r2w_shape(K, tern)) snprintf(p1, sizeof(p1), "k_scan_hist_r2w<%d, %d, %d, %s>", NML, g.nw, g.nq, cache ? "true" : "false");
-    else if (use_mfma && r2_shape(K, tern)) snprintf(p1, sizeof(p1), "k_scan_hist_r2<%d, %d, %d, %s>", NML, g.nw, g.nq, cache ? "true" : "false");
-    else if (use_mfma && tbits_shape(K, tern)) {
-        int nsh, nqt;
-        xmh::scan_hist_bits_shape(tbits_tiles(K), true, &nsh, &nqt);
-        snprintf(p1, sizeof(p1), "k_scan_hist_b<%d, %d, %d, %d, %s, true>", tbits_tiles(K), kMfmaWaves, nsh, nqt, cache ? "true" : "false");
-    }
-    else if (use_mfma) {
-        int nsh, nqt;
-        xmh::scan_hist_bits_shape(4, false, &nsh, &nqt);
-        snprintf(p1, sizeof(p1), "k_scan_hist_b<4, %d, %d, %d, %s, false>", kMfmaWaves, nsh, nqt, cache ? "true" : "false");
-    }
-    else {
-        const bool cached = cache && !tern && Wc <= 8;
-        const int S = cached ? cache_slots(Wc) : S4;
-        snprintf(p1, sizeof(p1), "k_scan_hist_s<%d, %d, %s, %d, %d, %s>", Wc, LW, tern ? "true" : "false", S, S == 64 ? waves_for(Wc, tern) : 1,
-                 cached ? "true" : "false");
-    }
-    const bool packable = packed_rank_bits(K, R) > 0;                 // exactly what hamming_ap_impl launches for an unsharded evaluation
-    const bool apc_on = ap_c_on();
-    const bool byte128 = cache && use_mfma && r2w_shape(K, tern);     // one-byte entries of 65..128-bit codes
-    const bool tb = tern && cache && use_mfma && tbits_shape(K, tern);  // ternary on the MFMA: the cached pass 2 of the 129..256-bit binary codes
-    if (tb) {
-        snprintf(p2, sizeof(p2), "%s%s", packable ? "k_scan_ap_s<8, 1, false, false, 8, true, false, 1, true>|" : "",
-                 apc_on && R <= kFloatBitsMaxItems ? "k_scan_ap_c<false, 16, false>" : "k_scan_ap_s<8, 1, false, false, 8, false, false, 1, true>");
-    } else if (cache && !tern && K <= 128 && apc_on && (byte128 || (K <= 64 && !packable)) && R <= kFloatBitsMaxItems) {
-        snprintf(p2, sizeof(p2), "k_scan_ap_c<false, 8, %s>", byte128 ? "true" : "false");     // all three template arguments: the name a profile prints
-    } else if (use_mfma && !cache && r2_shape(K, tern) && ap_r2_mode() != 0 && !packable && R <= kFloatBitsMaxItems) {
-        snprintf(p2, sizeof(p2), "k_scan_ap_r2<%d, %d, %d, false>", NML, kAp2Waves, kAp2Groups);
-    } else {
-        const bool cached = cache && !tern && Wc <= 8;
-        // codes of 65 bits and more launch both counter widths, a device word picks one: both names, packed first
-        char a32[96] = "";
-        if (packable) {
-            const int S = cached ? cache_slots(Wc) : S4;
-            snprintf(a32, sizeof(a32), "k_scan_ap_s<%d, %d, %s, %s, %d, true, false, %d, %s>|", Wc, cached ? 1 : LW, tern ? "true" : "false", cached ? "false" : "true", S,
-                     S == 64 ? waves_for(Wc, tern) : 1, cached ? "true" : "false");
+    if (const int rc = make_plan(Q, R, K, ternary, &p)) return rc;
+    Overrides ov;
+    ov.describe = true;
+    const ScanRoute r = scan_route(p, K, C, ternary != 0, R, p.ws_bytes, Mode::kUnsharded, ov, nullptr);
+    char p1[160], p2[200] = "", one[120];
+    if (const int rc = describe_launch(r.p1, p1, sizeof(p1))) return rc;
+    for (const bool p32 : {true, false})
+        for (int i = 0; i < r.n2; ++i) {
+            if (r.p2[i].stand_in || r.p2[i].p32 != p32) continue;
+            if (const int rc = describe_launch(r.p2[i], one, sizeof(one))) return rc;
+            const size_t at = strlen(p2);
+            snprintf(p2 + at, sizeof(p2) - at, "%s%s", at ? "|" : "", one);
         }
-        const int S = cached ? cache_slots(Wc) : S8;
-        if (cache && apc_on && K > 128 && K <= 256 && !tern && R <= kFloatBitsMaxItems)      // round 6: float-bit counters on two-byte entries
-            snprintf(p2, sizeof(p2), "%sk_scan_ap_c<false, 16, false>", a32);
-        else
-        snprintf(p2, sizeof(p2), "%sk_scan_ap_s<%d, %d, %s, %s, %d, false, false, %d, %s>", a32, Wc, cached ? 1 : LW, tern ? "true" : "false", cached ? "false" : "true", S,
-                 S == 64 ? waves_for(Wc, tern) : 1, cached ? "true" : "false");     // (uncached kernels: the capped form serves both)
-    }
     if ((size_t)snprintf(out, out_bytes, "pass1=%s;pass2=%s", p1, p2) >= out_bytes) return xmh::fail(XMH_EINVAL, "xmh_scan_describe: buffer too small");
     return XMH_OK;
 }
 
-extern "C" int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
-                                const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R,
-                                int K, int C, void* ws, size_t ws_bytes, uint32_t* hist_all, uint32_t* hist_rel,
-                                xmh_stream_t stream) {
-    XMH_RANGE("xmh_hamming_hist (pass 1)");
+namespace {
+int hamming_hist_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits, const uint32_t* rzero,
+                      const uint32_t* rlab, int64_t Q, int64_t R, int K, int C, void* ws, size_t ws_bytes, uint32_t* hist_all, uint32_t* hist_rel,
+                      xmh_stream_t stream, const Overrides& ov) {
     const bool tern = qzero != nullptr;
     xmh_scan_plan p;
-    int rc = make_plan(Q, R, K, tern, &p);
+    int rc = make_plan(Q, R, K, tern, &p, ov);
     if (rc) return rc;
     rc = check_common("xmh_hamming_hist", qbits, qzero, qlab, rbits, rzero, rlab, C, ws, ws_bytes, p);
     if (rc) return rc;
+    hipStream_t st = xmh::as_stream(stream);
+    const ScanRoute r = scan_route(p, K, C, tern, R, ws_bytes, Mode::kUnsharded, ov, st);
+    const Launch& h = r.p1;
+    const bool use_mfma = h.kern != Kern::kHistS;
     const ScanArgs a = make_args(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, p);
-    const size_t cache_bytes = cache_for_workspace(p, K, tern, ws_bytes);
-    const bool mfma_plan = mfma_shape(K, tern);
-    const WsLayout L = ws_layout(p, cache_bytes);
+    const WsLayout L = ws_layout(p, r.cache_bytes);
     char* base = static_cast<char*>(ws);
     uint32_t* chunk_hist = reinterpret_cast<uint32_t*>(base + L.chunk_hist);
     uint2* below = reinterpret_cast<uint2*>(base + L.below);
     uint2* tot = reinterpret_cast<uint2*>(base + L.tot);
-    hipStream_t st = xmh::as_stream(stream);
-    const int W = (K + 31) / 32, LW = (C + 31) / 32;
-    const bool use_mfma = mfma_plan && LW <= 4 && lane_order_ok(st);
-    // the tile tickets of k_scan_below, the nrel_max gate word and the finalize ticket of the evaluation calls on this workspace
-    if (!use_mfma) XMH_HIP(hipMemsetAsync(base + L.tick, 0, L.gate + 256 - L.tick, st));   // (the MFMA path clears them in its first launch)
-    if (use_mfma) {
-        rc = mfma_hist(qbits, qlab, rbits, rlab, Q, R, K, W, LW, p, base, L, chunk_hist,
-                       cache_bytes ? reinterpret_cast<uint4*>(base + L.pair_cache) : nullptr, st, qzero, rzero);
-        if (rc) return rc;
-    }
     auto launch = [&](auto tern_c) {
         constexpr bool T = decltype(tern_c)::value;
-        return dispatch_shape<T>(W, LW, [&](auto w, auto l) {
+        return dispatch_shape<T>(h.W, h.LW, [&](auto w, auto l) {
             constexpr int WW = decltype(w)::value, LL = decltype(l)::value;
             constexpr int S = slots_for(WW, T, 4);
             constexpr int NW = S == 64 ? waves_for(WW, T) : 1;
-            constexpr bool CAN = kPairCacheShape<WW, T>;           // the shape the pair cache is laid out for
             const size_t lds = (((size_t)p.nbuckets * (64 / S) + 3) & ~(size_t)3) * 4 * NW + aos_ring_bytes(WW, LL, T);
             ScanArgs as = a;
             as.nqt = a.nqt * S / NW;                              // tiles of (64/S) * NW queries
             xmh::ProfScope prof("scan_hist", st);
-            if constexpr (CAN) {
-                if (cache_bytes) {
+            if constexpr (kPairCacheShape<WW, T>) {               // the shape the pair cache is laid out for
+                if (h.cache) {
                     constexpr int SC = cache_slots(WW);
                     auto kc = k_scan_hist_s<WW, LL, T, SC, 1, true>;
                     const size_t ldsc = (((size_t)p.nbuckets * (64 / SC) + 3) & ~(size_t)3) * 4 + aos_ring_bytes(WW, LL, T);
@@ -1745,10 +1720,16 @@ extern "C" int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, co
             return (int)XMH_OK;
         });
     };
-    if (!use_mfma) {
+    if (use_mfma) {
+        rc = mfma_hist(h, qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, p, base, L, chunk_hist,
+                       r.cache_bytes ? reinterpret_cast<uint4*>(base + L.pair_cache) : nullptr, st);
+    } else {
+        // the tile tickets of k_scan_below, the nrel_max gate word and the finalize ticket of the evaluation calls on this workspace (the
+        // MFMA path clears them in its first launch)
+        XMH_HIP(hipMemsetAsync(base + L.tick, 0, L.gate + 256 - L.tick, st));
         rc = tern ? launch(std::true_type{}) : launch(std::false_type{});
-        if (rc) return rc;
     }
+    if (rc) return rc;
     XMH_LAUNCH_CHECK("xmh_hamming_hist");
     hipLaunchKernelGGL(k_scan_below, dim3((unsigned)p.nqtile, (unsigned)xmh::ceil_div(p.nbuckets, 4)), dim3(256), 0, st, chunk_hist,
                        (int)p.qpad, (int)p.nbuckets, (int)p.nchunk, use_mfma ? kRelHi16 : 0u, below, tot,
@@ -1756,6 +1737,15 @@ extern "C" int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, co
                        reinterpret_cast<uint32_t*>(base + L.cap), reinterpret_cast<uint32_t*>(base + L.gate), hist_all, hist_rel);
     XMH_LAUNCH_CHECK("xmh_hamming_hist below");
     return XMH_OK;
+}
+}  // namespace
+
+extern "C" int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
+                                const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R,
+                                int K, int C, void* ws, size_t ws_bytes, uint32_t* hist_all, uint32_t* hist_rel,
+                                xmh_stream_t stream) {
+    XMH_RANGE("xmh_hamming_hist (pass 1)");
+    return hamming_hist_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, hist_all, hist_rel, stream, {});
 }
 
 namespace {
@@ -1766,14 +1756,13 @@ namespace {
 // the gallery differently, so pass 2's per-chunk fp32 partial sums add in another order; a wrong rank moves a sum by >= 1 / R relative).
 // Synchronises the stream -- a diagnostic for a new device / compiler, not something to leave on.
 static std::atomic<int> g_verify{0};
-static thread_local bool g_in_verify = false;
 constexpr int XMH_EVERIFY_CODE = -74;                 // EBADMSG: the two derivations disagree
 
 int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits,
                     const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R, int K, int C, void* ws,
                     size_t ws_bytes, const uint32_t* base_all, const uint32_t* base_rel,
                     const uint32_t* nrel_total, int64_t k, double* ap_sum, int32_t* cap, double* map_out, xmh_stream_t stream,
-                    const uint32_t* hist_g = nullptr, int world = 0, int rank = 0);
+                    const uint32_t* hist_g, int world, int rank, const Overrides& ov);
 
 int verify_against_masked(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits, const uint32_t* rzero,
                           const uint32_t* rlab, int64_t Q, int64_t R, int K, int C, int64_t k, const double* ap_sum, const int32_t* cap,
@@ -1784,22 +1773,18 @@ int verify_against_masked(const uint32_t* qbits, const uint32_t* qzero, const ui
     XMH_HIP(hipMemcpyAsync(a1.data(), ap_sum, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
     XMH_HIP(hipMemcpyAsync(c1.data(), cap, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
     XMH_HIP(hipStreamSynchronize(st));
-    struct Restore {
-        int r2; bool fm;
-        ~Restore() { g_r2_force = r2; g_force_masked = fm; g_in_verify = false; }
-    } restore{g_r2_force, g_force_masked};
-    g_in_verify = true;
-    g_force_masked = true;
-    g_r2_force = 0;                                       // VALU pass 1 too
+    Overrides ov;
+    ov.mfma = 0;                                          // VALU pass 1 too
+    ov.masked = true;
     xmh_scan_plan p;
-    if (const int rc = xmh_scan_plan_make(Q, R, K, qzero != nullptr, &p)) return rc;
-    const size_t small = xmh_scan_ws_bytes_nocache(Q, R, K, qzero != nullptr);      // without a pair cache: the re-derivation evaluates the pairs from the codes
+    if (const int rc = make_plan(Q, R, K, qzero != nullptr, &p, ov)) return rc;
+    const size_t small = ws_layout(p, 0).total;           // without a pair cache: the re-derivation evaluates the pairs from the codes
     DevBuf ws2, ap2, cap2;
-    if (small == 0 || !ws2.alloc(small) || !ap2.alloc((size_t)Q * 8) || !cap2.alloc((size_t)Q * 4))
+    if (!ws2.alloc(small) || !ap2.alloc((size_t)Q * 8) || !cap2.alloc((size_t)Q * 4))
         return xmh::fail(XMH_ENOMEM, "xmh_scan_verify: no room for the second evaluation (%zu bytes)", small);
-    if (const int rc = xmh_hamming_hist(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws2.p, small, nullptr, nullptr, stream)) return rc;
+    if (const int rc = hamming_hist_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws2.p, small, nullptr, nullptr, stream, ov)) return rc;
     if (const int rc = hamming_ap_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws2.p, small, nullptr, nullptr, nullptr, k, ap2.as<double>(),
-                                       cap2.as<int32_t>(), nullptr, stream))
+                                       cap2.as<int32_t>(), nullptr, stream, nullptr, 0, 0, ov))
         return rc;
     XMH_HIP(hipMemcpyAsync(a0.data(), ap2.p, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
     XMH_HIP(hipMemcpyAsync(c0.data(), cap2.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
@@ -1824,36 +1809,29 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
                     const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R, int K, int C, void* ws,
                     size_t ws_bytes, const uint32_t* base_all, const uint32_t* base_rel,
                     const uint32_t* nrel_total, int64_t k, double* ap_sum, int32_t* cap, double* map_out, xmh_stream_t stream,
-                    const uint32_t* hist_g, int world, int rank) {
+                    const uint32_t* hist_g, int world, int rank, const Overrides& ov) {
     const bool tern = qzero != nullptr;
     xmh_scan_plan p;
-    int rc = make_plan(Q, R, K, tern, &p);
+    int rc = make_plan(Q, R, K, tern, &p, ov);
     if (rc) return rc;
     rc = check_common("xmh_hamming_ap", qbits, qzero, qlab, rbits, rzero, rlab, C, ws, ws_bytes, p);
     if (rc) return rc;
     if (!ap_sum || !cap) return xmh::fail(XMH_EINVAL, "xmh_hamming_ap: null output");
     const int ext = (base_all != nullptr) + (base_rel != nullptr) + (nrel_total != nullptr);
     if (ext != 0 && ext != 3) return xmh::fail(XMH_EINVAL, "xmh_hamming_ap: base_all, base_rel and nrel_total go together");
+    const Mode mode = hist_g ? (rank < 0 ? Mode::kAllToAll : Mode::kTotals) : (base_all ? Mode::kBaseAll : Mode::kUnsharded);
+    const bool sharded = mode != Mode::kUnsharded;
+    hipStream_t st = xmh::as_stream(stream);
+    const ScanRoute r = scan_route(p, K, C, tern, R, ws_bytes, mode, ov, st);
     const ScanArgs a = make_args(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, p);
-    const size_t cache_bytes = cache_for_workspace(p, K, tern, ws_bytes);
-    const bool mfma_plan = mfma_shape(K, tern);
-    const WsLayout L = ws_layout(p, cache_bytes);
+    const WsLayout L = ws_layout(p, r.cache_bytes);
     char* base = static_cast<char*>(ws);
     const uint2* below = reinterpret_cast<const uint2*>(base + L.below);
     const uint2* tot = reinterpret_cast<const uint2*>(base + L.tot);
     uint2* dpre = reinterpret_cast<uint2*>(base + L.dpre);
     uint32_t* cap_ws = reinterpret_cast<uint32_t*>(base + L.cap);
     float* ap_part = reinterpret_cast<float*>(base + L.ap_part);
-    hipStream_t st = xmh::as_stream(stream);
     uint32_t* nrel_max = reinterpret_cast<uint32_t*>(base + L.gate);
-    // packed 32-bit counters apply to a single shard when rank fits rank_bits and the largest relevant count fits the rest
-    // Measured at Q 5000 x R 117 218, sparse relevance (the packed width applies), pass 2 packed / 64-bit: K=16 0.275 / 0.251 ms,
-    // K=32 0.278 / 0.253, K=64 0.199 / 0.195, K=128 0.274 / 0.286, K=256 0.347 / 0.412 -- packed counters pay from 65 bits on;
-    // below that only the 64-bit kernel is launched (and no gated launch returns at once); XMH_SCAN_PACK32_ALL=1 brings the packed
-    // kernels back for every length (tests).
-    const bool sharded = base_all != nullptr || hist_g != nullptr;
-    const bool masked = !lane_order_ok(xmh::as_stream(stream));
-    const int rank_bits = sharded || masked ? 0 : packed_rank_bits(K, R);      // (the masked fallback has 64-bit counters only)
     // unsharded: k_scan_below left dpre, nrel and the gate word behind (xmh_hamming_hist).  Sharded: the offsets come from the caller.
     if (hist_g && rank < 0) {                                        // the all-to-all form: this shard's offset rows, by slice owner
         const int S = (int)(p.qpad / world);
@@ -1870,83 +1848,54 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
         XMH_LAUNCH_CHECK("xmh_hamming_ap dpre");
     }
     const uint32_t kcap = k > 0 && k < (int64_t)0xffffffffll ? (uint32_t)k : 0xffffffffu;
-    const int W = (K + 31) / 32, LW = (C + 31) / 32;
     const bool capped = k > 0;
+    uint4* pair_cache = reinterpret_cast<uint4*>(base + L.pair_cache);
+    auto gate_word = [&](const Launch& l, unsigned g, int word) { return (l.gate & g) ? (const uint32_t*)(nrel_max + word) : (const uint32_t*)nullptr; };
 
-    // k_scan_ap_c (float-bit counters): one-byte pair cache present, 64-bit counters, lane order holds, and the gallery over ALL
-    // shards small enough -- known here for an unsharded call; for the totals-table form of the sharded call the offsets kernel leaves
-    // the size in a device word and both kernels are launched, each returning at once when it is the other's turn (as for the counter
-    // widths); the explicit-offsets form stays on k_scan_ap_s, except on one-byte entries
-    // of 65..128-bit codes (which that kernel cannot read), where k_scan_dpre leaves the largest rank of the shard in the word instead.
-    // XMH_SCAN_AP_C=0 turns it off.
-    const bool apc_on = ap_c_on();
-    // 65..128-bit codes whose pass 1 (k_scan_hist_r2w: the MFMA pass 1 ran iff the lane order holds and the labels fit -- the same predicate
-    // as in xmh_hamming_hist) left ONE-byte entries: k_scan_ap_c reads them like those of shorter codes, 8 slots x 8 queries wide.  A
-    // distance of 128 does not fit a byte and wrapped; pass 1 raised a control word then, k_scan_ap_c returns at once and the kernel that
-    // evaluates the pairs from the codes (launched behind it, gated the other way) takes the call.  The cached k_scan_ap_s cannot read
-    // these entries.
-    const bool byte128 = cache_bytes && mfma_plan && LW <= 4 && !masked && r2w_shape(K, tern);
-    const uint32_t* wrapped = byte128 ? (const uint32_t*)(nrel_max + kGateWrapped) : nullptr;
-    const size_t cache_s = byte128 ? 0 : cache_bytes;                 // what the k_scan_ap_s launches below may read
-    const bool apc = cache_bytes && apc_on && (byte128 || (K <= 64 && rank_bits == 0)) && !tern && !masked && (!base_all || byte128) &&
-                     (sharded || R <= kFloatBitsMaxItems);
-    const uint32_t* fb_gate = apc && sharded ? (const uint32_t*)(nrel_max + 2) : nullptr;      // (k_scan_ap_r2 sets it too, below)
-    if (apc) {
-        // one-byte entries are read 8 slots x 8 queries wide (k_scan_ap_c<., 8, HALF>) where the counter rows of 16 queries leave few waves per
-        // CU -- 65..128-bit codes (129 rows: 16.5 KB per wave); 16 / 64 / 128 bit, 4 x 16 against 8 x 8: 0.154 / 0.185, 0.171 / 0.182, 0.220 / 0.189 ms
-        const bool half = byte128;
-        const int SC = half ? 8 : 4;                                     // slots of the geometry pass 2 runs: 64 / SC queries per wave
+    // k_scan_ap_c (float-bit counters) on one-byte entries: 4 slots x 16 queries per wave, or 8 x 8 (k_scan_ap_c<., 8, HALF>) where the counter
+    // rows of 16 queries leave few waves per CU -- 65..128-bit codes (129 rows: 16.5 KB per wave); 16 / 64 / 128 bit, 4 x 16 against 8 x 8:
+    // 0.154 / 0.185, 0.171 / 0.182, 0.220 / 0.189 ms.  On the 12-bit entries of the two-byte layout: 8 x 8.
+    auto launch_c = [&](const Launch& l) {
+        const int SC = l.eb == 16 || l.half ? 8 : 4;                     // slots of the geometry pass 2 runs: 64 / SC queries per wave
         ScanArgs as = a;
         as.nqt = a.nqt * SC;
-        as.pair_cache = reinterpret_cast<uint4*>(base + L.pair_cache);
+        as.pair_cache = pair_cache;
         const size_t lds = (size_t)p.nbuckets * (64 / SC) * 8;
-        const dim3 grid((unsigned)(scan_grid(p) * SC));
         xmh::ProfScope prof("scan_ap", st);
         auto go = [&](auto kc) {
             const int r3 = raise_lds(kc, lds, "xmh_hamming_ap");
             if (r3) return r3;
-            hipLaunchKernelGGL(kc, grid, dim3(64), lds, st, as, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part, fb_gate, kcap, wrapped,
-                               (const uint32_t*)nullptr, 0);
+            hipLaunchKernelGGL(kc, dim3((unsigned)(scan_grid(p) * SC)), dim3(64), lds, st, as, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part,
+                               gate_word(l, kBySize, 2), kcap, gate_word(l, kByWrap, kGateWrapped), gate_word(l, kByWidth, 0), l.gate & kByWidth ? r.rank_bits : 0);
             return (int)XMH_OK;
         };
-        rc = half ? (capped ? go(k_scan_ap_c<true, 8, true>) : go(k_scan_ap_c<false, 8, true>)) : (capped ? go(k_scan_ap_c<true, 8>) : go(k_scan_ap_c<false, 8>));
-        if (rc) return rc;
-        XMH_LAUNCH_CHECK("xmh_hamming_ap (float-bit counters)");
-    }
-    // k_scan_ap_r2: no pair cache, the pairs evaluated again on the MFMA from the packed words (same gating by the size word as k_scan_ap_c)
-    const bool apr2 = !cache_bytes && mfma_plan && K <= 64 && r2_shape(K, tern) && ap_r2_mode() != 0 && LW <= 4 && !tern && !masked && !base_all &&
-                      rank_bits == 0 && (sharded || R <= kFloatBitsMaxItems);
-    if (apr2) {
-        fb_gate = sharded ? (const uint32_t*)(nrel_max + 2) : nullptr;
+        if (l.eb == 16) return capped ? go(k_scan_ap_c<true, 16>) : go(k_scan_ap_c<false, 16>);
+        return l.half ? (capped ? go(k_scan_ap_c<true, 8, true>) : go(k_scan_ap_c<false, 8, true>)) : (capped ? go(k_scan_ap_c<true, 8>) : go(k_scan_ap_c<false, 8>));
+    };
+    // k_scan_ap_r2: the pairs evaluated again on the MFMA from the packed words
+    auto launch_r2 = [&](const Launch& l) {
         constexpr int NW2 = kAp2Waves, NQ2 = kAp2Groups;
-        const MfmaArgs ma = r2_args(qbits, qlab, rbits, rlab, Q, R, K, W, LW, p, NW2 * NQ2 * 16);
+        const MfmaArgs ma = r2_args(qbits, qlab, rbits, rlab, Q, R, K, l.W, l.LW, p, NW2 * NQ2 * 16);
         const dim3 grid((unsigned)(8 * ma.nqt * xmh::ceil_div(p.nchunk, 8)));
         const size_t lds = (size_t)NW2 * NQ2 * p.nbuckets * 16 * 8;
         xmh::ProfScope prof("scan_ap", st);
         auto go = [&](auto kern) {
             const int r3 = raise_lds(kern, lds, "xmh_hamming_ap");
             if (r3) return r3;
-            hipLaunchKernelGGL(kern, grid, dim3(64 * NW2), lds, st, ma, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part, fb_gate, kcap);
+            hipLaunchKernelGGL(kern, grid, dim3(64 * NW2), lds, st, ma, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part, gate_word(l, kBySize, 2), kcap);
             return (int)XMH_OK;
         };
-        rc = LW <= 2 ? (capped ? go(k_scan_ap_r2<1, NW2, NQ2, true>) : go(k_scan_ap_r2<1, NW2, NQ2, false>))
-                     : (capped ? go(k_scan_ap_r2<2, NW2, NQ2, true>) : go(k_scan_ap_r2<2, NW2, NQ2, false>));
-        if (rc) return rc;
-        XMH_LAUNCH_CHECK("xmh_hamming_ap (MFMA from the packed words)");
-    }
-    // tb: ternary codes whose pass 1 ran on the MFMA (same predicate as in xmh_hamming_hist) and left two-byte entries: the cached pass-2
-    // kernels read nothing but the entries and the tables, so the BINARY 256-bit instances serve (the bucket count comes from the plan)
-    const bool tb = tern && cache_bytes && mfma_plan && LW <= 4 && !masked && tbits_shape(K, tern);
-    // behind k_scan_ap_c on one-byte entries of 65..128-bit codes only the 64-bit stand-in is launched (always valid; it runs once in a blue moon)
-    const int rb = (byte128 && apc) ? 0 : rank_bits;
-    // both counter widths are launched; the device word nrel_max (written by k_scan_dpre) lets exactly one of them run
-    auto launch = [&](auto tern_c, auto cap_c, auto p32_c, auto masked_c) {
+        return l.nml == 1 ? (capped ? go(k_scan_ap_r2<1, NW2, NQ2, true>) : go(k_scan_ap_r2<1, NW2, NQ2, false>))
+                          : (capped ? go(k_scan_ap_r2<2, NW2, NQ2, true>) : go(k_scan_ap_r2<2, NW2, NQ2, false>));
+    };
+    // k_scan_ap_s: the cached kernel or the one that evaluates the pairs from the codes, in one of the two counter widths
+    auto launch_s_t = [&](const Launch& l, auto tern_c, auto cap_c, auto p32_c, auto masked_c) {
         constexpr bool T = decltype(tern_c)::value;
         constexpr bool CP = decltype(cap_c)::value;
         constexpr bool P32 = decltype(p32_c)::value;
         constexpr bool MK = decltype(masked_c)::value;
-        return dispatch_shape<T>(tb ? 8 : W, LW, [&](auto w, auto l) {
-            constexpr int WW = decltype(w)::value, LL = decltype(l)::value;
+        return dispatch_shape<T>(l.W, l.LW, [&](auto w, auto lw) {
+            constexpr int WW = decltype(w)::value, LL = decltype(lw)::value;
             if constexpr (P32 && MK) return xmh::fail(XMH_ENOTSUP, "xmh_hamming_ap: the masked fallback runs 64-bit counters only");      // (never launched: rank_bits is 0 when masked)
             else {
             constexpr int S = slots_for(WW, T, P32 ? 4 : 8);
@@ -1957,7 +1906,7 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
             as.nqt = a.nqt * S / NW;
             xmh::ProfScope prof(P32 ? "scan_ap32" : "scan_ap", st);
             if constexpr (kPairCacheShape<WW, T> && !MK) {
-                if (cache_s) {                                        // pass 1 of this call pair left the pairs in the workspace
+                if (l.cache) {                                        // pass 1 of this call pair left the pairs in the workspace
                     constexpr int SC = cache_slots(WW);
                     auto kc = k_scan_ap_s<WW, 1, T, CP, SC, P32, MK, 1, true>;      // the cached kernel reads no label word: one instance for every class count
                     const size_t cellsc = (size_t)p.nbuckets * (64 / SC);
@@ -1965,9 +1914,9 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
                     const int r3 = raise_lds(kc, lds, "xmh_hamming_ap");
                     if (r3) return r3;
                     as.nqt = a.nqt * SC;
-                    as.pair_cache = reinterpret_cast<uint4*>(base + L.pair_cache);
+                    as.pair_cache = pair_cache;
                     hipLaunchKernelGGL(kc, dim3(scan_grid(p) * SC), dim3(64), lds, st, as, below, (const uint2*)dpre, (const uint32_t*)cap_ws,
-                                       ap_part, (const uint32_t*)nrel_max, rb, kcap, fb_gate, (const uint32_t*)nullptr);
+                                       ap_part, (const uint32_t*)nrel_max, r.rank_bits, kcap, gate_word(l, kBySize, 2), (const uint32_t*)nullptr);
                     return (int)XMH_OK;
                 }
             }
@@ -1977,55 +1926,25 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
             auto kern = k_scan_ap_s<WW, LL, T, true, S, P32, MK, NW, false>;
             const int r2 = raise_lds(kern, lds, "xmh_hamming_ap");
             if (r2) return r2;
-            // behind a launched k_scan_ap_c (one-byte entries of 65..128-bit codes): the stand-in, gated by the wrap word / the size word
-            const bool stand_in = byte128 && apc;
             hipLaunchKernelGGL(kern, dim3(scan_grid(p) * S / NW), dim3(64 * NW), lds, st, as, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part,
-                               (const uint32_t*)nrel_max, rb, kcap, stand_in || apr2 ? fb_gate : (const uint32_t*)nullptr, stand_in ? wrapped : (const uint32_t*)nullptr);
+                               (const uint32_t*)nrel_max, r.rank_bits, kcap, gate_word(l, kBySize, 2), gate_word(l, kByWrap, kGateWrapped));
             return (int)XMH_OK;
             }
         });
     };
-    // Round 6: 129..256-bit binary codes (two-byte entries).  Where the shard is too large or too relevant for packed 32-bit counters --
-    // configs[4]: a shard of 1.25 M rows, 150 k relevant items per query -- the 64-bit pass 2 was the integer-counter k_scan_ap_s (15 VALU
-    // instructions per pair); the float-bit counters of k_scan_ap_c (9) read the same entries 8 slots x 8 queries wide.  Unsharded calls.
-    const bool apc16 = cache_bytes && apc_on && ((K > 128 && K <= 256 && !tern) || tb) && !masked && !sharded && R <= kFloatBitsMaxItems;
-    if (apc16) {
-        ScanArgs as = a;
-        as.nqt = a.nqt * 8;
-        as.pair_cache = reinterpret_cast<uint4*>(base + L.pair_cache);
-        const size_t lds16 = (size_t)p.nbuckets * 8 * 8;
-        xmh::ProfScope prof("scan_ap", st);
-        auto go16 = [&](auto kc) {
-            const int r3 = raise_lds(kc, lds16, "xmh_hamming_ap");
-            if (r3) return r3;
-            hipLaunchKernelGGL(kc, dim3((unsigned)(scan_grid(p) * 8)), dim3(64), lds16, st, as, below, (const uint2*)dpre, (const uint32_t*)cap_ws, ap_part,
-                               (const uint32_t*)nullptr, kcap, (const uint32_t*)nullptr, (const uint32_t*)nrel_max, rank_bits);
-            return (int)XMH_OK;
-        };
-        rc = capped ? go16(k_scan_ap_c<true, 16>) : go16(k_scan_ap_c<false, 16>);
-        if (rc) return rc;
-        XMH_LAUNCH_CHECK("xmh_hamming_ap (float-bit counters, two-byte entries)");
-    }
-    if ((apc || apr2) && !fb_gate && !byte128) {
-        // k_scan_ap_c / k_scan_ap_r2 alone takes the call
-    } else {
-    using T1 = std::true_type;
-    using T0 = std::false_type;
-    auto launch_width = [&](auto p32_c) {
-        auto by_mask = [&](auto tern_c, auto cap_c) { return masked ? launch(tern_c, cap_c, p32_c, T1{}) : launch(tern_c, cap_c, p32_c, T0{}); };
-        if (tern && !tb) return capped ? by_mask(T1{}, T1{}) : by_mask(T1{}, T0{});
-        return capped ? by_mask(T0{}, T1{}) : by_mask(T0{}, T0{});
+    auto launch_s = [&](const Launch& l) {
+        using T1 = std::true_type;
+        using T0 = std::false_type;
+        auto by_mask = [&](auto t, auto c, auto w) { return l.masked ? launch_s_t(l, t, c, w, T1{}) : launch_s_t(l, t, c, w, T0{}); };
+        auto by_width = [&](auto t, auto c) { return l.p32 ? by_mask(t, c, T1{}) : by_mask(t, c, T0{}); };
+        auto by_cap = [&](auto t) { return capped ? by_width(t, T1{}) : by_width(t, T0{}); };
+        return l.tern ? by_cap(T1{}) : by_cap(T0{});
     };
-    if (rb) {
-        rc = launch_width(T1{});
-        if (rc) return rc;
-        XMH_LAUNCH_CHECK("xmh_hamming_ap packed");
-    }
-    if (!apc16) {                                                   // (k_scan_ap_c<., 16> above is the 64-bit pass 2 of that shape)
-        rc = launch_width(T0{});
+    for (int i = 0; i < r.n2; ++i) {
+        const Launch& l = r.p2[i];
+        rc = l.kern == Kern::kApC ? launch_c(l) : (l.kern == Kern::kApR2 ? launch_r2(l) : launch_s(l));
         if (rc) return rc;
         XMH_LAUNCH_CHECK("xmh_hamming_ap");
-    }
     }
     const unsigned nred = (unsigned)xmh::ceil_div(Q, 64);
     if (map_out && nred <= 4096) {                                   // reduce + mean in one launch (last-ticket block finalises)
@@ -2041,9 +1960,89 @@ int hamming_ap_impl(const uint32_t* qbits, const uint32_t* qzero, const uint32_t
             XMH_LAUNCH_CHECK("xmh_hamming_map finalize");
         }
     }
-    if (g_verify.load(std::memory_order_relaxed) && !g_in_verify && !sharded)
+    if (g_verify.load(std::memory_order_relaxed) && !ov.masked && !sharded)
         return verify_against_masked(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, k, ap_sum, cap, stream);
     return XMH_OK;
+}
+
+// one (K, pinned kernel choice) evaluation of the self-check scan into host vectors; false on any HIP / library error
+bool selfcheck_eval(int K, int force, const std::vector<uint32_t>& qb, const std::vector<uint32_t>& ql, const std::vector<uint32_t>& rb,
+                    const std::vector<uint32_t>& rl, int64_t Q, int64_t R, int C, std::vector<uint32_t>& hist, std::vector<double>& ap,
+                    std::vector<int32_t>& cap) {
+    Overrides ov;
+    ov.mfma = force;
+    xmh_scan_plan p;
+    if (make_plan(Q, R, K, 0, &p, ov) != XMH_OK) return false;
+    const size_t nb = (size_t)p.nbuckets;
+    DevBuf dq, dql, dr, drl, ws, dh, dap, dcap;
+    if (!dq.alloc(qb.size() * 4) || !dql.alloc(ql.size() * 4) || !dr.alloc(rb.size() * 4) || !drl.alloc(rl.size() * 4) || !ws.alloc(p.ws_bytes) ||
+        !dh.alloc(2 * Q * nb * 4) || !dap.alloc(Q * 8) || !dcap.alloc(Q * 4))
+        return false;
+    if (hipMemcpy(dq.p, qb.data(), qb.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dql.p, ql.data(), ql.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dr.p, rb.data(), rb.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(drl.p, rl.data(), rl.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    uint32_t* h = dh.as<uint32_t>();
+    if (hamming_hist_impl(dq.as<uint32_t>(), nullptr, dql.as<uint32_t>(), dr.as<uint32_t>(), nullptr, drl.as<uint32_t>(), Q, R, K, C, ws.p, p.ws_bytes, h, h + Q * nb,
+                          nullptr, ov) != XMH_OK)
+        return false;
+    if (hamming_ap_impl(dq.as<uint32_t>(), nullptr, dql.as<uint32_t>(), dr.as<uint32_t>(), nullptr, drl.as<uint32_t>(), Q, R, K, C, ws.p, p.ws_bytes, nullptr, nullptr,
+                        nullptr, 0, dap.as<double>(), dcap.as<int32_t>(), nullptr, nullptr, nullptr, 0, 0, ov) != XMH_OK)
+        return false;
+    hist.resize(2 * Q * nb); ap.resize(Q); cap.resize(Q);
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    return hipMemcpy(hist.data(), dh.p, hist.size() * 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(ap.data(), dap.p, Q * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(cap.data(), dcap.p, Q * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+bool r2_selfcheck_ok() {
+    static int state[64];                                 // 0 unknown, 1 passed, 2 failed
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;     // no device: nothing can run, nothing to guard
+    const char* e = getenv("XMH_SCAN_M2_SELFCHECK");
+    if (e && atoi(e) == 0) return true;
+    std::lock_guard<std::mutex> lock(mu);
+    if (state[dev]) return state[dev] == 1;
+    state[dev] = 1;                                       // the evaluations below pin Overrides::mfma and do not ask again
+    const int64_t Q = 200, R = 9000;
+    const int C = 80, LW = 3;
+    bool same = true, ran = true;
+    for (int K : {64, 40, 16, 100}) {                     // two code words, one + a partial one, <= 32 bits (all k_scan_hist_r2), 65..128 bits (k_scan_hist_r2w)
+        const int W = (K + 31) / 32;
+        std::vector<uint32_t> qb(Q * W), ql(Q * LW), rb(R * W), rl(R * LW);
+        uint64_t x = 0x9E3779B97F4A7C15ull ^ (uint64_t)K;
+        auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (uint32_t)(x >> 16); };
+        const uint32_t last = K % 32 ? (1u << (K % 32)) - 1 : 0xffffffffu;
+        for (auto& v : qb) v = rnd();
+        for (int64_t i = 0; i < R; ++i)                   // a quarter of the gallery repeats earlier codes: ties inside and across chunks
+            for (int w = 0; w < W; ++w) rb[i * W + w] = (i > 64 && (rnd() & 3) == 0) ? rb[(rnd() % 64) * W + w] : rnd();
+        for (int64_t i = 0; i < Q; ++i) qb[i * W + W - 1] &= last;
+        for (int64_t i = 0; i < R; ++i) rb[i * W + W - 1] &= last;
+        for (int64_t i = 0; i < Q * LW; ++i) ql[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
+        for (int64_t i = 0; i < R * LW; ++i) rl[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
+        for (int64_t i = 0; i < Q; ++i) ql[i * LW] |= 1u;                            // every query has a relevant item
+        for (int64_t i = 0; i < R; i += 7) rl[i * LW] |= 1u;
+        std::vector<uint32_t> h1, h0;
+        std::vector<double> a1, a0;
+        std::vector<int32_t> c1, c0;
+        if (!selfcheck_eval(K, 1, qb, ql, rb, rl, Q, R, C, h1, a1, c1) || !selfcheck_eval(K, 0, qb, ql, rb, rl, Q, R, C, h0, a0, c0)) { ran = false; break; }
+        // histograms and divisors bit for bit; the two kernels chunk the gallery differently, so pass 2's per-chunk float partial sums
+        // add in another order: the AP sums to float rounding (a wrong pair moves one by >= 1 / R relative, far above it)
+        bool ap_close = true;
+        for (int64_t i = 0; i < Q; ++i) ap_close = ap_close && fabs(a1[i] - a0[i]) <= 4e-6 * fabs(a0[i]) + 1e-9;
+        if (h1 != h0 || c1 != c0 || !ap_close) { same = false; break; }
+    }
+    if (e && atoi(e) == 2) same = false;
+    if (!ran) {                                           // out of memory or a launch failure: no verdict, do not cache one
+        state[dev] = 0;
+        return true;
+    }
+    if (!same) {
+        state[dev] = 2;
+        fprintf(stderr, "xmh: k_scan_hist_r2 self-check FAILED on device %d (results differ from the VALU kernels): falling back to the VALU scan "
+                        "for this process.  Please report the hipcc / ROCm versions.\n", dev);
+    }
+    return state[dev] == 1;
 }
 }  // namespace
 
@@ -2058,7 +2057,7 @@ extern "C" int xmh_hamming_ap(const uint32_t* qbits, const uint32_t* qzero, cons
                               const uint32_t* nrel_total, int64_t k, double* ap_sum, int32_t* cap, xmh_stream_t stream) {
     XMH_RANGE("xmh_hamming_ap (pass 2)");
     return hamming_ap_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, base_all, base_rel, nrel_total, k, ap_sum, cap,
-                           nullptr, stream);
+                           nullptr, stream, nullptr, 0, 0, {});
 }
 
 extern "C" int xmh_hamming_map(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits,
@@ -2067,15 +2066,14 @@ extern "C" int xmh_hamming_map(const uint32_t* qbits, const uint32_t* qzero, con
     XMH_RANGE("xmh_hamming_map (pass 2 + mean)");
     if (!map_out) return xmh::fail(XMH_EINVAL, "xmh_hamming_map: null output");
     return hamming_ap_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, nullptr, nullptr, nullptr, k, ap_sum, cap, map_out,
-                           stream);
+                           stream, nullptr, 0, 0, {});
 }
 
 extern "C" size_t xmh_scan_totals_offset(int64_t Q, int64_t R, int K, int ternary, size_t* bytes) {
     xmh_scan_plan p;
     if (make_plan(Q, R, K, ternary, &p)) return (size_t)-1;
-    const WsLayout L = ws_layout(p, pair_cache_bytes(p, K, ternary != 0));
     if (bytes) *bytes = (size_t)p.nbuckets * p.qpad * 8;
-    return L.tot;
+    return ws_layout(p, 0).tot;
 }
 
 extern "C" int xmh_hamming_map_sharded(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab, const uint32_t* rbits,
@@ -2086,7 +2084,7 @@ extern "C" int xmh_hamming_map_sharded(const uint32_t* qbits, const uint32_t* qz
     if (!hist_gathered || !map_partial) return xmh::fail(XMH_EINVAL, "xmh_hamming_map_sharded: null pointer");
     if (world <= 0 || rank < 0 || rank >= world) return xmh::fail(XMH_EINVAL, "xmh_hamming_map_sharded: bad world=%d rank=%d", world, rank);
     return hamming_ap_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, nullptr, nullptr, nullptr, k, ap_sum, cap, map_partial,
-                           stream, hist_gathered, world, rank);
+                           stream, hist_gathered, world, rank, {});
 }
 
 extern "C" int xmh_shard_slice_offsets(const uint32_t* totals_slices, int world, int nbuckets, int slice, uint32_t* offsets_out, xmh_stream_t stream) {
@@ -2110,7 +2108,7 @@ extern "C" int xmh_hamming_map_sharded_offsets(const uint32_t* qbits, const uint
     if (rc) return rc;
     if (world <= 0 || p.qpad % world) return xmh::fail(XMH_EINVAL, "xmh_hamming_map_sharded_offsets: qpad=%lld is not a multiple of world=%d", (long long)p.qpad, world);
     return hamming_ap_impl(qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, nullptr, nullptr, nullptr, k, ap_sum, cap, map_partial,
-                           stream, offsets, world, -1);
+                           stream, offsets, world, -1, {});
 }
 
 extern "C" int xmh_map_finalize(const double* ap_sum, const int32_t* cap, int64_t Q, double* map_out, xmh_stream_t stream) {
