@@ -1,0 +1,482 @@
+// HyP loss of DSPH (reference models/DSPH/loss/HyP.py:18-70) and its gradient with respect to the two code matrices and the proxies.
+//
+//   n(v) = v / max(|v|, 1e-12) (F.normalize), cos = n(x) n(P)^T, cos_t = n(y) n(P)^T, labels l packed by xmh_pack_labels
+//   pos = sum_{l=1} (1 - cos) / P_num          neg = sum_{l=0} relu(cos - thr) / N_num          (and _t on cos_t)
+//   alpha > 0: M = rows with >= 2 labels, Z = #ordered pairs of M x M with disjoint label sets,
+//              reg / reg_t / reg_xt = sum_{pairs} alpha relu(sim - thr) / Z with sim = cos of x-x / y-y / x-y; 0 when Z == 0
+//
+//   xmh_hyp_loss       k_hyp_rows<true>  (one block per code row: its sums over the proxies and over its disjoint partners, its
+//                                         label count, its Z share; one block per proxy: its norm) -> per-row partials in ws
+//                      k_hyp_finalize    (one block: ordered sums of the partials, the divisions, the Z == 0 branch) -> out8
+//   xmh_hyp_loss_grad  k_hyp_rows<false> (counts and norms only)
+//                      k_hyp_grad        (blocks [0, B): d/dx_i and d/dy_i; blocks [B, B + C): d/dP_c, each a fixed-order sum)
+//
+// Every quantity the reference counts with nonzero() (P_num, N_num, M, Z) is counted here on the device, so neither call synchronises
+// with the host.  There are no float atomics: every sum has one fixed order, so two calls on the same inputs agree to the bit.
+// The dot products that decide a relu' mask ([cos > thr]) are formed in the same lane order by every kernel that needs them, so the
+// forward, the row gradient and the proxy gradient see the same mask.
+// Bound: B = 100, K = 16..128, C = 80 (COCO, configs[4]) is a few tens of KB of L2-resident operands: launch-latency bound.
+#include "xmh_common.h"
+
+namespace {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kMaxB = 4096, kMaxK = 4096, kMaxC = 1024;
+constexpr int kSlots = kMaxK / kThreads;         // columns per thread in the column-parallel phases (K <= 4096)
+constexpr int kChunk = 256;                      // partner rows whose pair weights are staged in LDS at a time
+constexpr float kEps = 1e-12f;                   // F.normalize's eps
+
+// workspace: per-row partial sums (7 doubles, padded to 8), per-row counts (labels, Z share), row norms of x, y and P
+struct WsView {
+    double* part;
+    int* cnt;
+    float* nx;
+    float* ny;
+    float* np;
+};
+
+__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+__host__ __device__ inline size_t ws_layout(int64_t B, int C, char* base, WsView* v) {
+    size_t off = 0;
+    const size_t o_part = off; off = align256(off + (size_t)B * 8 * sizeof(double));
+    const size_t o_cnt = off;  off = align256(off + (size_t)B * 2 * sizeof(int));
+    const size_t o_nx = off;   off = align256(off + (size_t)B * sizeof(float));
+    const size_t o_ny = off;   off = align256(off + (size_t)B * sizeof(float));
+    const size_t o_np = off;   off = align256(off + (size_t)C * sizeof(float));
+    if (v) {
+        v->part = reinterpret_cast<double*>(base + o_part);
+        v->cnt = reinterpret_cast<int*>(base + o_cnt);
+        v->nx = reinterpret_cast<float*>(base + o_nx);
+        v->ny = reinterpret_cast<float*>(base + o_ny);
+        v->np = reinterpret_cast<float*>(base + o_np);
+    }
+    return off;
+}
+
+// xor butterfly: every lane ends with the same bits (each step adds the same two values, in either order)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// block sum in a fixed order (wave butterflies, then the waves in index order); valid on every thread
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = sh[0];
+    for (int w = 1; w < kWaves; ++w) s += sh[w];
+    __syncthreads();
+    return s;
+}
+
+__device__ __forceinline__ float inv_norm(float n) { return 1.0f / fmaxf(n, kEps); }
+
+__device__ __forceinline__ bool has_label(const uint32_t* lab, int Lw, int row, int c) {
+    return (lab[(int64_t)row * Lw + (c >> 5)] >> (c & 31)) & 1u;
+}
+
+// Is row j (lanes < Lw hold its label words in w) a regulariser partner of the row whose words are `mine` (itself in M)?
+// j must be in M as well (>= 2 labels) and share no class with it.  Wave-uniform.
+__device__ __forceinline__ bool disjoint_partner(uint32_t mine, uint32_t w) {
+    return wave_sum((int)__popc(w)) >= 2 && __ballot((mine & w) != 0u) == 0ull;
+}
+
+// Blocks [0, B): row i of the codes.  Blocks [B, B + C): the norm of proxy c.
+// kLoss: also the row's sums over the proxies and over its regulariser partners (the forward); otherwise counts and norms only.
+template <bool kLoss>
+__global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__ x, const float* __restrict__ y,
+                                                       const float* __restrict__ P, int B, int K, int C,
+                                                       const uint32_t* __restrict__ lab, int Lw, float thr, float alpha, WsView ws) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double red[kWaves][7];
+    __shared__ int zred[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((int)blockIdx.x >= B) {
+        const int c = blockIdx.x - B;
+        if (wave == 0) {
+            float s = 0.0f;
+            for (int k = lane; k < K; k += 64) s = fmaf(P[(int64_t)c * K + k], P[(int64_t)c * K + k], s);
+            s = wave_sum(s);
+            if (lane == 0) ws.np[c] = sqrtf(s);
+        }
+        return;
+    }
+    const int i = blockIdx.x;
+    float* xs = smem;
+    float* ys = smem + K;
+    for (int k = threadIdx.x; k < K; k += kThreads) {
+        xs[k] = x[(int64_t)i * K + k];
+        ys[k] = y[(int64_t)i * K + k];
+    }
+    __syncthreads();
+    float sx = 0.0f, sy = 0.0f;
+    for (int k = lane; k < K; k += 64) {
+        sx = fmaf(xs[k], xs[k], sx);
+        sy = fmaf(ys[k], ys[k], sy);
+    }
+    const float nxi = sqrtf(wave_sum(sx)), nyi = sqrtf(wave_sum(sy));
+    const float ix = inv_norm(nxi), iy = inv_norm(nyi);
+    const uint32_t mine = lane < Lw ? lab[(int64_t)i * Lw + lane] : 0u;
+    const int npos = wave_sum((int)__popc(mine));
+
+    double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // pos, neg, pos_t, neg_t, reg, reg_t, reg_xt (before alpha / Z)
+    if (kLoss) {
+        for (int c = wave; c < C; c += kWaves) {
+            const float* pc = P + (int64_t)c * K;
+            float d = 0.0f, dt = 0.0f, pp = 0.0f;
+            for (int k = lane; k < K; k += 64) {
+                const float p = pc[k];
+                d = fmaf(xs[k], p, d);
+                dt = fmaf(ys[k], p, dt);
+                pp = fmaf(p, p, pp);
+            }
+            d = wave_sum(d);
+            dt = wave_sum(dt);
+            const float ip = inv_norm(sqrtf(wave_sum(pp)));
+            const float cs = d * ix * ip, ct = dt * iy * ip;
+            if (has_label(lab, Lw, i, c)) {
+                acc[0] += (double)(1.0f - cs);
+                acc[2] += (double)(1.0f - ct);
+            } else {
+                acc[1] += (double)fmaxf(cs - thr, 0.0f);
+                acc[3] += (double)fmaxf(ct - thr, 0.0f);
+            }
+        }
+    }
+    int z = 0;
+    if (alpha > 0.0f && npos >= 2) {
+        for (int j = wave; j < B; j += kWaves) {
+            const uint32_t w = lane < Lw ? lab[(int64_t)j * Lw + lane] : 0u;
+            if (!disjoint_partner(mine, w)) continue;
+            ++z;
+            if (kLoss) {
+                const float* xj = x + (int64_t)j * K;
+                const float* yj = y + (int64_t)j * K;
+                float dxx = 0.0f, dyy = 0.0f, dxy = 0.0f, nx2 = 0.0f, ny2 = 0.0f;
+                for (int k = lane; k < K; k += 64) {
+                    const float a = xj[k], b = yj[k];
+                    dxx = fmaf(xs[k], a, dxx);
+                    dyy = fmaf(ys[k], b, dyy);
+                    dxy = fmaf(xs[k], b, dxy);
+                    nx2 = fmaf(a, a, nx2);
+                    ny2 = fmaf(b, b, ny2);
+                }
+                const float ixj = inv_norm(sqrtf(wave_sum(nx2))), iyj = inv_norm(sqrtf(wave_sum(ny2)));
+                acc[4] += (double)fmaxf(wave_sum(dxx) * ix * ixj - thr, 0.0f);
+                acc[5] += (double)fmaxf(wave_sum(dyy) * iy * iyj - thr, 0.0f);
+                acc[6] += (double)fmaxf(wave_sum(dxy) * ix * iyj - thr, 0.0f);
+            }
+        }
+    }
+    if (lane == 0) {
+        for (int t = 0; t < 7; ++t) red[wave][t] = acc[t];
+        zred[wave] = z;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int t = threadIdx.x;
+        double s = 0.0;
+        if (t < 7)
+            for (int w = 0; w < kWaves; ++w) s += red[w][t];
+        if (kLoss) ws.part[(int64_t)i * 8 + t] = s;
+        if (t == 0) {
+            int zs = 0;
+            for (int w = 0; w < kWaves; ++w) zs += zred[w];
+            ws.cnt[2 * i] = npos;
+            ws.cnt[2 * i + 1] = zs;
+            ws.nx[i] = nxi;
+            ws.ny[i] = nyi;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_hyp_finalize(int B, int C, float alpha, WsView ws, double* __restrict__ out8) {
+    __shared__ double sh[kWaves];
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int r = threadIdx.x; r < B; r += kThreads) {
+        for (int t = 0; t < 7; ++t) s[t] += ws.part[(int64_t)r * 8 + t];
+        s[7] += (double)ws.cnt[2 * r];
+        s[8] += (double)ws.cnt[2 * r + 1];
+    }
+    for (int t = 0; t < 9; ++t) s[t] = block_sum(s[t], sh);   // counts: exact in double
+    if (threadIdx.x == 0) {
+        const double pn = s[7], nn = (double)B * (double)C - s[7], z = s[8];
+        const double pos = s[0] / pn, neg = s[1] / nn, pos_t = s[2] / pn, neg_t = s[3] / nn;   // 0 / 0 = NaN, as the reference
+        const double a = (double)alpha;
+        const double reg = z > 0.0 ? a * s[4] / z : 0.0, reg_t = z > 0.0 ? a * s[5] / z : 0.0, reg_xt = z > 0.0 ? a * s[6] / z : 0.0;
+        out8[0] = pos + neg + pos_t + neg_t + reg + reg_t + reg_xt;
+        out8[1] = pos;
+        out8[2] = neg;
+        out8[3] = pos_t;
+        out8[4] = neg_t;
+        out8[5] = reg;
+        out8[6] = reg_t;
+        out8[7] = reg_xt;
+    }
+}
+
+// dv of F.normalize for one row v (in LDS) with du in the thread's column slots, then written / accumulated times g
+__device__ __forceinline__ void normalize_backward_store(const float* v, float nv, const float (&du)[kSlots], int K, float g, float* __restrict__ out,
+                                                         int accumulate, float* sh) {
+    const float iv = inv_norm(nv);
+    float vd = 0.0f;
+#pragma unroll
+    for (int r = 0; r < kSlots; ++r) {
+        const int k = threadIdx.x + r * kThreads;
+        if (k < K) vd = fmaf(v[k], du[r], vd);
+    }
+    vd = block_sum(vd, sh);
+    const float s = nv >= kEps ? vd * iv : 0.0f;                 // u . du; a clamped row passes du / eps only
+#pragma unroll
+    for (int r = 0; r < kSlots; ++r) {
+        const int k = threadIdx.x + r * kThreads;
+        if (k < K) {
+            const float d = g * ((du[r] - v[k] * iv * s) * iv);
+            out[k] = accumulate ? out[k] + d : d;
+        }
+    }
+}
+
+// Blocks [0, B): grad_x[i], grad_y[i].  Blocks [B, B + C): grad_P[c].  The global counts come from k_hyp_rows<false>.
+__global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ P,
+                                                       int B, int K, int C, const uint32_t* __restrict__ lab, int Lw, float thr, float alpha,
+                                                       WsView ws, const float* __restrict__ up, float* __restrict__ gx,
+                                                       float* __restrict__ gy, float* __restrict__ gP, int accumulate) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double dsh[kWaves];
+    __shared__ float fsh[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double pn = 0.0, z = 0.0;
+    for (int r = threadIdx.x; r < B; r += kThreads) {
+        pn += (double)ws.cnt[2 * r];
+        z += (double)ws.cnt[2 * r + 1];
+    }
+    pn = block_sum(pn, dsh);
+    z = block_sum(z, dsh);
+    const double nn = (double)B * (double)C - pn;
+    // d loss / d cos: -1 / P_num on a label, [cos > thr] / N_num off it; d loss / d sim: alpha / Z on a pair
+    const float wpos = pn > 0.0 ? (float)(-1.0 / pn) : 0.0f, wneg = nn > 0.0 ? (float)(1.0 / nn) : 0.0f;
+    const float wreg = z > 0.0 ? (float)((double)alpha / z) : 0.0f;
+    const float g = up ? up[0] : 1.0f;
+    float ax[kSlots], ay[kSlots];
+#pragma unroll
+    for (int r = 0; r < kSlots; ++r) ax[r] = ay[r] = 0.0f;
+
+    if ((int)blockIdx.x < B) {
+        const int i = blockIdx.x;
+        float* xs = smem;
+        float* ys = xs + K;
+        float* cw = ys + K;                                      // [C] weight of P_c in d/dx_i (d loss/d cos times 1/|P_c|)
+        float* ctw = cw + C;                                     // [C] the same for y_i
+        float* pw = ctw + C;                                     // [4][kChunk] pair weights of a chunk of partners
+        for (int k = threadIdx.x; k < K; k += kThreads) {
+            xs[k] = x[(int64_t)i * K + k];
+            ys[k] = y[(int64_t)i * K + k];
+        }
+        const float ix = inv_norm(ws.nx[i]), iy = inv_norm(ws.ny[i]);
+        __syncthreads();
+        for (int c = wave; c < C; c += kWaves) {
+            const float ip = inv_norm(ws.np[c]);
+            float a = wpos * ip, b = wpos * ip;
+            if (!has_label(lab, Lw, i, c)) {
+                const float* pc = P + (int64_t)c * K;
+                float d = 0.0f, dt = 0.0f;
+                for (int k = lane; k < K; k += 64) {
+                    const float p = pc[k];
+                    d = fmaf(xs[k], p, d);
+                    dt = fmaf(ys[k], p, dt);
+                }
+                a = wave_sum(d) * ix * ip > thr ? wneg * ip : 0.0f;
+                b = wave_sum(dt) * iy * ip > thr ? wneg * ip : 0.0f;
+            }
+            if (lane == 0) {
+                cw[c] = a;
+                ctw[c] = b;
+            }
+        }
+        __syncthreads();
+        for (int c = 0; c < C; ++c) {
+            const float a = cw[c], b = ctw[c];
+            if (a == 0.0f && b == 0.0f) continue;
+            const float* pc = P + (int64_t)c * K;
+#pragma unroll
+            for (int r = 0; r < kSlots; ++r) {
+                const int k = threadIdx.x + r * kThreads;
+                if (k < K) {
+                    const float p = pc[k];
+                    ax[r] = fmaf(a, p, ax[r]);
+                    ay[r] = fmaf(b, p, ay[r]);
+                }
+            }
+        }
+        if (wreg != 0.0f && ws.cnt[2 * i] >= 2) {
+            const uint32_t mine = lane < Lw ? lab[(int64_t)i * Lw + lane] : 0u;
+            for (int j0 = 0; j0 < B; j0 += kChunk) {
+                const int n = min(kChunk, B - j0);
+                for (int jj = wave; jj < n; jj += kWaves) {
+                    const int j = j0 + jj;
+                    const uint32_t w = lane < Lw ? lab[(int64_t)j * Lw + lane] : 0u;
+                    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
+                    if (disjoint_partner(mine, w)) {
+                        const float* xj = x + (int64_t)j * K;
+                        const float* yj = y + (int64_t)j * K;
+                        float dxx = 0.0f, dyy = 0.0f, dxy = 0.0f, dyx = 0.0f;
+                        for (int k = lane; k < K; k += 64) {
+                            const float a = xj[k], b = yj[k];
+                            dxx = fmaf(xs[k], a, dxx);
+                            dyy = fmaf(ys[k], b, dyy);
+                            dxy = fmaf(xs[k], b, dxy);
+                            dyx = fmaf(a, ys[k], dyx);               // x_j . y_i, the order the forward forms it for row j
+                        }
+                        const float ixj = inv_norm(ws.nx[j]), iyj = inv_norm(ws.ny[j]);
+                        // x-x and y-y: the pair masks are symmetric, so row i collects both (i, j) and (j, i)
+                        c0 = wave_sum(dxx) * ix * ixj > thr ? 2.0f * wreg * ixj : 0.0f;   // x_j into d/dx_i
+                        c1 = wave_sum(dxy) * ix * iyj > thr ? wreg * iyj : 0.0f;          // y_j into d/dx_i (x-y term, i first)
+                        c2 = wave_sum(dyy) * iy * iyj > thr ? 2.0f * wreg * iyj : 0.0f;   // y_j into d/dy_i
+                        c3 = wave_sum(dyx) * ixj * iy > thr ? wreg * ixj : 0.0f;          // x_j into d/dy_i (x-y term, i second)
+                    }
+                    if (lane == 0) {
+                        pw[jj] = c0;
+                        pw[kChunk + jj] = c1;
+                        pw[2 * kChunk + jj] = c2;
+                        pw[3 * kChunk + jj] = c3;
+                    }
+                }
+                __syncthreads();
+                for (int jj = 0; jj < n; ++jj) {
+                    const float c0 = pw[jj], c1 = pw[kChunk + jj], c2 = pw[2 * kChunk + jj], c3 = pw[3 * kChunk + jj];
+                    if (c0 == 0.0f && c1 == 0.0f && c2 == 0.0f && c3 == 0.0f) continue;
+                    const float* xj = x + (int64_t)(j0 + jj) * K;
+                    const float* yj = y + (int64_t)(j0 + jj) * K;
+#pragma unroll
+                    for (int r = 0; r < kSlots; ++r) {
+                        const int k = threadIdx.x + r * kThreads;
+                        if (k < K) {
+                            const float a = xj[k], b = yj[k];
+                            ax[r] = fmaf(c1, b, fmaf(c0, a, ax[r]));
+                            ay[r] = fmaf(c3, a, fmaf(c2, b, ay[r]));
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        normalize_backward_store(xs, ws.nx[i], ax, K, g, gx + (int64_t)i * K, accumulate, fsh);
+        normalize_backward_store(ys, ws.ny[i], ay, K, g, gy + (int64_t)i * K, accumulate, fsh);
+    } else {
+        const int c = blockIdx.x - B;
+        float* ps = smem;                                        // P_c
+        float* wx = ps + K;                                      // [kChunk] weight of x_i in d/dP_c
+        float* wy = wx + kChunk;                                 // [kChunk] weight of y_i
+        for (int k = threadIdx.x; k < K; k += kThreads) ps[k] = P[(int64_t)c * K + k];
+        const float ip = inv_norm(ws.np[c]);
+        __syncthreads();
+        for (int i0 = 0; i0 < B; i0 += kChunk) {
+            const int n = min(kChunk, B - i0);
+            for (int ii = wave; ii < n; ii += kWaves) {
+                const int i = i0 + ii;
+                const float ixi = inv_norm(ws.nx[i]), iyi = inv_norm(ws.ny[i]);
+                float a = wpos * ixi, b = wpos * iyi;
+                if (!has_label(lab, Lw, i, c)) {
+                    const float* xi = x + (int64_t)i * K;
+                    const float* yi = y + (int64_t)i * K;
+                    float d = 0.0f, dt = 0.0f;
+                    for (int k = lane; k < K; k += 64) {
+                        const float p = ps[k];
+                        d = fmaf(xi[k], p, d);
+                        dt = fmaf(yi[k], p, dt);
+                    }
+                    a = wave_sum(d) * ixi * ip > thr ? wneg * ixi : 0.0f;
+                    b = wave_sum(dt) * iyi * ip > thr ? wneg * iyi : 0.0f;
+                }
+                if (lane == 0) {
+                    wx[ii] = a;
+                    wy[ii] = b;
+                }
+            }
+            __syncthreads();
+            for (int ii = 0; ii < n; ++ii) {
+                const float a = wx[ii], b = wy[ii];
+                if (a == 0.0f && b == 0.0f) continue;
+                const float* xi = x + (int64_t)(i0 + ii) * K;
+                const float* yi = y + (int64_t)(i0 + ii) * K;
+#pragma unroll
+                for (int r = 0; r < kSlots; ++r) {
+                    const int k = threadIdx.x + r * kThreads;
+                    if (k < K) ax[r] = fmaf(b, yi[k], fmaf(a, xi[k], ax[r]));
+                }
+            }
+            __syncthreads();
+        }
+        normalize_backward_store(ps, ws.np[c], ax, K, g, gP + (int64_t)c * K, accumulate, fsh);
+    }
+}
+
+// shared argument checks of both entry points: they run before any HIP call
+int check_args(const char* who, const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab, void* ws,
+               size_t ws_bytes) {
+    if (B <= 0 || K <= 0 || C <= 0) return xmh::fail(XMH_EINVAL, "%s: bad shape B=%lld K=%d C=%d", who, (long long)B, K, C);
+    if (B > kMaxB || K > kMaxK || C > kMaxC)
+        return xmh::fail(XMH_ENOTSUP, "%s: B=%lld K=%d C=%d outside B <= %d, K <= %d, C <= %d", who, (long long)B, K, C, kMaxB, kMaxK, kMaxC);
+    if (!x || !y || !P || !lab || !ws) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    const size_t need = ws_layout(B, C, nullptr, nullptr);
+    if (ws_bytes < need) return xmh::fail(XMH_EINVAL, "%s: workspace of %zu bytes < %zu (xmh_hyp_loss_ws_bytes)", who, ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
+    return XMH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t xmh_hyp_loss_ws_bytes(int64_t B, int K, int C) {
+    if (B <= 0 || K <= 0 || C <= 0 || B > kMaxB || K > kMaxK || C > kMaxC) return 0;
+    return ws_layout(B, C, nullptr, nullptr);
+}
+
+extern "C" int xmh_hyp_loss(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab, float threshold,
+                            float alpha, void* ws, size_t ws_bytes, double* out8, xmh_stream_t stream) {
+    XMH_RANGE("xmh_hyp_loss");
+    if (int rc = check_args("xmh_hyp_loss", x, y, P, B, K, C, lab, ws, ws_bytes)) return rc;
+    if (!out8) return xmh::fail(XMH_EINVAL, "xmh_hyp_loss: null pointer");
+    WsView v;
+    ws_layout(B, C, static_cast<char*>(ws), &v);
+    hipStream_t st = xmh::as_stream(stream);
+    hipLaunchKernelGGL(k_hyp_rows<true>, dim3((unsigned)(B + C)), dim3(kThreads), (size_t)2 * K * 4, st, x, y, P, (int)B, K, C, lab,
+                       (C + 31) / 32, threshold, alpha, v);
+    hipLaunchKernelGGL(k_hyp_finalize, dim3(1), dim3(kThreads), 0, st, (int)B, C, alpha, v, out8);
+    XMH_LAUNCH_CHECK("xmh_hyp_loss");
+    return XMH_OK;
+}
+
+extern "C" int xmh_hyp_loss_grad(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab,
+                                 float threshold, float alpha, const float* upstream, float* grad_x, float* grad_y, float* grad_P,
+                                 int accumulate, void* ws, size_t ws_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_hyp_loss_grad");
+    if (int rc = check_args("xmh_hyp_loss_grad", x, y, P, B, K, C, lab, ws, ws_bytes)) return rc;
+    if (!grad_x || !grad_y || !grad_P) return xmh::fail(XMH_EINVAL, "xmh_hyp_loss_grad: null pointer");
+    WsView v;
+    ws_layout(B, C, static_cast<char*>(ws), &v);
+    hipStream_t st = xmh::as_stream(stream);
+    hipLaunchKernelGGL(k_hyp_rows<false>, dim3((unsigned)(B + C)), dim3(kThreads), (size_t)2 * K * 4, st, x, y, P, (int)B, K, C, lab,
+                       (C + 31) / 32, threshold, alpha, v);
+    const size_t lds = ((size_t)2 * K + (size_t)2 * C + 4 * kChunk) * 4;   // <= 45 KB at K = 4096, C = 1024
+    hipLaunchKernelGGL(k_hyp_grad, dim3((unsigned)(B + C)), dim3(kThreads), lds, st, x, y, P, (int)B, K, C, lab, (C + 31) / 32,
+                       threshold, alpha, v, upstream, grad_x, grad_y, grad_P, accumulate);
+    XMH_LAUNCH_CHECK("xmh_hyp_loss_grad");
+    return XMH_OK;
+}

@@ -1,23 +1,28 @@
-"""DSPH model wrapper (reference models/DSPH/DSPH.py:13-60): backbone + Linear/tanh head, registered as "DSPH".
-The reference reads ``loss/codetable.xlsx`` at construction for its HyP loss threshold (:33-35); that is a
-training-only input and is not needed here.  What IS part of the contract is the parameter the loss module
-owns: a reference DSPH checkpoint carries ``hyp.proxies`` [numclass, K] (models/DSPH/loss/HyP.py:15-16) beside ``backbone.*``
-and ``hash.*`` -- pinned by tests/golden/runner.npz (DSPH_state_keys, from the reference's own class) -- so the module tree
-here has it too and ``load_state_dict`` of such a checkpoint succeeds strictly."""
+"""DSPH model wrapper (reference models/DSPH/DSPH.py:13-82): backbone + Linear/tanh head, registered as "DSPH", and its HyP loss
+(models/DSPH/loss/HyP.py) through xmh_hyp.hip.  A reference DSPH checkpoint carries ``hyp.proxies`` [numclass, K]
+(models/DSPH/loss/HyP.py:15-16) beside ``backbone.*`` and ``hash.*`` -- pinned by tests/golden/runner.npz (DSPH_state_keys, from the
+reference's own class) -- so the module tree here has it too and ``load_state_dict`` of such a checkpoint succeeds strictly.
+
+The reference reads the HyP threshold out of ``loss/codetable.xlsx`` at construction (:33-35).  Here it is, in this order: an
+explicit ``threshold`` (constructor argument or ``cfg.threshold``); the cell of ``cfg.codetable`` (a path to the user's copy of
+that workbook, read by codetable.hyp_threshold); otherwise unset -- the model constructs and encodes as usual and the first loss
+call raises ValueError."""
 import torch
 import torch.nn as nn
 
+from .. import retrieval as R
+from .._lib import check, current_stream, lib, ptr
 from ..common.register import registry
 from .base import BaseModel
+from .codetable import hyp_threshold
 from .heads import DSPHHashLayer
 
 
 class HyPProxies(nn.Module):
-    """parameter container of the reference's HyP loss (models/DSPH/loss/HyP.py:8-16): ``proxies`` [numclass, output_dim],
-    randn then kaiming_normal_(fan_out).  The reference seeds the GLOBAL generator with ``hypseed`` to draw them; a private
-    generator is used here so that constructing a model has no side effect on the caller's random stream (values of a freshly
-    constructed model therefore differ from the reference's; a loaded checkpoint overwrites them either way).  The loss itself
-    is training code (out of scope)."""
+    """the reference's HyP loss (models/DSPH/loss/HyP.py:7-70): ``proxies`` [numclass, output_dim], randn then
+    kaiming_normal_(fan_out).  The reference seeds the GLOBAL generator with ``hypseed`` to draw them; a private generator is used
+    here so that constructing a model has no side effect on the caller's random stream (values of a freshly constructed model
+    therefore differ from the reference's; a loaded checkpoint overwrites them either way)."""
 
     def __init__(self, numclass=80, output_dim=16, hypseed=0, alpha=0.8, threshold=None):
         super().__init__()
@@ -26,15 +31,80 @@ class HyPProxies(nn.Module):
         std = (2.0 / max(1, numclass)) ** 0.5                          # kaiming_normal_, mode="fan_out" of a [numclass, output_dim] matrix
         self.proxies = nn.Parameter(torch.randn(numclass, output_dim, generator=g) * std)
 
+    def forward(self, x=None, y=None, label=None):
+        """reference HyP.forward (:18-70): the loss as a 0-dim fp32 device tensor, differentiable with respect to x, y and the
+        proxies.  `label` is the [B, numclass] 0/1 matrix; on another device it is moved, as the reference does."""
+        if self.threshold is None:
+            raise ValueError("DSPH's HyP loss has no threshold: set `threshold` in the model config, or `codetable` to the path of "
+                             "the reference's codetable.xlsx")
+        for t in (x, y, self.proxies):
+            if not t.is_cuda:
+                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        if x.dim() != 2 or y.shape != x.shape or label.dim() != 2 or label.shape[0] != x.shape[0] \
+                or label.shape[1] != self.proxies.shape[0] or x.shape[1] != self.proxies.shape[1]:
+            raise RuntimeError("HyP loss: x %s, y %s, label %s, proxies %s do not fit together"
+                               % (tuple(x.shape), tuple(y.shape), tuple(label.shape), tuple(self.proxies.shape)))
+        if label.device != x.device:
+            label = label.to(x.device)
+        return _HyP.apply(self, x, y, self.proxies, R.pack_labels(label))
+
+
+class _HyP(torch.autograd.Function):
+    """forward = xmh_hyp_loss, backward = xmh_hyp_loss_grad (both with respect to x, y and the proxies, one call)"""
+
+    @staticmethod
+    def _args(hyp, x, y, P, lab):
+        B, K = x.shape
+        C = P.shape[0]
+        ws = torch.empty(lib.xmh_hyp_loss_ws_bytes(B, K, C), dtype=torch.uint8, device=x.device)
+        return (ptr(x), ptr(y), ptr(P), B, K, C, ptr(lab), float(hyp.threshold), float(hyp.alpha)), ws
+
+    @staticmethod
+    def forward(ctx, hyp, x, y, proxies, lab):
+        xs, ys, P = (t.detach().float().contiguous() for t in (x, y, proxies))
+        args, ws = _HyP._args(hyp, xs, ys, P, lab)
+        out = torch.empty(8, dtype=torch.float64, device=xs.device)
+        check(lib.xmh_hyp_loss(*args, ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_hyp_loss")
+        ctx.hyp = hyp
+        ctx.meta = ((x.shape, x.dtype), (y.shape, y.dtype), (proxies.shape, proxies.dtype))
+        ctx.save_for_backward(xs, ys, P, lab)
+        return out[0].float()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable: fail loudly on double backward
+    def backward(ctx, g):
+        xs, ys, P, lab = ctx.saved_tensors
+        args, ws = _HyP._args(ctx.hyp, xs, ys, P, lab)
+        up = g.detach().float().reshape(1).contiguous()
+        gx, gy, gP = torch.empty_like(xs), torch.empty_like(ys), torch.empty_like(P)
+        check(lib.xmh_hyp_loss_grad(*args, ptr(up), ptr(gx), ptr(gy), ptr(gP), 0, ptr(ws), ws.numel(), current_stream()),
+              "xmh_hyp_loss_grad")
+        grads = [t.reshape(s).to(d) if need else None for t, (s, d), need in zip((gx, gy, gP), ctx.meta, ctx.needs_input_grad[1:4])]
+        return (None, *grads, None)
+
 
 @registry.register_model("DSPH")
 class DSPH(BaseModel):
-    def __init__(self, cfg, outputDim=16, clipPath="./ViT-B-32.pt", train_num=10000, numclass=80, hypseed=1, alpha=0):
+    def __init__(self, cfg, outputDim=16, clipPath="./ViT-B-32.pt", train_num=10000, numclass=80, hypseed=1, alpha=0, threshold=None,
+                 codetable=None):
         super().__init__(cfg)
         embed_dim, self.backbone = self.load_backbone(clipPath=clipPath, return_patches=False)
         self.hash = DSPHHashLayer(inputDim=embed_dim, outputDim=outputDim)
         self.output_dim, self.numclass, self.hypseed, self.alpha = outputDim, numclass, hypseed, alpha
-        self.hyp = HyPProxies(numclass=numclass, output_dim=outputDim, hypseed=hypseed, alpha=alpha)
+        threshold = self.resolve_threshold(cfg, outputDim, numclass, threshold, codetable)
+        self.hyp = HyPProxies(numclass=numclass, output_dim=outputDim, hypseed=hypseed, alpha=alpha, threshold=threshold)
+
+    @staticmethod
+    def resolve_threshold(cfg, output_dim, numclass, threshold=None, codetable=None):
+        """explicit threshold (argument, then cfg.threshold), else the cell of the codetable (argument, then cfg.codetable), else None"""
+        get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: d)
+        if threshold is None:
+            threshold = get("threshold", None)
+        if threshold is not None:
+            return float(threshold)
+        if codetable is None:
+            codetable = get("codetable", None)
+        return None if codetable is None else hyp_threshold(codetable, output_dim, numclass)
 
     def encode_image(self, image):
         return self.hash.encode_img(self.backbone.encode_image(image))
@@ -42,8 +112,19 @@ class DSPH(BaseModel):
     def encode_text(self, text):
         return self.hash.encode_txt(self.backbone.encode_text(text))
 
-    def object_function(self, *a, **k):
-        raise NotImplementedError("training losses are outside the encode-and-retrieve path (SURVEY 2.1 #9)")
+    def loss(self, image, text, labels=None, indexs=None, **kwags):
+        """reference :68-76 -- (loss, {"All loss": detached loss})"""
+        loss = self.hyp(image, text, labels)
+        return loss, {"All loss": loss.detach()}
+
+    def object_function(self, img_hash, txt_hash, labels=None, indexs=None, **kwags):
+        """reference :78-82 -- without labels every sample is its own class, which fits the proxies only when numclass == B"""
+        if labels is None:
+            if img_hash.shape[0] != self.hyp.proxies.shape[0]:
+                raise RuntimeError("object_function without labels needs numclass == batch size (numclass %d, batch %d): the "
+                                   "identity labels are [B, B]" % (self.hyp.proxies.shape[0], img_hash.shape[0]))
+            labels = torch.ones([img_hash.shape[0]], dtype=torch.int).diag()
+        return self.loss(img_hash, txt_hash, labels, indexs, **kwags)
 
     @classmethod
     def from_config(cls, cfg, output_dim=16, train_num=10000):

@@ -77,6 +77,17 @@ class DCMHTTrainer(_MethodTrainer):
 class DSPHTrainer(_MethodTrainer):
     """runners/DSPH/runner.py: base generate_hash + sign quantiser."""
 
+    hash_scale = 1                                              # runners/DSPH/runner.py:38
+
+    def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
+        """runners/DSPH/runner.py:93-101: the HyP objective of one batch (xmh_hyp.hip behind torch.autograd), differentiable with
+        respect to img_hash / txt_hash and the model's hyp.proxies; the display line needs the training loop's loader and
+        optimiser, which this package does not build, and is skipped without them."""
+        all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, labels=label, indexs=index, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
 
 @registry.register_runner("MITHTrainer")
 class MITHTrainer(_MethodTrainer):

@@ -540,6 +540,26 @@ int xmh_pair_similarity_loss_grad(const float* a, const float* b, int64_t B, int
 int xmh_quant_loss_grad(const float* code, int64_t n, float scale, const float* upstream, float* grad, int accumulate,
                         xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * HyP loss of DSPH (models/DSPH/loss/HyP.py:18-70): forward, and its gradient with respect to the two code matrices and the
+ * proxies (what loss.backward() of runners/DSPH/runner.py:123 hands to the hash heads and to the proxies' own optimiser).
+ * x, y [B, K] fp32 (image / text codes), P [C, K] fp32 (proxies), lab [B][ceil(C/32)] as xmh_pack_labels writes it.
+ * B <= 4096, K <= 4096, C <= 1024 (XMH_ENOTSUP beyond).  Both calls count P_num, N_num and the regulariser's pairs on the device
+ * (no host synchronisation, no allocation) and sum in one fixed order (two calls on the same inputs agree to the bit).
+ * Workspace: xmh_hyp_loss_ws_bytes(B, K, C) bytes of device memory, 256-byte aligned (0 for a shape outside the bounds).
+ * ------------------------------------------------------------------------------------------- */
+size_t xmh_hyp_loss_ws_bytes(int64_t B, int K, int C);
+/* out8 (device, 8 doubles) = (loss, pos, neg, pos_t, neg_t, reg, reg_t, reg_xt); loss is their sum.  P_num == 0 or N_num == 0
+ * gives NaN terms (0 / 0) as the reference does; alpha <= 0, or no pair of multi-label rows with disjoint labels, gives reg = 0. */
+int xmh_hyp_loss(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab,
+                 float threshold, float alpha, void* ws, size_t ws_bytes, double* out8, xmh_stream_t stream);
+/* d loss / d x, d y, d P as autograd derives them from the reference's expression (relu'(0) = 0; F.normalize's backward, a row
+ * clamped by its eps receiving du / 1e-12).  grad_x [B, K], grad_y [B, K] and grad_P [C, K] (device, all required) are written,
+ * or added to when accumulate != 0, with upstream[0] (device float, NULL = 1) folded in. */
+int xmh_hyp_loss_grad(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab,
+                      float threshold, float alpha, const float* upstream, float* grad_x, float* grad_y, float* grad_P,
+                      int accumulate, void* ws, size_t ws_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
