@@ -69,6 +69,14 @@ class MithHead(C.Structure):                   # xmh_mith_head
                 ("hash_w", vp), ("hash_b", vp)]
 
 
+class MithLossArgs(C.Structure):               # xmh_mith_loss_args
+    _fields_ = [("N", i64), ("B", i32), ("K", i32), ("D", i32), ("res_img_cls", vp), ("res_txt_cls", vp), ("img_cls_hash", vp),
+                ("txt_cls_hash", vp), ("tokens_hash_i", vp), ("tokens_hash_t", vp), ("trans_tokens_i", vp), ("trans_tokens_t", vp),
+                ("buffer", vp), ("label_sim", vp), ("hyper_tokens_intra", C.c_double), ("hyper_distill", C.c_double),
+                ("hyper_info_nce", C.c_double), ("hyper_cls_inter", C.c_double), ("hyper_quan", C.c_double), ("hyper_alpha", C.c_double),
+                ("hyper_lambda", C.c_double), ("temperature", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
 PROTOTYPES = {
     "xmh_version": (i32, []),
@@ -143,6 +151,9 @@ PROTOTYPES = {
     "xmh_hyp_loss_ws_bytes": (sz, [i64, i32, i32]),
     "xmh_hyp_loss": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, sz, vp, vp]),
     "xmh_hyp_loss_grad": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "xmh_mith_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_mith_loss": (i32, [C.POINTER(MithLossArgs), vp, sz, vp, vp]),
+    "xmh_mith_loss_grad": (i32, [C.POINTER(MithLossArgs), vp, C.POINTER(vp), i32, vp, sz, vp]),
     "xmh_topk_ws_bytes": (sz, [i64, i64, i32, i32]),
     "xmh_hamming_topk": (i32, [vp, vp, i64, i64, i32, i32, i64, vp, sz, vp, vp, vp]),
     "xmh_topk_ws_init": (i32, [i64, i64, i32, i32, vp, sz, vp]),

@@ -2,12 +2,19 @@
 models/MITH/hash/hash.py:9-254), registered as "MITH".  Parameters sit under the reference's key names
 (``hash.gcl_i.mlp.mlps.0.0.weight`` ..., ``gcl_t`` aliasing ``gcl_i`` like in the reference, :218); the eval-path
 dataflow is SURVEY 2.4.  ``res_*_cls`` / ``trans_tokens_*`` only feed the training losses and are returned as None.
+
+The training objective (reference :116-232) runs through xmh_mith_loss.hip behind ``_MITHLoss`` (a torch.autograd.Function).
+Its rolling code buffer is one [train_num, K] tensor bound to the reference's four names (img_buffer_cls, txt_buffer_cls,
+img_buffer_tokens, txt_buffer_tokens): that is what the reference's device branch (:169-173) leaves behind on every GPU run, because
+``.to()`` of a tensor already on the device returns the tensor itself.  After a step's four row writes the batch rows therefore hold
+tokens_hash_t, and all four likelihoods read the one buffer.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -154,8 +161,53 @@ class MITHHashLayer(nn.Module):
         return self._encode(self.gcl_t, self.lct_t, txt_eos, txt_tokens, key_padding_mask)
 
 
+class _MITHLoss(torch.autograd.Function):
+    """forward = xmh_mith_loss -> the ten terms as fp32 [10] (element 0 the loss), backward = xmh_mith_loss_grad (all eight inputs
+    in one call).  The buffer Y is saved as it is, so an in-place write to it before backward() fails autograd's version check."""
+
+    TEMPERATURE = 0.07                                    # info_nce_loss / info_nce_loss_bmm default (:116, :133)
+
+    @staticmethod
+    def _args(model, Y, S, xs):
+        B, K = xs[2].shape
+        D = xs[0].shape[1]
+        N = Y.shape[0]
+        a = _lib.MithLossArgs(N, B, K, D, *(t.data_ptr() for t in xs), Y.data_ptr(), S.data_ptr(),
+                              *(getattr(model, n) for n, _ in MITH.HYPER), _MITHLoss.TEMPERATURE)
+        ws = torch.empty(lib.xmh_mith_loss_ws_bytes(N, B, K, D), dtype=torch.uint8, device=Y.device)
+        return a, ws
+
+    @staticmethod
+    def forward(ctx, model, Y, S, *inputs):
+        xs = tuple(t.detach().float().contiguous() for t in inputs)
+        a, ws = _MITHLoss._args(model, Y, S, xs)
+        out = torch.empty(10, dtype=torch.float64, device=Y.device)
+        check(lib.xmh_mith_loss(ctypes.byref(a), ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_mith_loss")
+        ctx.model = model
+        ctx.meta = tuple((t.shape, t.dtype) for t in inputs)
+        ctx.save_for_backward(Y, S, *xs)
+        return out.float()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable: fail loudly on double backward
+    def backward(ctx, g):
+        Y, S, *xs = ctx.saved_tensors
+        need = ctx.needs_input_grad[3:]
+        a, ws = _MITHLoss._args(ctx.model, Y, S, xs)
+        up = g.detach().float().contiguous()          # only element 0 (the loss) carries a gradient
+        grads = [torch.empty_like(t) if n else None for t, n in zip(xs, need)]
+        gp = (ctypes.c_void_p * 8)(*(None if t is None else t.data_ptr() for t in grads))
+        check(lib.xmh_mith_loss_grad(ctypes.byref(a), ptr(up), gp, 0, ptr(ws), ws.numel(), current_stream()), "xmh_mith_loss_grad")
+        return (None, None, None, *(None if t is None else t.to(d).reshape(s) for t, (s, d) in zip(grads, ctx.meta)))
+
+
 @registry.register_model("MITH")
 class MITH(BaseModel):
+    # the loss weights and their defaults (models/MITH/MITH.py:16-25); cfg values override them through from_config
+    HYPER = (("hyper_tokens_intra", 1.0), ("hyper_distill", 1.0), ("hyper_info_nce", 50.0), ("hyper_cls_inter", 10.0),
+             ("hyper_quan", 8.0), ("hyper_alpha", 0.01), ("hyper_lambda", 0.99))
+    BUFFER_SEED = 1814
+
     def __init__(self, cfg, outputDim=16, clipPath="./ViT-B-32.pt", train_num=10000, hash_func="tanh", dropout=0,
                  transformer_layers=2, activation="gelu", top_k_label=8, res_mlp_layers=2, **hyper):
         super().__init__(cfg)
@@ -163,6 +215,16 @@ class MITH(BaseModel):
         self.hash = MITHHashLayer(embed_dim, outputDim, dropout, transformer_layers, activation, top_k_label, res_mlp_layers)
         self.output_dim, self.hash_func = outputDim, hash_func
         self.hyper = hyper
+        for name, default in self.HYPER:
+            setattr(self, name, float(hyper.get(name, default)))
+        # The rolling code buffer (:47-51): randn [train_num, K] on the host, a plain attribute, so not in state_dict.  It is drawn from
+        # a private generator, as HyPProxies draws its proxies, so that constructing a model leaves the caller's random stream alone
+        # (its values therefore differ from the reference's draw from the global generator).  One tensor under the four names.
+        g = torch.Generator().manual_seed(self.BUFFER_SEED)
+        self._bind_buffer(torch.randn(train_num, outputDim, generator=g))
+
+    def _bind_buffer(self, t):
+        self.img_buffer_cls = self.txt_buffer_cls = self.img_buffer_tokens = self.txt_buffer_tokens = t
 
     def encode_image(self, image):
         cls_token, seq_tokens, _ = self.backbone.encode_image(image)
@@ -177,13 +239,70 @@ class MITH(BaseModel):
         return self.hash.encode_txt(txt_eos, txt_tokens, new_mask)
 
     def forward(self, image, text, key_padding_mask=None, labels=None, indexs=None, return_loss=False):
-        if return_loss:
-            return self.object_function()
         img, txt = towers.run_both(lambda: self.encode_image(image), lambda: self.encode_text(text, key_padding_mask=key_padding_mask))
+        if return_loss:                                   # reference :71-74: no label_sim is passed, so its assertion fires
+            return self.object_function(*img, *txt, labels=labels, indexs=indexs)
         return (*img, *txt)
 
-    def object_function(self, *a, **k):
-        raise NotImplementedError("training losses are outside the encode-and-retrieve path (SURVEY 2.1 #8)")
+    def compute_loss(self, res_img_cls, img_cls_hash, tokens_hash_i, trans_tokens_i, res_txt_cls, txt_cls_hash, tokens_hash_t,
+                     trans_tokens_t, labels=None, indexs=None, label_sim=None, **kwags):
+        """reference :162-231 -- (loss, loss_dict).  `loss` is a 0-dim fp32 device tensor, differentiable with respect to the eight
+        inputs; loss_dict has the reference's nested keys, its values detached 0-dim slices of the kernel's output."""
+        assert label_sim is not None, "MITH must provide the label similarity"
+        xs = (res_img_cls, res_txt_cls, img_cls_hash, txt_cls_hash, tokens_hash_i, tokens_hash_t, trans_tokens_i, trans_tokens_t)
+        N, K = self.img_buffer_cls.shape
+        B, D = img_cls_hash.shape[0], res_img_cls.shape[-1]
+        if any(tuple(t.shape) != (B, D) for t in xs[:2]) or any(tuple(t.shape) != (B, K) for t in xs[2:6]) \
+                or any(tuple(t.shape) != (K, B, D) for t in xs[6:]) or tuple(label_sim.shape) != (N, B):
+            raise RuntimeError("MITH loss: inputs %s and label_sim %s do not fit a [%d, %d] buffer"
+                               % ([tuple(t.shape) for t in xs], tuple(label_sim.shape), N, K))
+        rows = self._rows(indexs, N, B)                   # host indices are checked before anything is launched
+        for t in xs:
+            if not t.is_cuda:
+                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        dev = img_cls_hash.device
+        if self.img_buffer_cls.device != dev:             # :170-173 -- all four names end up on the one device tensor
+            self._bind_buffer(self.img_buffer_cls.to(dev, non_blocking=True))
+        if label_sim.device != dev:
+            label_sim = label_sim.to(dev)
+        Y = self.img_buffer_cls
+        Y.index_copy_(0, rows.to(dev), tokens_hash_t.detach().to(Y.dtype))   # :174-177: of the four writes, tokens_hash_t's stays
+        out = _MITHLoss.apply(self, Y, label_sim.float().contiguous(), *xs)
+        v = out.detach()
+        loss_dict = {"All loss": v[0],
+                     "LikeHood": {"intra_tokens": {"image": v[1], "text": v[2]}, "cls_inter": {"image": v[3], "text": v[4]}},
+                     "Quantization": {"image": v[5], "text": v[6]},
+                     "InfoNCE": {"cls": v[7], "tokens": v[8]},
+                     "Distillation": v[9]}
+        return out[0], loss_dict
+
+    @staticmethod
+    def _rows(indexs, N, B):
+        """the batch's buffer rows as an int64 tensor (on the host unless they came on the device).  numpy arrays, lists and host
+        tensors are range-checked here (IndexError, as the reference's indexing raises); rows below 0 count from the end, as in torch
+        indexing.  Rows on the device are taken as they are: checking them would synchronise."""
+        if indexs is None:
+            raise RuntimeError("MITH loss needs `indexs`, the batch's rows in the training set")
+        if isinstance(indexs, torch.Tensor) and indexs.is_cuda:
+            idx = indexs.to(torch.int64).reshape(-1)
+            idx = torch.where(idx < 0, idx + N, idx)
+        else:
+            host = np.asarray(indexs.cpu() if isinstance(indexs, torch.Tensor) else indexs).astype(np.int64).reshape(-1)
+            bad = host[(host < -N) | (host >= N)]
+            if bad.size:
+                raise IndexError("MITH loss: index %d is out of bounds for the buffer of %d rows" % (int(bad[0]), N))
+            idx = torch.from_numpy(np.where(host < 0, host + N, host))
+        if idx.numel() != B:
+            raise RuntimeError("MITH loss: %d indices for a batch of %d" % (idx.numel(), B))
+        return idx
+
+    def object_function(self, res_img_cls, img_cls_hash, tokens_hash_i, trans_tokens_i, res_txt_cls, txt_cls_hash, tokens_hash_t,
+                        trans_tokens_t, labels=None, indexs=None, label_sim=None, **kwags):
+        """reference :234-241: compute_loss with the same keywords"""
+        return self.compute_loss(res_img_cls=res_img_cls, img_cls_hash=img_cls_hash, tokens_hash_i=tokens_hash_i,
+                                 trans_tokens_i=trans_tokens_i, res_txt_cls=res_txt_cls, txt_cls_hash=txt_cls_hash,
+                                 tokens_hash_t=tokens_hash_t, trans_tokens_t=trans_tokens_t, labels=labels, indexs=indexs,
+                                 label_sim=label_sim, **kwags)
 
     @classmethod
     def from_config(cls, cfg, output_dim=16, train_num=10000):

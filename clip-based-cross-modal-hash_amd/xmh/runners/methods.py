@@ -93,6 +93,29 @@ class DSPHTrainer(_MethodTrainer):
 class MITHTrainer(_MethodTrainer):
     """runners/MITH/runner.py:125-131: code = sign(cls_hash + tokens_hash); the text tower gets the padding mask."""
 
+    hash_scale = 1                                              # runners/MITH/runner.py:39
+    loss_type = "l1"                                            # runners/MITH/runner.py:28-32: only named in the display line
+
+    def compute_loss(self, res_img_cls, img_cls_hash, tokens_hash_i, trans_tokens_i, res_txt_cls, txt_cls_hash, tokens_hash_t,
+                     trans_tokens_t, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
+        """runners/MITH/runner.py:84-96: the objective of one batch (xmh_mith_loss.hip behind torch.autograd), differentiable with
+        respect to the eight head outputs.  label_sim = calc_label_sim(train_labels, label), [train_num, B], is formed on the codes'
+        device, with the packed train labels kept there between calls; the display line needs the training loop's loader and
+        optimiser, which this package does not build, and is skipped without them."""
+        dev = img_cls_hash.device
+        cached = getattr(self, "_train_lab", None)
+        if cached is None or cached[0] is not self.train_labels or cached[1] != dev:
+            tl = torch.as_tensor(self.train_labels)
+            cached = self._train_lab = (self.train_labels, dev, R.pack_labels(tl.to(dev)), tl.shape[1])
+        label_sim = R.label_sim(cached[2], R.pack_labels(torch.as_tensor(label).to(dev)), cached[3])
+        all_loss, loss_dict = self.model.object_function(res_img_cls=res_img_cls, img_cls_hash=img_cls_hash, tokens_hash_i=tokens_hash_i,
+                                                         trans_tokens_i=trans_tokens_i, res_txt_cls=res_txt_cls, txt_cls_hash=txt_cls_hash,
+                                                         tokens_hash_t=tokens_hash_t, trans_tokens_t=trans_tokens_t, labels=label,
+                                                         indexs=index, label_sim=label_sim, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=img_cls_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)
         return img_cls_hash + tokens_hash_i, txt_cls_hash + tokens_hash_t

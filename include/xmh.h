@@ -560,6 +560,45 @@ int xmh_hyp_loss_grad(const float* x, const float* y, const float* P, int64_t B,
                       float threshold, float alpha, const float* upstream, float* grad_x, float* grad_y, float* grad_P,
                       int accumulate, void* ws, size_t ws_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * MITH's training objective (models/MITH/MITH.py:116-232): forward, and its gradient with respect to its eight inputs (what
+ * loss.backward() of runners/MITH/runner.py:121 hands to the hash heads).  All tensors are fp32, contiguous, on the device:
+ *   res_img_cls, res_txt_cls [B, D]; img_cls_hash, txt_cls_hash, tokens_hash_i, tokens_hash_t [B, K];
+ *   trans_tokens_i, trans_tokens_t [K, B, D] (the reference's LND layout, read in place);
+ *   buffer [N, K] the rolling code buffer AFTER this step's row write (on the GPU the reference's four buffers are one tensor);
+ *   label_sim [N, B] any float similarity.
+ * The weights are the reference's hyper_* (defaults 1, 1, 50, 10, 8, 0.01, 0.99); temperature is InfoNCE's (0.07).
+ * N <= 2^22, B <= 1024, K <= 256, D <= 2048 (XMH_ENOTSUP beyond); no alignment requirement on K or D.  Neither call
+ * synchronises with the host or allocates; sums run in one fixed order (two calls on the same inputs agree to the bit).
+ * Workspace: xmh_mith_loss_ws_bytes(N, B, K, D) bytes of device memory, 256-byte aligned (0 for a shape outside the bounds).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_mith_loss_args {
+    int64_t N;
+    int B, K, D;
+    const float* res_img_cls;
+    const float* res_txt_cls;
+    const float* img_cls_hash;
+    const float* txt_cls_hash;
+    const float* tokens_hash_i;
+    const float* tokens_hash_t;
+    const float* trans_tokens_i;
+    const float* trans_tokens_t;
+    const float* buffer;
+    const float* label_sim;
+    double hyper_tokens_intra, hyper_distill, hyper_info_nce, hyper_cls_inter, hyper_quan, hyper_alpha, hyper_lambda;
+    double temperature;
+} xmh_mith_loss_args;
+size_t xmh_mith_loss_ws_bytes(int64_t N, int B, int K, int D);
+/* out10 (device, 10 doubles) = (loss, intra_i, intra_t, i2t, t2i, quan_i, quan_t, nce_cls, nce_tokens, distillation): the
+ * unweighted terms of the reference's loss_dict except distillation, which is weighted as there; loss is the weighted total. */
+int xmh_mith_loss(const xmh_mith_loss_args* args, void* ws, size_t ws_bytes, double* out10, xmh_stream_t stream);
+/* grads: 8 device pointers in the input order (res_img_cls, res_txt_cls, img_cls_hash, txt_cls_hash, tokens_hash_i, tokens_hash_t,
+ * trans_tokens_i, trans_tokens_t), each with its input's shape, or NULL when that gradient is not needed.  They are written, or
+ * added to when accumulate != 0, with upstream[0] (device float, NULL = 1) folded in.  The clamp's gradient passes on the closed
+ * interval [-64, 64], as torch's does. */
+int xmh_mith_loss_grad(const xmh_mith_loss_args* args, const float* upstream, float* const* grads, int accumulate, void* ws,
+                       size_t ws_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
