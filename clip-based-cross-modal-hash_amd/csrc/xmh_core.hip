@@ -47,7 +47,7 @@ int raise_dynamic_lds(const void* kern, size_t bytes, const char* who) {
 }
 
 // ---- per-kernel event timing (bench only) ----------------------------------------------------------
-constexpr int kProfSlots = 32;
+constexpr int kProfSlots = 64;       // named kernels plus one name per GEMM tile instance (xmh_gemm.hip)
 struct ProfSlot {
     char name[48];
     hipEvent_t a, b;

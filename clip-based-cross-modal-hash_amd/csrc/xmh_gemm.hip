@@ -663,8 +663,20 @@ __global__ __launch_bounds__(256) void k_quickgelu_planes(const float* __restric
     }
 }
 
+// profiling name of one tile instance, "g16_<TBM>x<TBN>_w<waves>_a<A planes>w<W planes>_bk<BK>": with xmh_prof_enable on, every launch is
+// counted under it as well as under gemm_f16 / gemm_s16, so a test can tell which tile a shape ran on (tests/test_gpu_encode_numerics.py)
+template <int WM, int WN, int MI, int NJ, int NA, int NW, int BK>
+const char* g16_tile_name() {
+    static const struct Name {
+        char s[48];
+        Name() { snprintf(s, sizeof(s), "g16_%dx%d_w%d_a%dw%d_bk%d", 32 * MI * WM, 32 * NJ * WN, WM * WN, NA, NW, BK); }
+    } name;
+    return name.s;
+}
+
 template <int WM, int WN, int MI, int NJ, int NA, int NW, int BK, int MINB>
 int launch_g16(const GArgsP& a, hipStream_t st) {
+    xmh::ProfScope prof(g16_tile_name<WM, WN, MI, NJ, NA, NW, BK>(), st);
     constexpr int TBM = 32 * MI * WM, TBN = 32 * NJ * WN;
     constexpr size_t stage_b = (size_t)2 * (NA * TBM + NW * TBN) * BK * 2, epi_b = (size_t)WM * WN * G16Epi<NJ>::kWaveBytes;
     constexpr size_t lds = stage_b > epi_b ? stage_b : epi_b;     // the epilogue regions reuse the staging buffers

@@ -4,9 +4,10 @@
 // whatever feeds a GEMM stores its result directly in the GEMM's operand format instead of fp32:
 //   fast mode   one plane   hi = half(x), round to nearest;
 //   parity mode two planes  x = hi + lo + r: hi = x truncated to 11 significant bits (a mask: exactly an fp16 value inside the
-//               fp16 exponent range), lo = half(x - hi) rounded toward zero, |r| <= 2^-21 |x| (for |x| below 2^-3 the low part is
-//               subnormal: absolute error <= 2^-24).  Both parts come from v_cvt_pkrtz_f16_f32, which saturates at 65504
-//               instead of producing inf.  Every fp16 x fp16 product is exact in fp32, so  acc += lo*w; acc += hi*w
+//               fp16 exponent range), lo = half(x - hi) rounded toward zero, |r| <= 2^-21 |x| for 2^-3 <= |x| < 65536.  Below 2^-3
+//               the low part is subnormal, below 2^-14 the high part too (it loses the bits under 2^-24 that the mask kept):
+//               |r| <= 2^-23 absolute there.  Both parts come from v_cvt_pkrtz_f16_f32, which saturates at 65504 instead of
+//               producing inf: from 65536 up hi is 65504 and the result is finite but wrong.  Every fp16 x fp16 product is exact in fp32, so  acc += lo*w; acc += hi*w
 //               reproduces the fp32 product to 2^-22 relative (reference weights are fp16 values held in fp32,
 //               models/CLIP/model.py:415-436).
 // Same bytes per element as fp32 in parity mode (2 + 2), half in fast mode.  The split is a pure function of the fp32 value, so

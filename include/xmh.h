@@ -298,7 +298,10 @@ int xmh_cast_f32_to_f16(const float* x, void* y_half, int64_t n, xmh_stream_t st
  *                      models/CLIP/model.py:415-436): two MFMAs per product, relative error 2^-22;
  *   W_lo_half != NULL: any fp32 weight, given as w = W_half + W_lo_half (host: hi = half(w), lo = half(w - hi)): three MFMAs
  *                      per product (the lo*lo term, 2^-22 relative, is dropped).
- * Requires |a| < 65504 (larger values saturate).  Same shape rules as xmh_gemm_nt_h16 (16-byte aligned rows, K % 32 == 0). */
+ * Domain |a| < 65536: there a = hi + lo to 2^-21 |a| (2^-23 absolute below 2^-3, where the planes turn subnormal).  From 65536
+ * up hi saturates at 65504: the result stays finite but is wrong.  inf and NaN in A make their output row non-finite.  (Fast
+ * mode's single plane, half(a) rounded to nearest, is inf from 65520 up.)  Same shape rules as xmh_gemm_nt_h16 (16-byte aligned
+ * rows, K % 32 == 0). */
 int xmh_gemm_nt_split16(const float* A, int64_t lda, const void* W_half, const void* W_lo_half, int64_t ldw, const float* bias,
                         const float* residual, int64_t ldr, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                         int act, xmh_stream_t stream);

@@ -99,9 +99,9 @@ def vit_front(sd, image):
     """conv1 + class / positional embedding + ln_pre (models/CLIP/model.py:232-244) -> x [B, L, width] entering the block stack"""
     w = sd["visual.conv1.weight"]
     width, patch = w.shape[0], w.shape[-1]
-    x = F.conv2d(image.float(), w, stride=patch)
+    x = F.conv2d(image if image.dtype == torch.float64 else image.float(), w, stride=patch)    # float64 in -> float64 throughout
     x = x.reshape(x.shape[0], width, -1).permute(0, 2, 1)
-    cls = sd["visual.class_embedding"] + torch.zeros(x.shape[0], 1, width)
+    cls = sd["visual.class_embedding"] + torch.zeros(x.shape[0], 1, width, dtype=x.dtype)
     x = torch.cat([cls, x], dim=1) + sd["visual.positional_embedding"]
     return F.layer_norm(x, (width,), sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"], 1e-5)
 

@@ -2,8 +2,9 @@
 the encoder oracle, and the goldens generated from the reference's own modules.
 
 Tolerances (fp32 "parity mode", v_mfma_f32_32x32x2_f32): elementwise ops 1e-5 relative; whole 12-layer towers
-1e-4 relative to the reference golden (different but equally valid fp32 summation orders); fp16 "fast mode" is
-checked for the error level SURVEY H4 predicts, not for parity."""
+1e-5 relative to the reference golden (different but equally valid fp32 summation orders; one block whose GEMM inputs
+lost their low fp16 plane moves them by about 6e-5); fp16 "fast mode" is checked for the error level SURVEY H4
+predicts, not for parity.  tests/test_gpu_encode_numerics.py holds the same kernels to float64 per element and per row."""
 import os
 
 import numpy as np
@@ -243,15 +244,15 @@ def test_clip_towers_match_reference_goldens(ops, clip_models):
     g, W, m, m_rp = clip_models
     seed = int(g["seed"])
     image, (ids, pad) = W.synth_images(seed, 2).cuda(), W.synth_text(seed, 2)
-    assert rel(m.encode_image(image), torch.from_numpy(g["img_cls"])) < 1e-4
-    assert rel(m.encode_text(ids.cuda()), torch.from_numpy(g["txt_eos"])) < 1e-4
+    assert rel(m.encode_image(image), torch.from_numpy(g["img_cls"])) < 1e-5
+    assert rel(m.encode_text(ids.cuda()), torch.from_numpy(g["txt_eos"])) < 1e-5
     cls, tok, _ = m_rp.encode_image(image)
-    assert rel(cls, torch.from_numpy(g["img_cls_rp"])) < 1e-4 and rel(tok, torch.from_numpy(g["img_tokens_rp"])) < 1e-4
+    assert rel(cls, torch.from_numpy(g["img_cls_rp"])) < 1e-5 and rel(tok, torch.from_numpy(g["img_tokens_rp"])) < 1e-5
     eos, ttok, _, nm = m_rp.encode_text(ids.cuda(), key_padding_mask=pad.cuda())
-    assert rel(eos, torch.from_numpy(g["txt_eos_rp"])) < 1e-4
+    assert rel(eos, torch.from_numpy(g["txt_eos_rp"])) < 1e-5
     assert np.array_equal(nm.cpu().numpy(), g["txt_mask_rp"])
     keep = torch.from_numpy(~g["txt_mask_rp"].T)
-    assert rel(ttok.cpu()[keep], torch.from_numpy(g["txt_tokens_rp"])[keep]) < 1e-4
+    assert rel(ttok.cpu()[keep], torch.from_numpy(g["txt_tokens_rp"])[keep]) < 1e-5
 
 
 def test_whole_tower_entry_points_equal_the_primitive_chain(ops, clip_models):
@@ -588,7 +589,7 @@ def test_clip_batch_100_matches_oracle_on_a_subsample(ops, clip_models):
     with torch.no_grad():
         want_i, want_t = enc.clip_image(sd, image[pick]), enc.clip_text(sd, ids[pick])
     got_i, got_t = m.encode_image(image.cuda()), m.encode_text(ids.cuda())
-    assert rel(got_i[pick], want_i) < 1e-4 and rel(got_t[pick], want_t) < 1e-4
+    assert rel(got_i[pick], want_i) < 1e-5 and rel(got_t[pick], want_t) < 1e-5
     assert torch.equal(got_i[:2], m.encode_image(image[:2].cuda()))          # bitwise batch invariance
 
 
@@ -659,7 +660,7 @@ def test_fast_mode_fp16_error_and_bit_agreement(ops, clip_models):
         fast = m.encode_image(image)
     finally:
         ops.set_precision("f32")
-    assert rel(fast, ref) < 1e-2
+    assert 1e-5 < rel(fast, ref) < 2e-3
     proj = torch.randn(512, 64, generator=g_(1)).cuda()
     flips = ((ref @ proj).sign() != (fast @ proj).sign()).float().mean().item()
     assert flips < 0.01
