@@ -1,0 +1,536 @@
+// Train-mode forward and backward of the two small hash heads.
+//
+//   DCMHT  models/DCMHT/hash/hash.py:15-46   v = x Wv^T + bv, o = v Wo^T + bo (MultiheadAttention on a length-1 sequence), BatchNorm1d
+//          with BATCH statistics (image) or LayerNorm (text) -> nhat, n = nhat gamma + beta, f = relu(n W2^T + b2), pair softmax
+//   DSPH   models/DSPH/hash/hash.py:6-15     y = tanh(keep * (x W^T + b) / (1 - p)), the keep mask handed in by the caller
+//
+//   forward   DCMHT 4 launches: k_mm<NT> (v), k_mm<NT> (o), k_bn_train | k_ln_train, k_mm<NT> with the relu + pair-softmax epilogue
+//             DSPH  1 launch:   k_mm<NT> with the dropout + tanh epilogue
+//   backward  DCMHT k_pair_relu_bwd (df), k_mm<TN> (dW2, db2), k_mm<NN> (dn), k_norm_bwd_cols (dgamma, dbeta; BatchNorm: do as well),
+//             k_ln_bwd_rows (LayerNorm: do), k_mm<TN> (dWo, dbo), k_mm<NN> (dv), k_mm<TN> (dWv, dbv), k_mm<NN> (dx): 8 (BN) / 9 (LN)
+//             launches with every gradient asked for, fewer with frozen parameters (a product nobody reads is not launched)
+//             DSPH  k_tanh_drop_bwd (dz), k_mm<TN> (dW, db), k_mm<NN> (dx): 3 launches
+//
+// One product kernel, C[i][j] = sum_k A(i, k) B(j, k) over strided views, covers y = x W^T ("NT"), dx = dy W ("NN") and dW = dy^T x ("TN",
+// the reduction runs over the batch: no alignment assumption, B = 1 works).  Exact fp32: every output element is a chain of fmaf over each 32 consecutive k,
+// the 32-blocks added in index order -- one fixed order, so two calls agree to the bit and forward and backward see the same numbers.  The bias gradients
+// (column sums of dy) ride on the TN kernel's pass over dy, summed in double in row order.  No float atomics, no host synchronisation, no
+// allocation.  The relu mask of backward is the sign of the f that forward stored: nothing is evaluated twice.
+// Shapes are small (B <= 1024, E = 512, N <= 512 in practice): launch- and latency-bound, a few hundred KB of L2-resident operands.
+#include "xmh_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxB = 4096, kMaxE = 2048, kMaxN = 1024;
+constexpr int kT = 32;                           // product tile: 32 x 32 outputs per block, 32 k per LDS stage, 2 x 2 outputs per thread
+constexpr int kPad = kT + 1;
+constexpr int kCols = 32, kGroups = kThreads / kCols;   // column kernels: 32 adjacent columns x 8 interleaved row groups per block
+
+__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// what forward keeps for backward (DCMHT)
+struct Saved {
+    float* v;      // [B, E]
+    float* nhat;   // [B, E] normalised activations before the affine
+    float* n;      // [B, E] after it (the operand of dW2 = df^T n)
+    float* rstd;   // [E] (BatchNorm, per column) or [B] (LayerNorm, per row)
+    float* f;      // [B, N] relu output: its sign is the mask
+    float* p;      // [B, N] probabilities
+};
+
+__host__ __device__ inline size_t saved_layout(int64_t B, int E, int N, char* base, Saved* s) {
+    size_t off = 0;
+    const size_t be = align256((size_t)B * E * 4), bn = align256((size_t)B * N * 4);
+    const size_t o_v = off;    off += be;
+    const size_t o_nh = off;   off += be;
+    const size_t o_n = off;    off += be;
+    const size_t o_r = off;    off += align256((size_t)(B > E ? B : E) * 4);
+    const size_t o_f = off;    off += bn;
+    const size_t o_p = off;    off += bn;
+    if (s) {
+        s->v = reinterpret_cast<float*>(base + o_v);
+        s->nhat = reinterpret_cast<float*>(base + o_nh);
+        s->n = reinterpret_cast<float*>(base + o_n);
+        s->rstd = reinterpret_cast<float*>(base + o_r);
+        s->f = reinterpret_cast<float*>(base + o_f);
+        s->p = reinterpret_cast<float*>(base + o_p);
+    }
+    return off;
+}
+
+// workspace: a [B, E] (o in forward; dn, then do in place, in backward), b [B, E] (dv), c [B, N] (df)
+struct Work {
+    float *a, *b, *c;
+};
+
+__host__ __device__ inline size_t work_layout(int64_t B, int E, int N, char* base, Work* w) {
+    const size_t be = align256((size_t)B * E * 4), bn = align256((size_t)B * N * 4);
+    if (w) {
+        w->a = reinterpret_cast<float*>(base);
+        w->b = reinterpret_cast<float*>(base + be);
+        w->c = reinterpret_cast<float*>(base + 2 * be);
+    }
+    return 2 * be + bn;
+}
+
+enum { EPI_PLAIN = 0, EPI_RELU_PAIR = 1, EPI_DROP_TANH = 2 };
+
+struct MmOut {
+    float* C;                 // [I, J] row-major
+    const float* bias;        // [J] added to every row, or NULL
+    int accumulate;           // C += instead of C = (EPI_PLAIN), rowsum alike
+    float* rowsum;            // [I]: sum_k A(i, k) in double, k in index order (the bias gradient of the TN product), or NULL
+    int epi;
+    float* aux;               // EPI_RELU_PAIR: the probabilities' second copy (saved); C receives the probabilities, f the relu output
+    float* f;
+    const uint8_t* keep;      // EPI_DROP_TANH: [I, J] keep mask or NULL
+    float scale;              // 1 / (1 - p)
+};
+
+// C[i][j] = sum_k A[i * sai + k * sak] * B[j * sbj + k * sbk].  AK / BK: k is the unit-stride index of that operand (decides which
+// index the lanes of a load walk; the arithmetic does not depend on it).
+// SUM: also rowsum[i] = sum_k A(i, k) (only the TN instance that owes a bias gradient is compiled with it).
+template <bool AK, bool BK, bool SUM>
+__global__ __launch_bounds__(kThreads) void k_mm(const float* __restrict__ A, int64_t sai, int64_t sak, const float* __restrict__ Bm,
+                                                 int64_t sbj, int64_t sbk, int I, int J, int Kd, MmOut o) {
+    __shared__ float As[kT][kPad];               // [k][i]
+    __shared__ float Bs[kT][kPad];               // [k][j]
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int i0 = blockIdx.y * kT, j0 = blockIdx.x * kT;
+    const int lo = tid & 31, hi = tid >> 5;      // a load: 32 lanes along the unit-stride index, 8 steps along the other, 4 rounds
+    float ra[4], rb[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ai = AK ? hi + 8 * r : lo, ak = AK ? lo : hi + 8 * r;
+            const int bj = BK ? hi + 8 * r : lo, bk = BK ? lo : hi + 8 * r;
+            ra[r] = (i0 + ai < I && k0 + ak < Kd) ? A[(int64_t)(i0 + ai) * sai + (int64_t)(k0 + ak) * sak] : 0.0f;
+            rb[r] = (j0 + bj < J && k0 + bk < Kd) ? Bm[(int64_t)(j0 + bj) * sbj + (int64_t)(k0 + bk) * sbk] : 0.0f;
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ai = AK ? hi + 8 * r : lo, ak = AK ? lo : hi + 8 * r;
+            const int bj = BK ? hi + 8 * r : lo, bk = BK ? lo : hi + 8 * r;
+            As[ak][ai] = ra[r];
+            Bs[bk][bj] = rb[r];
+        }
+    };
+    float c00 = 0.0f, c01 = 0.0f, c10 = 0.0f, c11 = 0.0f;
+    double s0 = 0.0, s1 = 0.0;
+    const bool sums = SUM && blockIdx.x == 0 && tx == 0;
+    fetch(0);
+    for (int k0 = 0; k0 < Kd; k0 += kT) {
+        stash();
+        __syncthreads();
+        if (k0 + kT < Kd) fetch(k0 + kT);        // the next stage's loads fly over this stage's arithmetic
+        float p00 = 0.0f, p01 = 0.0f, p10 = 0.0f, p11 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kT; ++k) {           // zero padding past Kd: fmaf(0, 0, p) == p
+            const float a0 = As[k][2 * ty], a1 = As[k][2 * ty + 1], b0 = Bs[k][2 * tx], b1 = Bs[k][2 * tx + 1];
+            p00 = fmaf(a0, b0, p00);
+            p01 = fmaf(a0, b1, p01);
+            p10 = fmaf(a1, b0, p10);
+            p11 = fmaf(a1, b1, p11);
+            if (SUM) {
+                if (sums) {
+                    s0 += (double)a0;
+                    s1 += (double)a1;
+                }
+            }
+        }
+        c00 += p00;                              // two-level sum: a 32-term chain per stage, the stages in order -- the rounding
+        c01 += p01;                              // error of a 512-term dot product grows with sqrt(32) + sqrt(16), not sqrt(512)
+        c10 += p10;
+        c11 += p11;
+        __syncthreads();
+    }
+    const int j = j0 + 2 * tx;
+    const float acc[2][2] = {{c00, c01}, {c10, c11}};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = i0 + 2 * ty + r;
+        if (i >= I) continue;
+        if (sums) {
+            const float s = (float)(r ? s1 : s0);
+            o.rowsum[i] = o.accumulate ? o.rowsum[i] + s : s;
+        }
+        if (j >= J) continue;
+        const bool two = j + 1 < J;
+        float z0 = acc[r][0], z1 = acc[r][1];
+        if (o.bias) {
+            z0 += o.bias[j];
+            if (two) z1 += o.bias[j + 1];
+        }
+        float* c = o.C + (int64_t)i * J + j;
+        if (o.epi == EPI_PLAIN) {
+            c[0] = o.accumulate ? c[0] + z0 : z0;
+            if (two) c[1] = o.accumulate ? c[1] + z1 : z1;
+        } else if (o.epi == EPI_RELU_PAIR) {     // J is even (checked by the entry point) and j is: (j, j + 1) is one (off, on) pair
+            const float f0 = fmaxf(z0, 0.0f), f1 = fmaxf(z1, 0.0f), m = fmaxf(f0, f1);
+            const float e0 = expf(f0 - m), e1 = expf(f1 - m), inv = 1.0f / (e0 + e1);
+            const int64_t at = (int64_t)i * J + j;
+            o.f[at] = f0;
+            o.f[at + 1] = f1;
+            c[0] = o.aux[at] = e0 * inv;
+            c[1] = o.aux[at + 1] = e1 * inv;
+        } else {                                 // EPI_DROP_TANH
+            const int64_t at = (int64_t)i * J + j;
+            if (o.keep) {
+                z0 = o.keep[at] ? z0 * o.scale : 0.0f;
+                if (two) z1 = o.keep[at + 1] ? z1 * o.scale : 0.0f;
+            }
+            c[0] = tanhf(z0);
+            if (two) c[1] = tanhf(z1);
+        }
+    }
+}
+
+// fixed-order sum of the row groups' partials of one column; valid on every thread of the column
+__device__ __forceinline__ double group_sum(double v, double (*sh)[kCols], int col, int grp) {
+    sh[grp][col] = v;
+    __syncthreads();
+    double s = sh[0][col];
+    for (int g = 1; g < kGroups; ++g) s += sh[g][col];
+    __syncthreads();
+    return s;
+}
+
+// BatchNorm1d in training mode over o [B, E]: batch mean and BIASED variance (two passes, double), nhat, n, rstd per column, and the
+// running statistics updated in place with `momentum` and the UNBIASED variance (either pointer may be NULL: track_running_stats=False)
+__global__ __launch_bounds__(kThreads) void k_bn_train(const float* __restrict__ o, int B, int E, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps, float momentum, float* run_mean,
+                                                       float* run_var, Saved s) {
+    __shared__ double sh[kGroups][kCols];
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    const bool live = e < E;
+    double a = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) a += (double)o[(int64_t)b * E + e];
+    const double mean = group_sum(a, sh, col, grp) / (double)B;
+    a = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) {
+            const double d = (double)o[(int64_t)b * E + e] - mean;
+            a += d * d;
+        }
+    const double m2 = group_sum(a, sh, col, grp);
+    if (!live) return;
+    const float var = (float)(m2 / (double)B), fmean = (float)mean;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    const float g = gamma[e], bt = beta[e];
+    for (int b = grp; b < B; b += kGroups) {
+        const int64_t at = (int64_t)b * E + e;
+        const float nh = (o[at] - fmean) * rstd;
+        s.nhat[at] = nh;
+        s.n[at] = fmaf(nh, g, bt);
+    }
+    if (grp == 0) {
+        s.rstd[e] = rstd;
+        if (run_mean) run_mean[e] = (1.0f - momentum) * run_mean[e] + momentum * fmean;
+        if (run_var) run_var[e] = (1.0f - momentum) * run_var[e] + momentum * (float)(m2 / (double)(B - 1));
+    }
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// LayerNorm over the rows of o [B, E] (fp32 in, statistics in double, biased variance): one wave per row
+__global__ __launch_bounds__(kThreads) void k_ln_train(const float* __restrict__ o, int B, int E, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps, Saved s) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float* row = o + (int64_t)b * E;
+    double a = 0.0;
+    for (int e = lane; e < E; e += 64) a += (double)row[e];
+    const double mean = wave_sum(a) / (double)E;
+    a = 0.0;
+    for (int e = lane; e < E; e += 64) {
+        const double d = (double)row[e] - mean;
+        a += d * d;
+    }
+    const float var = (float)(wave_sum(a) / (double)E), fmean = (float)mean;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    for (int e = lane; e < E; e += 64) {
+        const float nh = (row[e] - fmean) * rstd;
+        s.nhat[(int64_t)b * E + e] = nh;
+        s.n[(int64_t)b * E + e] = fmaf(nh, gamma[e], beta[e]);
+    }
+    if (lane == 0) s.rstd[b] = rstd;
+}
+
+// df from d probs: pair-softmax backward dz_a = p_a (g_a - p_a g_a - p_b g_b), then the relu mask of the f forward stored
+__global__ __launch_bounds__(kThreads) void k_pair_relu_bwd(const float* __restrict__ g, const float* __restrict__ p,
+                                                            const float* __restrict__ f, int64_t pairs, float* __restrict__ df) {
+    const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (q >= pairs) return;
+    const float g0 = g[2 * q], g1 = g[2 * q + 1], p0 = p[2 * q], p1 = p[2 * q + 1];
+    const float dot = fmaf(p1, g1, p0 * g0);
+    df[2 * q] = f[2 * q] > 0.0f ? p0 * (g0 - dot) : 0.0f;
+    df[2 * q + 1] = f[2 * q + 1] > 0.0f ? p1 * (g1 - dot) : 0.0f;
+}
+
+// dz = g (1 - y^2) keep / (1 - p)
+__global__ __launch_bounds__(kThreads) void k_tanh_drop_bwd(const float* __restrict__ g, const float* __restrict__ y,
+                                                            const uint8_t* __restrict__ keep, float scale, int64_t n,
+                                                            float* __restrict__ dz) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float yy = y[i];
+    float d = g[i] * fmaf(-yy, yy, 1.0f);
+    if (keep) d = keep[i] ? d * scale : 0.0f;
+    dz[i] = d;
+}
+
+// Column sums of the normalisation's backward: dgamma[e] = sum_b dn nhat, dbeta[e] = sum_b dn (double, fixed order; written or added
+// to; either may be NULL).  kBN: also do = gamma rstd (dn - mean(dn) - nhat mean(dn nhat)), in place over dn.
+template <bool kBN>
+__global__ __launch_bounds__(kThreads) void k_norm_bwd_cols(float* dn, const float* __restrict__ nhat, int B, int E,
+                                                            const float* __restrict__ gamma, const float* __restrict__ rstd,
+                                                            float* dgamma, float* dbeta, int accumulate) {
+    __shared__ double sh[kGroups][kCols];
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    const bool live = e < E;
+    double a = 0.0, c = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) {
+            const float d = dn[(int64_t)b * E + e];
+            a += (double)d * (double)nhat[(int64_t)b * E + e];
+            c += (double)d;
+        }
+    const double sg = group_sum(a, sh, col, grp), sb = group_sum(c, sh, col, grp);
+    if (!live) return;
+    if (grp == 0) {
+        if (dgamma) dgamma[e] = accumulate ? dgamma[e] + (float)sg : (float)sg;
+        if (dbeta) dbeta[e] = accumulate ? dbeta[e] + (float)sb : (float)sb;
+    }
+    if (kBN) {
+        const float mg = (float)(sg / (double)B), mb = (float)(sb / (double)B), w = gamma[e] * rstd[e];
+        for (int b = grp; b < B; b += kGroups) {
+            const int64_t at = (int64_t)b * E + e;
+            dn[at] = w * (dn[at] - mb - nhat[at] * mg);
+        }
+    }
+}
+
+// LayerNorm backward over one row (one wave): h = dn gamma, do = rstd (h - mean(h) - nhat mean(h nhat)), in place over dn
+__global__ __launch_bounds__(kThreads) void k_ln_bwd_rows(float* dn, const float* __restrict__ nhat, int B, int E,
+                                                          const float* __restrict__ gamma, const float* __restrict__ rstd) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    float* row = dn + (int64_t)b * E;
+    const float* nh = nhat + (int64_t)b * E;
+    double a = 0.0, c = 0.0;
+    for (int e = lane; e < E; e += 64) {
+        const float h = row[e] * gamma[e];
+        a += (double)h;
+        c += (double)h * (double)nh[e];
+    }
+    const float mh = (float)(wave_sum(a) / (double)E), mc = (float)(wave_sum(c) / (double)E), r = rstd[b];
+    for (int e = lane; e < E; e += 64) row[e] = r * (row[e] * gamma[e] - mh - nh[e] * mc);
+}
+
+// y [M, N] = x [M, K] w[N, K]^T (+ bias, epilogue)
+void launch_nt(hipStream_t st, const float* x, const float* w, int M, int N, int K, MmOut o) {
+    hipLaunchKernelGGL((k_mm<true, true, false>), dim3((N + kT - 1) / kT, (M + kT - 1) / kT), dim3(kThreads), 0, st, x, (int64_t)K, (int64_t)1, w,
+                       (int64_t)K, (int64_t)1, M, N, K, o);
+}
+
+// dx [M, K] = dy [M, N] w [N, K]
+void launch_nn(hipStream_t st, const float* dy, const float* w, int M, int N, int K, float* dx) {
+    MmOut o = {};
+    o.C = dx;
+    hipLaunchKernelGGL((k_mm<true, false, false>), dim3((K + kT - 1) / kT, (M + kT - 1) / kT), dim3(kThreads), 0, st, dy, (int64_t)N, (int64_t)1, w,
+                       (int64_t)1, (int64_t)K, M, K, N, o);
+}
+
+// dw [N, K] = dy [M, N]^T x [M, K] and, when db is not NULL, db [N] = column sums of dy from the same pass (weight_grads picks the route)
+void launch_tn(hipStream_t st, const float* dy, const float* x, int M, int N, int K, float* dw, float* db, int accumulate) {
+    MmOut o = {};
+    o.C = dw;
+    o.rowsum = db;
+    o.accumulate = accumulate;
+    const dim3 grid((K + kT - 1) / kT, (N + kT - 1) / kT);
+    if (db)
+        hipLaunchKernelGGL((k_mm<false, false, true>), grid, dim3(kThreads), 0, st, dy, (int64_t)1, (int64_t)N, x, (int64_t)1, (int64_t)K, N,
+                           K, M, o);
+    else
+        hipLaunchKernelGGL((k_mm<false, false, false>), grid, dim3(kThreads), 0, st, dy, (int64_t)1, (int64_t)N, x, (int64_t)1, (int64_t)K, N,
+                           K, M, o);
+}
+
+// bias gradient alone (its weight is frozen): column sums of dy [M, N] in double, row order
+__global__ __launch_bounds__(kThreads) void k_col_sum(const float* __restrict__ dy, int M, int N, float* db, int accumulate) {
+    __shared__ double sh[kGroups][kCols];
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    double a = 0.0;
+    if (e < N)
+        for (int b = grp; b < M; b += kGroups) a += (double)dy[(int64_t)b * N + e];
+    const double s = group_sum(a, sh, col, grp);
+    if (e < N && grp == 0) db[e] = accumulate ? db[e] + (float)s : (float)s;
+}
+
+void weight_grads(hipStream_t st, const float* dy, const float* x, int M, int N, int K, float* dw, float* db, int accumulate) {
+    if (dw)
+        launch_tn(st, dy, x, M, N, K, dw, db, accumulate);
+    else if (db)
+        hipLaunchKernelGGL(k_col_sum, dim3((N + kCols - 1) / kCols), dim3(kThreads), 0, st, dy, M, N, db, accumulate);
+}
+
+int check_shape(const char* who, int64_t B, int E, int N) {
+    if (B <= 0 || E <= 0 || N <= 0) return xmh::fail(XMH_EINVAL, "%s: bad shape B=%lld E=%d N=%d", who, (long long)B, E, N);
+    if (B > kMaxB || E > kMaxE || N > kMaxN)
+        return xmh::fail(XMH_ENOTSUP, "%s: B=%lld E=%d N=%d outside B <= %d, E <= %d, N <= %d", who, (long long)B, E, N, kMaxB, kMaxE, kMaxN);
+    return XMH_OK;
+}
+
+int check_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
+    if (!p) return xmh::fail(XMH_EINVAL, "%s: null %s", who, what);
+    if (have < need) return xmh::fail(XMH_EINVAL, "%s: %s of %zu bytes < %zu (xmh_head_dcmht_train_bytes)", who, what, have, need);
+    if (reinterpret_cast<uintptr_t>(p) & 255u) return xmh::fail(XMH_EINVAL, "%s: %s not 256-byte aligned", who, what);
+    return XMH_OK;
+}
+
+int check_dcmht(const char* who, const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N) {
+    if (int rc = check_shape(who, B, E, N)) return rc;
+    if (N & 1) return xmh::fail(XMH_EINVAL, "%s: N=%d is odd (N = 2K, one (off, on) pair per bit)", who, N);
+    if (!h || !x || !h->wv || !h->bv || !h->wo || !h->bo || !h->norm_w || !h->norm_b || !h->w2 || !h->b2)
+        return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    return XMH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t xmh_head_dcmht_train_bytes(int64_t B, int E, int N, size_t* workspace_bytes) {
+    const bool ok = B > 0 && E > 0 && N > 0 && !(N & 1) && B <= kMaxB && E <= kMaxE && N <= kMaxN;
+    if (workspace_bytes) *workspace_bytes = ok ? work_layout(B, E, N, nullptr, nullptr) : 0;
+    return ok ? saved_layout(B, E, N, nullptr, nullptr) : 0;
+}
+
+extern "C" int xmh_head_dcmht_train_forward(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, float* probs, void* saved,
+                                            size_t saved_bytes, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_train_forward");
+    const char* who = "xmh_head_dcmht_train_forward";
+    if (int rc = check_dcmht(who, h, x, B, E, N)) return rc;
+    if (!probs) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (h->norm_is_batchnorm && B < 2) return xmh::fail(XMH_EINVAL, "%s: BatchNorm in training mode needs more than 1 row", who);
+    if (int rc = check_buffer(who, "saved buffer", saved, saved_bytes, saved_layout(B, E, N, nullptr, nullptr))) return rc;
+    if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, work_layout(B, E, N, nullptr, nullptr))) return rc;
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, static_cast<char*>(saved), &s);
+    work_layout(B, E, N, static_cast<char*>(workspace), &w);
+    hipStream_t st = xmh::as_stream(stream);
+    MmOut o = {};
+    o.C = s.v;
+    o.bias = h->bv;
+    launch_nt(st, x, h->wv, (int)B, E, E, o);
+    o.C = w.a;
+    o.bias = h->bo;
+    launch_nt(st, s.v, h->wo, (int)B, E, E, o);
+    if (h->norm_is_batchnorm)
+        hipLaunchKernelGGL(k_bn_train, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, (int)B, E, h->norm_w, h->norm_b, h->eps,
+                           h->momentum, h->running_mean, h->running_var, s);
+    else
+        hipLaunchKernelGGL(k_ln_train, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, w.a, (int)B, E, h->norm_w, h->norm_b, h->eps, s);
+    o.C = probs;
+    o.bias = h->b2;
+    o.epi = EPI_RELU_PAIR;
+    o.aux = s.p;
+    o.f = s.f;
+    launch_nt(st, s.n, h->w2, (int)B, N, E, o);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dcmht_backward(const xmh_dcmht_train* h, const float* x, const float* d_probs, int64_t B, int E, int N,
+                                       const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate, void* workspace,
+                                       size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_backward");
+    const char* who = "xmh_head_dcmht_backward";
+    if (int rc = check_dcmht(who, h, x, B, E, N)) return rc;
+    if (!d_probs || !g) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (int rc = check_buffer(who, "saved buffer", saved, saved_bytes, saved_layout(B, E, N, nullptr, nullptr))) return rc;
+    if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, work_layout(B, E, N, nullptr, nullptr))) return rc;
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, static_cast<char*>(const_cast<void*>(saved)), &s);
+    work_layout(B, E, N, static_cast<char*>(workspace), &w);
+    hipStream_t st = xmh::as_stream(stream);
+    const int M = (int)B;
+    // what has to exist for the gradients asked for: each stage is needed by everything upstream of it
+    const bool need_dv = g->d_wv || g->d_bv || g->d_x;
+    const bool need_do = need_dv || g->d_wo || g->d_bo;
+    const bool need_dn = need_do || g->d_norm_w || g->d_norm_b;
+    if (!need_dn && !g->d_w2 && !g->d_b2) return XMH_OK;
+    const int64_t pairs = B * (N / 2);
+    hipLaunchKernelGGL(k_pair_relu_bwd, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_probs, s.p, s.f, pairs,
+                       w.c);
+    weight_grads(st, w.c, s.n, M, N, E, g->d_w2, g->d_b2, accumulate);
+    if (need_dn) {
+        launch_nn(st, w.c, h->w2, M, N, E, w.a);                                  // dn
+        if (h->norm_is_batchnorm) {
+            hipLaunchKernelGGL(k_norm_bwd_cols<true>, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, s.nhat, M, E, h->norm_w,
+                               s.rstd, g->d_norm_w, g->d_norm_b, accumulate);
+        } else {
+            if (g->d_norm_w || g->d_norm_b)
+                hipLaunchKernelGGL(k_norm_bwd_cols<false>, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, s.nhat, M, E,
+                                   h->norm_w, s.rstd, g->d_norm_w, g->d_norm_b, accumulate);
+            if (need_do)
+                hipLaunchKernelGGL(k_ln_bwd_rows, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, w.a, s.nhat, M, E, h->norm_w, s.rstd);
+        }
+    }
+    if (need_do) weight_grads(st, w.a, s.v, M, E, E, g->d_wo, g->d_bo, accumulate);
+    if (need_dv) {
+        launch_nn(st, w.a, h->wo, M, E, E, w.b);                                  // dv
+        weight_grads(st, w.b, x, M, E, E, g->d_wv, g->d_bv, accumulate);
+        if (g->d_x) launch_nn(st, w.b, h->wv, M, E, E, g->d_x);               // an activation gradient: written, never added to
+    }
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dsph_train_forward(const float* w, const float* b, const float* x, const uint8_t* keep, float p, int64_t B, int E,
+                                           int K, float* y, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dsph_train_forward");
+    const char* who = "xmh_head_dsph_train_forward";
+    if (int rc = check_shape(who, B, E, K)) return rc;
+    if (!w || !b || !x || !y) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (!(p >= 0.0f && p < 1.0f)) return xmh::fail(XMH_EINVAL, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+    MmOut o = {};
+    o.C = y;
+    o.bias = b;
+    o.epi = EPI_DROP_TANH;
+    o.keep = keep;
+    o.scale = 1.0f / (1.0f - p);
+    launch_nt(xmh::as_stream(stream), x, w, (int)B, K, E, o);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dsph_backward(const float* w, const float* x, const float* y, const uint8_t* keep, float p, const float* d_y,
+                                      int64_t B, int E, int K, float* d_w, float* d_b, float* d_x, int accumulate, void* workspace,
+                                      size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dsph_backward");
+    const char* who = "xmh_head_dsph_backward";
+    if (int rc = check_shape(who, B, E, K)) return rc;
+    if (!w || !x || !y || !d_y) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (!(p >= 0.0f && p < 1.0f)) return xmh::fail(XMH_EINVAL, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+    if (!workspace) return xmh::fail(XMH_EINVAL, "%s: null workspace", who);
+    if (workspace_bytes < (size_t)B * K * 4) return xmh::fail(XMH_EINVAL, "%s: workspace of %zu bytes < %zu (4 B K)", who, workspace_bytes, (size_t)B * K * 4);
+    if (!d_w && !d_b && !d_x) return XMH_OK;
+    hipStream_t st = xmh::as_stream(stream);
+    float* dz = static_cast<float*>(workspace);
+    const int64_t n = B * K;
+    hipLaunchKernelGGL(k_tanh_drop_bwd, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_y, y, keep, 1.0f / (1.0f - p),
+                       n, dz);
+    weight_grads(st, dz, x, (int)B, K, E, d_w, d_b, accumulate);
+    if (d_x) launch_nn(st, dz, w, (int)B, K, E, d_x);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}

@@ -77,6 +77,16 @@ class MithLossArgs(C.Structure):               # xmh_mith_loss_args
                 ("hyper_lambda", C.c_double), ("temperature", C.c_double)]
 
 
+class DcmhtTrain(C.Structure):                 # xmh_dcmht_train
+    _fields_ = [("wv", vp), ("bv", vp), ("wo", vp), ("bo", vp), ("norm_w", vp), ("norm_b", vp), ("running_mean", vp),
+                ("running_var", vp), ("w2", vp), ("b2", vp), ("norm_is_batchnorm", i32), ("eps", C.c_float), ("momentum", C.c_float)]
+
+
+class DcmhtGrads(C.Structure):                 # xmh_dcmht_grads
+    _fields_ = [("d_wv", vp), ("d_bv", vp), ("d_wo", vp), ("d_bo", vp), ("d_norm_w", vp), ("d_norm_b", vp), ("d_w2", vp),
+                ("d_b2", vp), ("d_x", vp)]
+
+
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
 PROTOTYPES = {
     "xmh_version": (i32, []),
@@ -154,6 +164,11 @@ PROTOTYPES = {
     "xmh_mith_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
     "xmh_mith_loss": (i32, [C.POINTER(MithLossArgs), vp, sz, vp, vp]),
     "xmh_mith_loss_grad": (i32, [C.POINTER(MithLossArgs), vp, C.POINTER(vp), i32, vp, sz, vp]),
+    "xmh_head_dcmht_train_bytes": (sz, [i64, i32, i32, C.POINTER(C.c_size_t)]),
+    "xmh_head_dcmht_train_forward": (i32, [C.POINTER(DcmhtTrain), vp, i64, i32, i32, vp, vp, sz, vp, sz, vp]),
+    "xmh_head_dcmht_backward": (i32, [C.POINTER(DcmhtTrain), vp, vp, i64, i32, i32, vp, sz, C.POINTER(DcmhtGrads), i32, vp, sz, vp]),
+    "xmh_head_dsph_train_forward": (i32, [vp, vp, vp, vp, C.c_float, i64, i32, i32, vp, vp]),
+    "xmh_head_dsph_backward": (i32, [vp, vp, vp, vp, C.c_float, vp, i64, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
     "xmh_topk_ws_bytes": (sz, [i64, i64, i32, i32]),
     "xmh_hamming_topk": (i32, [vp, vp, i64, i64, i32, i32, i64, vp, sz, vp, vp, vp]),
     "xmh_topk_ws_init": (i32, [i64, i64, i32, i32, vp, sz, vp]),

@@ -1,8 +1,9 @@
 """DCMHT model wrapper (reference models/DCMHT/DCMHT.py:11-70): backbone + DCMHT head, registered as "DCMHT"; the loss
 (:72-155: similarity_loss / soft_argmax_hash_loss / our_loss / object_function) through xmh_loss.hip.  `our_loss` /
 `object_function` are differentiable with respect to the two code matrices (`_Objective`: the gradient kernels of xmh_loss.hip
-behind torch.autograd, i.e. what `loss.backward()` of runners/DCMHT/runner.py:124 hands to the hash heads); the backward of
-the encoders themselves is outside this path."""
+behind torch.autograd, i.e. what `loss.backward()` of runners/DCMHT/runner.py:124 hands to the hash heads).  In `.train()` mode the
+heads carry that gradient on to every one of their parameters and to the embeddings (heads.py, xmh_head_grad.hip); the backward
+of the CLIP towers is not built, so the backbone is trained frozen: embeddings under no_grad, `model.hash(...)`."""
 import torch
 
 from .. import retrieval as R

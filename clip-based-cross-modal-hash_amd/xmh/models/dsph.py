@@ -6,7 +6,10 @@ reference's own class) -- so the module tree here has it too and ``load_state_di
 The reference reads the HyP threshold out of ``loss/codetable.xlsx`` at construction (:33-35).  Here it is, in this order: an
 explicit ``threshold`` (constructor argument or ``cfg.threshold``); the cell of ``cfg.codetable`` (a path to the user's copy of
 that workbook, read by codetable.hyp_threshold); otherwise unset -- the model constructs and encodes as usual and the first loss
-call raises ValueError."""
+call raises ValueError.
+
+In `.train()` mode the two heads (heads.py::DSPHLinearHash) run dropout with a keep mask drawn on the device and carry the loss
+gradient on to `fc.weight`, `fc.bias` and the embeddings (xmh_head_grad.hip); the backward of the CLIP towers is not built."""
 import torch
 import torch.nn as nn
 

@@ -186,7 +186,9 @@ class BaseTrainer:
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t}, mAP: {self.max_mapt2i}")
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")
+        raise NotImplementedError("train_epoch is not built: the losses and the DCMHT / DSPH hash heads have their backward (a frozen "
+                                  "backbone trains the heads with a stock torch optimiser), but the backward of the CLIP towers and of "
+                                  "MITH's / TwDH's heads, and the BertAdam optimiser, are still missing")
 
     def compute_loss(self, *a, **k):
         raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")

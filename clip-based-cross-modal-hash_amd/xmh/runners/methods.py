@@ -65,7 +65,8 @@ class DCMHTTrainer(_MethodTrainer):
 
     def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
         """runners/DCMHT/runner.py:97-105: the objective of one batch.  The returned loss is differentiable with respect to
-        img_hash / txt_hash (xmh_loss.hip behind torch.autograd); the display line of :101-103 needs the training loop's
+        img_hash / txt_hash (xmh_loss.hip behind torch.autograd), and through them -- when they come from `model.hash` in
+        .train() mode -- with respect to every parameter of the heads (xmh_head_grad.hip); the display line of :101-103 needs the training loop's
         loader and optimiser, which this package does not build, and is skipped without them."""
         all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, labels=label, indexs=index, **kwags)
         if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:

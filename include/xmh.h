@@ -602,6 +602,52 @@ int xmh_mith_loss(const xmh_mith_loss_args* args, void* ws, size_t ws_bytes, dou
 int xmh_mith_loss_grad(const xmh_mith_loss_args* args, const float* upstream, float* const* grads, int accumulate, void* ws,
                        size_t ws_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DCMHT / DSPH hash heads in TRAINING mode: forward that keeps what backward reads, and backward to every parameter of the head
+ * and to the input embeddings (models/DCMHT/hash/hash.py:15-46, models/DSPH/hash/hash.py:6-15).  Plain fp32 weight
+ * pointers, exact-fp32 FMA products (not the precision-tagged xmh_linear descriptors: cached weight planes go stale after every
+ * optimiser step).  B <= 4096, E <= 2048, N <= 1024 (XMH_ENOTSUP beyond); no alignment requirement on B, E or K.  No call
+ * synchronises with the host or allocates; every sum has one fixed order (two calls on the same inputs agree to the bit).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_dcmht_train {
+    const float *wv, *bv;                              /* rows [2E, 3E) of atten.in_proj_weight [E, E] / in_proj_bias [E] */
+    const float *wo, *bo;                              /* atten.out_proj [E, E], [E] */
+    const float *norm_w, *norm_b;                      /* [E] */
+    float *running_mean, *running_var;                 /* BatchNorm: [E], updated in place by forward; NULL = not tracked */
+    const float *w2, *b2;                              /* fc2 [N, E], [N] with N = 2K */
+    int norm_is_batchnorm;                             /* 1: BatchNorm1d with batch statistics; 0: LayerNorm */
+    float eps, momentum;
+} xmh_dcmht_train;
+/* where backward puts each gradient; NULL = not needed (its product is not launched) */
+typedef struct xmh_dcmht_grads {
+    float *d_wv, *d_bv, *d_wo, *d_bo, *d_norm_w, *d_norm_b, *d_w2, *d_b2;   /* shapes of the parameters above */
+    float* d_x;                                        /* [B, E] */
+} xmh_dcmht_grads;
+/* bytes of the saved buffer (returned) and of the workspace (*workspace_bytes, may be NULL) for one head at this shape; both
+ * 256-byte aligned device memory, both non-decreasing in B.  0 for a shape outside the bounds or an odd N.
+ * Saved buffer, each section rounded up to 256 bytes: v [B, E], nhat [B, E] (normalised, before the affine), n [B, E] (after it),
+ * rstd [max(B, E)] (per column for BatchNorm, per row for LayerNorm), f [B, N] (relu output: its sign is backward's mask),
+ * probs [B, N].  x is not copied: the caller hands the same x to backward. */
+size_t xmh_head_dcmht_train_bytes(int64_t B, int E, int N, size_t* workspace_bytes);
+/* x [B, E] -> probs [B, N].  BatchNorm: batch mean and biased variance normalise; running_mean / running_var move by `momentum`
+ * towards the batch mean / the UNBIASED batch variance (num_batches_tracked is the caller's); B = 1 is XMH_EINVAL. */
+int xmh_head_dcmht_train_forward(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, float* probs, void* saved,
+                                 size_t saved_bytes, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* d_probs [B, N] -> the gradients named in g.  Parameter gradients are written, or added to when accumulate != 0; d_x is always
+ * written.  `saved` is what the forward of the SAME x and parameters filled (the relu mask is taken from it, never re-derived). */
+int xmh_head_dcmht_backward(const xmh_dcmht_train* h, const float* x, const float* d_probs, int64_t B, int E, int N,
+                            const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate, void* workspace,
+                            size_t workspace_bytes, xmh_stream_t stream);
+/* y [B, K] = tanh(keep * (x w^T + b) / (1 - p)): w [K, E], b [K], keep [B, K] bytes (non-zero = kept) or NULL for no dropout.
+ * The library draws no random numbers. */
+int xmh_head_dsph_train_forward(const float* w, const float* b, const float* x, const uint8_t* keep, float p, int64_t B, int E,
+                                int K, float* y, xmh_stream_t stream);
+/* d_y [B, K] and the forward's y, keep, p -> d_w [K, E], d_b [K] (written, or added to when accumulate != 0), d_x [B, E]
+ * (written); each may be NULL.  Workspace: 4 B K bytes of device memory. */
+int xmh_head_dsph_backward(const float* w, const float* x, const float* y, const uint8_t* keep, float p, const float* d_y,
+                           int64_t B, int E, int K, float* d_w, float* d_b, float* d_x, int accumulate, void* workspace,
+                           size_t workspace_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
