@@ -11,14 +11,9 @@
 //                         then one pass over the sorted row for sum(ordinal / rank).  Replaces the round-2 comparison-counting
 //                         kernel (O(R * n_rel) per query: 8e12 comparisons at the COCO shape).
 #include "xmh_common.h"
+#include "xmh_device.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_row_norm(const float* __restrict__ x, int64_t rows, int D, float* __restrict__ y,
                                                   float* __restrict__ sqnorm) {
@@ -27,7 +22,7 @@ __global__ __launch_bounds__(256) void k_row_norm(const float* __restrict__ x, i
     if (r >= rows) return;
     float s = 0.0f;
     for (int c = lane; c < D; c += 64) s = fmaf(x[r * D + c], x[r * D + c], s);
-    s = wave_sum_f(s);
+    s = xmh::wave_sum(s);
     if (sqnorm && lane == 0) sqnorm[r] = s;
     if (y) {
         const float n = sqrtf(s);

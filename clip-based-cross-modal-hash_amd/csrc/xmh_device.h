@@ -1,0 +1,54 @@
+// Device helpers shared by the training kernels (xmh_hyp, xmh_mith_loss, xmh_head_grad), xmh_encode and xmh_dense, and the workspace
+// carver of the host entry points.  The scan, top-k and GEMM kernels keep their own hand-scheduled idioms; xmh_loss.hip keeps its
+// block_sum, whose result lives on thread 0 only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace xmh {
+
+__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Carve-out of a caller-owned buffer in 256-byte aligned pieces.  The same walk sizes the buffer (base == nullptr: every take
+// returns null) and hands out the pieces, so the two cannot disagree; `used` is the byte total so far.
+struct Arena {
+    char* base;
+    size_t used = 0;
+    __host__ __device__ explicit Arena(void* p) : base(static_cast<char*>(p)) {}
+    template <typename T>
+    __host__ __device__ T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used = align256(used + count * sizeof(T));
+        return p;
+    }
+};
+
+// Wave reductions by xor butterfly, 32 down to 1: every lane ends with the same bits (each step combines the same two values, in
+// either order), and the order is fixed, which is what the bit-reproducibility promises of the callers rest on.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float, double or int");
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+
+// Block sum in a fixed order (wave butterflies, then the kWaves waves in index order); valid on every thread.  sh: kWaves elements.
+template <int kWaves, typename T>
+__device__ __forceinline__ T block_sum(T v, T* sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = sh[0];
+    for (int w = 1; w < kWaves; ++w) s += sh[w];
+    __syncthreads();
+    return s;
+}
+
+}  // namespace xmh

@@ -15,17 +15,14 @@
 //   xmh_bitwise_hash      MITH BitwiseHashing (models/MITH/hash/hash.py:68-85)
 // Every one of these is HBM-bound elementwise / row-reduction work; the GEMMs around them dominate the time.
 #include "xmh_common.h"
+#include "xmh_device.h"
 #include "xmh_planes.h"
 
 #include <stdlib.h>
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+using xmh::wave_sum;
 
 // ---- LayerNorm: one wave per row, row cached in registers (D <= 64*16) -------------------------------
 constexpr int kLnMaxPerLane = 16;

@@ -7,6 +7,7 @@
 //   text : embed + pos -> blocks (causal [+ key padding]) -> ln_final -> GEMM text_projection -> EOS row
 //   block: LN, GEMM qkv, attention, GEMM out + residual, LN, GEMM c_fc + QuickGELU, GEMM c_proj + residual
 #include "xmh_common.h"
+#include "xmh_device.h"
 #include "xmh_planes.h"
 
 namespace {
@@ -15,20 +16,7 @@ constexpr int kActNone = 0, kActQuickGelu = 1, kActGeluErf = 2, kActTanh = 3, kA
 constexpr int kPrecParity = 0, kPrecFast = 1, kPrecExact = 2;
 constexpr float kLnEps = 1e-5f;                      // nn.LayerNorm default, as in the reference
 
-inline size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
-
-// carve-out of the workspace; the same arithmetic sizes it (xmh_clip_workspace_bytes) and hands out the pieces
-struct Arena {
-    char* base;
-    size_t used = 0;
-    explicit Arena(void* p) : base(static_cast<char*>(p)) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += align_up(count * sizeof(T));
-        return p;
-    }
-};
+using xmh::Arena;                                    // the same arithmetic sizes the workspace (xmh_clip_workspace_bytes) and hands out the pieces
 
 // Parity and fast mode keep every GEMM input as fp16 operand planes (xmh_planes.h), written by the kernel that produces it:
 // LayerNorm -> qkv / c_fc, attention -> out_proj, the c_fc epilogue (QuickGELU) -> c_proj.  Only the residual stream x and the

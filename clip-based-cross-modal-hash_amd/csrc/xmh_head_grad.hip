@@ -18,6 +18,7 @@
 // allocation.  The relu mask of backward is the sign of the f that forward stored: nothing is evaluated twice.
 // Shapes are small (B <= 1024, E = 512, N <= 512 in practice): launch- and latency-bound, a few hundred KB of L2-resident operands.
 #include "xmh_common.h"
+#include "xmh_device.h"
 
 namespace {
 
@@ -26,8 +27,6 @@ constexpr int kMaxB = 4096, kMaxE = 2048, kMaxN = 1024;
 constexpr int kT = 32;                           // product tile: 32 x 32 outputs per block, 32 k per LDS stage, 2 x 2 outputs per thread
 constexpr int kPad = kT + 1;
 constexpr int kCols = 32, kGroups = kThreads / kCols;   // column kernels: 32 adjacent columns x 8 interleaved row groups per block
-
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // what forward keeps for backward (DCMHT)
 struct Saved {
@@ -39,24 +38,17 @@ struct Saved {
     float* p;      // [B, N] probabilities
 };
 
-__host__ __device__ inline size_t saved_layout(int64_t B, int E, int N, char* base, Saved* s) {
-    size_t off = 0;
-    const size_t be = align256((size_t)B * E * 4), bn = align256((size_t)B * N * 4);
-    const size_t o_v = off;    off += be;
-    const size_t o_nh = off;   off += be;
-    const size_t o_n = off;    off += be;
-    const size_t o_r = off;    off += align256((size_t)(B > E ? B : E) * 4);
-    const size_t o_f = off;    off += bn;
-    const size_t o_p = off;    off += bn;
-    if (s) {
-        s->v = reinterpret_cast<float*>(base + o_v);
-        s->nhat = reinterpret_cast<float*>(base + o_nh);
-        s->n = reinterpret_cast<float*>(base + o_n);
-        s->rstd = reinterpret_cast<float*>(base + o_r);
-        s->f = reinterpret_cast<float*>(base + o_f);
-        s->p = reinterpret_cast<float*>(base + o_p);
-    }
-    return off;
+__host__ __device__ inline size_t saved_layout(int64_t B, int E, int N, void* base, Saved* s) {
+    xmh::Arena ar(base);
+    Saved v;
+    v.v = ar.take<float>((size_t)B * E);
+    v.nhat = ar.take<float>((size_t)B * E);
+    v.n = ar.take<float>((size_t)B * E);
+    v.rstd = ar.take<float>((size_t)(B > E ? B : E));
+    v.f = ar.take<float>((size_t)B * N);
+    v.p = ar.take<float>((size_t)B * N);
+    if (s) *s = v;
+    return ar.used;
 }
 
 // workspace: a [B, E] (o in forward; dn, then do in place, in backward), b [B, E] (dv), c [B, N] (df)
@@ -64,14 +56,14 @@ struct Work {
     float *a, *b, *c;
 };
 
-__host__ __device__ inline size_t work_layout(int64_t B, int E, int N, char* base, Work* w) {
-    const size_t be = align256((size_t)B * E * 4), bn = align256((size_t)B * N * 4);
-    if (w) {
-        w->a = reinterpret_cast<float*>(base);
-        w->b = reinterpret_cast<float*>(base + be);
-        w->c = reinterpret_cast<float*>(base + 2 * be);
-    }
-    return 2 * be + bn;
+__host__ __device__ inline size_t work_layout(int64_t B, int E, int N, void* base, Work* w) {
+    xmh::Arena ar(base);
+    Work v;
+    v.a = ar.take<float>((size_t)B * E);
+    v.b = ar.take<float>((size_t)B * E);
+    v.c = ar.take<float>((size_t)B * N);
+    if (w) *w = v;
+    return ar.used;
 }
 
 enum { EPI_PLAIN = 0, EPI_RELU_PAIR = 1, EPI_DROP_TANH = 2 };
@@ -234,11 +226,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_train(const float* __restrict__
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+using xmh::wave_sum;
 
 // LayerNorm over the rows of o [B, E] (fp32 in, statistics in double, biased variance): one wave per row
 __global__ __launch_bounds__(kThreads) void k_ln_train(const float* __restrict__ o, int B, int E, const float* __restrict__ gamma,
@@ -423,8 +411,8 @@ extern "C" int xmh_head_dcmht_train_forward(const xmh_dcmht_train* h, const floa
     if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, work_layout(B, E, N, nullptr, nullptr))) return rc;
     Saved s;
     Work w;
-    saved_layout(B, E, N, static_cast<char*>(saved), &s);
-    work_layout(B, E, N, static_cast<char*>(workspace), &w);
+    saved_layout(B, E, N, saved, &s);
+    work_layout(B, E, N, workspace, &w);
     hipStream_t st = xmh::as_stream(stream);
     MmOut o = {};
     o.C = s.v;
@@ -459,8 +447,8 @@ extern "C" int xmh_head_dcmht_backward(const xmh_dcmht_train* h, const float* x,
     if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, work_layout(B, E, N, nullptr, nullptr))) return rc;
     Saved s;
     Work w;
-    saved_layout(B, E, N, static_cast<char*>(const_cast<void*>(saved)), &s);
-    work_layout(B, E, N, static_cast<char*>(workspace), &w);
+    saved_layout(B, E, N, const_cast<void*>(saved), &s);
+    work_layout(B, E, N, workspace, &w);
     hipStream_t st = xmh::as_stream(stream);
     const int M = (int)B;
     // what has to exist for the gradients asked for: each stage is needed by everything upstream of it

@@ -17,6 +17,7 @@
 // forward, the row gradient and the proxy gradient see the same mask.
 // Bound: B = 100, K = 16..128, C = 80 (COCO, configs[4]) is a few tens of KB of L2-resident operands: launch-latency bound.
 #include "xmh_common.h"
+#include "xmh_device.h"
 
 namespace {
 
@@ -35,55 +36,19 @@ struct WsView {
     float* np;
 };
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-__host__ __device__ inline size_t ws_layout(int64_t B, int C, char* base, WsView* v) {
-    size_t off = 0;
-    const size_t o_part = off; off = align256(off + (size_t)B * 8 * sizeof(double));
-    const size_t o_cnt = off;  off = align256(off + (size_t)B * 2 * sizeof(int));
-    const size_t o_nx = off;   off = align256(off + (size_t)B * sizeof(float));
-    const size_t o_ny = off;   off = align256(off + (size_t)B * sizeof(float));
-    const size_t o_np = off;   off = align256(off + (size_t)C * sizeof(float));
-    if (v) {
-        v->part = reinterpret_cast<double*>(base + o_part);
-        v->cnt = reinterpret_cast<int*>(base + o_cnt);
-        v->nx = reinterpret_cast<float*>(base + o_nx);
-        v->ny = reinterpret_cast<float*>(base + o_ny);
-        v->np = reinterpret_cast<float*>(base + o_np);
-    }
-    return off;
+__host__ __device__ inline size_t ws_layout(int64_t B, int C, void* base, WsView* v) {
+    xmh::Arena ar(base);
+    WsView w;
+    w.part = ar.take<double>((size_t)B * 8);
+    w.cnt = ar.take<int>((size_t)B * 2);
+    w.nx = ar.take<float>((size_t)B);
+    w.ny = ar.take<float>((size_t)B);
+    w.np = ar.take<float>((size_t)C);
+    if (v) *v = w;
+    return ar.used;
 }
 
-// xor butterfly: every lane ends with the same bits (each step adds the same two values, in either order)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// block sum in a fixed order (wave butterflies, then the waves in index order); valid on every thread
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = sh[0];
-    for (int w = 1; w < kWaves; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
+using xmh::wave_sum;
 
 __device__ __forceinline__ float inv_norm(float n) { return 1.0f / fmaxf(n, kEps); }
 
@@ -214,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_finalize(int B, int C, float a
         s[7] += (double)ws.cnt[2 * r];
         s[8] += (double)ws.cnt[2 * r + 1];
     }
-    for (int t = 0; t < 9; ++t) s[t] = block_sum(s[t], sh);   // counts: exact in double
+    for (int t = 0; t < 9; ++t) s[t] = xmh::block_sum<kWaves>(s[t], sh);   // counts: exact in double
     if (threadIdx.x == 0) {
         const double pn = s[7], nn = (double)B * (double)C - s[7], z = s[8];
         const double pos = s[0] / pn, neg = s[1] / nn, pos_t = s[2] / pn, neg_t = s[3] / nn;   // 0 / 0 = NaN, as the reference
@@ -241,7 +206,7 @@ __device__ __forceinline__ void normalize_backward_store(const float* v, float n
         const int k = threadIdx.x + r * kThreads;
         if (k < K) vd = fmaf(v[k], du[r], vd);
     }
-    vd = block_sum(vd, sh);
+    vd = xmh::block_sum<kWaves>(vd, sh);
     const float s = nv >= kEps ? vd * iv : 0.0f;                 // u . du; a clamped row passes du / eps only
 #pragma unroll
     for (int r = 0; r < kSlots; ++r) {
@@ -267,8 +232,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
         pn += (double)ws.cnt[2 * r];
         z += (double)ws.cnt[2 * r + 1];
     }
-    pn = block_sum(pn, dsh);
-    z = block_sum(z, dsh);
+    pn = xmh::block_sum<kWaves>(pn, dsh);
+    z = xmh::block_sum<kWaves>(z, dsh);
     const double nn = (double)B * (double)C - pn;
     // d loss / d cos: -1 / P_num on a label, [cos > thr] / N_num off it; d loss / d sim: alpha / Z on a pair
     const float wpos = pn > 0.0 ? (float)(-1.0 / pn) : 0.0f, wneg = nn > 0.0 ? (float)(1.0 / nn) : 0.0f;
@@ -454,7 +419,7 @@ extern "C" int xmh_hyp_loss(const float* x, const float* y, const float* P, int6
     if (int rc = check_args("xmh_hyp_loss", x, y, P, B, K, C, lab, ws, ws_bytes)) return rc;
     if (!out8) return xmh::fail(XMH_EINVAL, "xmh_hyp_loss: null pointer");
     WsView v;
-    ws_layout(B, C, static_cast<char*>(ws), &v);
+    ws_layout(B, C, ws, &v);
     hipStream_t st = xmh::as_stream(stream);
     hipLaunchKernelGGL(k_hyp_rows<true>, dim3((unsigned)(B + C)), dim3(kThreads), (size_t)2 * K * 4, st, x, y, P, (int)B, K, C, lab,
                        (C + 31) / 32, threshold, alpha, v);
@@ -470,7 +435,7 @@ extern "C" int xmh_hyp_loss_grad(const float* x, const float* y, const float* P,
     if (int rc = check_args("xmh_hyp_loss_grad", x, y, P, B, K, C, lab, ws, ws_bytes)) return rc;
     if (!grad_x || !grad_y || !grad_P) return xmh::fail(XMH_EINVAL, "xmh_hyp_loss_grad: null pointer");
     WsView v;
-    ws_layout(B, C, static_cast<char*>(ws), &v);
+    ws_layout(B, C, ws, &v);
     hipStream_t st = xmh::as_stream(stream);
     hipLaunchKernelGGL(k_hyp_rows<false>, dim3((unsigned)(B + C)), dim3(kThreads), (size_t)2 * K * 4, st, x, y, P, (int)B, K, C, lab,
                        (C + 31) / 32, threshold, alpha, v);

@@ -19,6 +19,7 @@
 
 namespace {
 
+// not xmh_device.h's block_sum: thread 0 alone adds the waves (their count read from blockDim, starting from 0.0) and gets the sum
 __device__ __forceinline__ double block_sum(double v, double* sh) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

@@ -25,6 +25,7 @@
 // gradient form the likelihood dot products with the same routine, so both see the same clamp mask.  No call allocates or
 // synchronises with the host.
 #include "xmh_common.h"
+#include "xmh_device.h"
 
 namespace {
 
@@ -33,8 +34,6 @@ constexpr int kTile = 64, kKc = 16, kLd = kTile + 4;     // output tile, reducti
 constexpr int64_t kMaxN = int64_t(1) << 22;
 constexpr int kMaxB = 1024, kMaxK = 256, kMaxD = 2048;
 constexpr int kLikTarget = 1024;                          // blocks the likelihood grid aims for (sets the N chunk count P)
-
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the likelihood grid: kTile-column tiles of the 4B stacked code columns x P chunks of `rows` rows of N (a whole number of tiles).
 // Depends on the shape only, so the forward, the gradient and the workspace agree on it.
@@ -63,23 +62,18 @@ struct WsView {
     float* gpart;     // [P][4B][K] per-chunk likelihood gradient sums (gradient only)
 };
 
-__host__ __device__ inline size_t ws_layout(int64_t N, int B, int K, char* base, WsView* v) {
+__host__ __device__ inline size_t ws_layout(int64_t N, int B, int K, void* base, WsView* v) {
     const LikGrid g = lik_grid(N, B);
     const size_t lines = (size_t)2 * B + (size_t)2 * B * K;
-    size_t off = 0;
-    const size_t o_lik = off;    off = align256(off + (size_t)g.P * g.ctiles * 4 * sizeof(double));
-    const size_t o_ce = off;     off = align256(off + lines * sizeof(double));
-    const size_t o_lse = off;    off = align256(off + lines * sizeof(float));
-    const size_t o_logits = off; off = align256(off + ((size_t)B * B + (size_t)B * K * K) * sizeof(float));
-    const size_t o_gpart = off;  off = align256(off + (size_t)g.P * 4 * B * K * sizeof(float));
-    if (v) {
-        v->lik = reinterpret_cast<double*>(base + o_lik);
-        v->ce = reinterpret_cast<double*>(base + o_ce);
-        v->lse = reinterpret_cast<float*>(base + o_lse);
-        v->logits = reinterpret_cast<float*>(base + o_logits);
-        v->gpart = reinterpret_cast<float*>(base + o_gpart);
-    }
-    return off;
+    xmh::Arena ar(base);
+    WsView w;
+    w.lik = ar.take<double>((size_t)g.P * g.ctiles * 4);
+    w.ce = ar.take<double>(lines);
+    w.lse = ar.take<float>(lines);
+    w.logits = ar.take<float>((size_t)B * B + (size_t)B * K * K);
+    w.gpart = ar.take<float>((size_t)g.P * 4 * B * K);
+    if (v) *v = w;
+    return ar.used;
 }
 
 // the kernels' view of xmh_mith_loss_args (device pointers), the codes stacked in likelihood order (t_i, t_t, c_t, c_i)
@@ -96,34 +90,8 @@ struct Grads {
                       // tokens_hash_t, trans_tokens_i, trans_tokens_t (NULL = not needed)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// block sum in a fixed order (wave butterflies, then the waves in index order); valid on every thread
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = sh[0];
-    for (int w = 1; w < kWaves; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
+using xmh::wave_max;
+using xmh::wave_sum;
 
 // ---- operands of the tile products: element (m, k), 0 outside [0, M) x [0, Kr) -------------------------------------------------
 struct Strided {
@@ -283,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void k_mith_lik(Args a, WsView ws, LikGri
         const int blk = blockIdx.y * gridDim.x + blockIdx.x;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const double s = block_sum(part[q], red);
+            const double s = xmh::block_sum<kWaves>(part[q], red);
             if (threadIdx.x == 0) ws.lik[(int64_t)blk * 4 + q] = s;
         }
     } else {
@@ -436,9 +404,9 @@ __global__ __launch_bounds__(kThreads) void k_mith_finalize(Args a, WsView ws, L
         qd[3] += xt * xt;
     }
     for (int q = 0; q < 4; ++q) {
-        lik[q] = block_sum(lik[q], sh);
-        ce[q] = block_sum(ce[q], sh);
-        qd[q] = block_sum(qd[q], sh);
+        lik[q] = xmh::block_sum<kWaves>(lik[q], sh);
+        ce[q] = xmh::block_sum<kWaves>(ce[q], sh);
+        qd[q] = xmh::block_sum<kWaves>(qd[q], sh);
     }
     if (threadIdx.x == 0) {
         const double nb = (double)a.N * (double)B, bk = (double)BK;
@@ -598,7 +566,7 @@ extern "C" int xmh_mith_loss(const xmh_mith_loss_args* args, void* ws, size_t ws
     if (!out10) return xmh::fail(XMH_EINVAL, "xmh_mith_loss: null pointer (out10)");
     const Args a = device_args(args);
     WsView v;
-    ws_layout(a.N, a.B, a.K, static_cast<char*>(ws), &v);
+    ws_layout(a.N, a.B, a.K, ws, &v);
     const LikGrid g = lik_grid(a.N, a.B);
     hipStream_t st = xmh::as_stream(stream);
     launch_lik(false, a, v, g, st);
@@ -624,7 +592,7 @@ extern "C" int xmh_mith_loss_grad(const xmh_mith_loss_args* args, const float* u
     }
     if (!any) return XMH_OK;
     WsView v;
-    ws_layout(a.N, a.B, a.K, static_cast<char*>(ws), &v);
+    ws_layout(a.N, a.B, a.K, ws, &v);
     const LikGrid g = lik_grid(a.N, a.B);
     hipStream_t st = xmh::as_stream(stream);
     if (any_code) launch_lik(true, a, v, g, st);

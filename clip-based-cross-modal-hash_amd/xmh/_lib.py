@@ -210,6 +210,13 @@ def current_stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def workspace(nbytes: int, device):
+    """Scratch bytes for one call, from torch's stream-aware caching allocator: the runner drives several forwards of ONE model on
+    different streams at a time, a workspace owned by the module would be shared between them."""
+    import torch
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 def prof_enable(on=True) -> None:
     """True / 1: HIP events around the dominant kernels (prof_read); 2: roctx ranges around every phase of the path (a
     `rocprofv3 --marker-trace` timeline gets phase markers); 3: both; False / 0: off."""

@@ -94,10 +94,7 @@ def _cached_desc(module, build, params=None, slot="tower"):
     return hit[1], precision
 
 
-def _workspace(nbytes: int, device) -> torch.Tensor:
-    # per call, from torch's stream-aware caching allocator: the runner drives several forwards of ONE model on different
-    # streams at a time, a workspace owned by the module would be shared between them
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+_workspace = _lib.workspace                      # the name heads.py and mith.py know it by
 
 
 class _Block(nn.Module):

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import retrieval as R
-from .._lib import check, current_stream, lib, ptr
+from .._lib import check, current_stream, lib, ptr, workspace
 from ..common.register import registry
 from .base import BaseModel
 from .codetable import hyp_threshold
@@ -59,7 +59,7 @@ class _HyP(torch.autograd.Function):
     def _args(hyp, x, y, P, lab):
         B, K = x.shape
         C = P.shape[0]
-        ws = torch.empty(lib.xmh_hyp_loss_ws_bytes(B, K, C), dtype=torch.uint8, device=x.device)
+        ws = workspace(lib.xmh_hyp_loss_ws_bytes(B, K, C), x.device)
         return (ptr(x), ptr(y), ptr(P), B, K, C, ptr(lab), float(hyp.threshold), float(hyp.alpha)), ws
 
     @staticmethod

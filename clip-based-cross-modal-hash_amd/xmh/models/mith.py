@@ -174,7 +174,7 @@ class _MITHLoss(torch.autograd.Function):
         N = Y.shape[0]
         a = _lib.MithLossArgs(N, B, K, D, *(t.data_ptr() for t in xs), Y.data_ptr(), S.data_ptr(),
                               *(getattr(model, n) for n, _ in MITH.HYPER), _MITHLoss.TEMPERATURE)
-        ws = torch.empty(lib.xmh_mith_loss_ws_bytes(N, B, K, D), dtype=torch.uint8, device=Y.device)
+        ws = _clip._workspace(lib.xmh_mith_loss_ws_bytes(N, B, K, D), Y.device)
         return a, ws
 
     @staticmethod

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Golden vectors of MITH's training objective and of its gradients (loss.backward() with respect to the eight head outputs),
 produced by the UNMODIFIED reference (models/MITH/MITH.py) through oracle._ref_import:
-python tools/make_golden_mith_loss.py -> tests/golden/loss_mith.npz.  Needs the reference checkout; nothing at test time runs this.
+python oracle/make_golden_mith_loss.py [DIR] -> tests/golden/loss_mith.npz (or DIR/).  Needs the reference checkout; nothing at test time runs this.
 
-The model is the reference's own class with only its backbone replaced (load_backbone -> (D, Identity)).  Before the first step its
+The model is the reference's own class with only its backbone replaced (oracle/_ref_models.py: load_backbone -> (D, Identity)).  Before the first step its
 four buffer names are bound to ONE tensor: that is what the reference's device branch (MITH.py:169-173) leaves behind on every GPU run,
 and this machine has no GPU to take that branch.  Each step then runs the reference's object_function and loss.backward().
 
@@ -18,28 +18,12 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-from oracle import _ref_import  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import _ref_models  # noqa: E402
+from oracle.fixtures import out_path, q64  # noqa: E402
+from oracle.losses import MITH_CASES as CASES, MITH_INPUTS as INPUTS, MITH_WEIGHTS as WEIGHTS  # noqa: E402
 
-_ref_import.setup()
-from models.MITH.MITH import MITH  # noqa: E402  (the reference class)
-
-INPUTS = ["res_img_cls", "res_txt_cls", "img_cls_hash", "txt_cls_hash", "tokens_hash_i", "tokens_hash_t", "trans_tokens_i",
-          "trans_tokens_t"]
-WEIGHTS = ["hyper_tokens_intra", "hyper_distill", "hyper_info_nce", "hyper_cls_inter", "hyper_quan", "hyper_alpha", "hyper_lambda"]
 DEFAULT = dict(zip(WEIGHTS, (1.0, 1.0, 50.0, 10.0, 8.0, 0.01, 0.99)))    # configs/MITH/config.yaml
-CASES = ["consecutive", "clamp", "sign0", "float_sim", "weights", "odd"]
-
-
-def ref_model(N, K, D, weights):
-    stub = type("NoBackbone", (MITH,), {"load_backbone": lambda self, clipPath, return_patches=False: (D, torch.nn.Identity())})
-    return stub(cfg=None, outputDim=K, train_num=N, **weights)
-
-
-def q64(t):
-    return torch.round(t * 64.0) / 64.0
 
 
 def features(g, B, K, D, normalise):
@@ -124,7 +108,7 @@ def main():
     for ci, name in enumerate(CASES):
         g = torch.Generator().manual_seed(1814 + ci)
         N, B, K, D, w, buf0, steps = case_steps(name, g)
-        m = ref_model(N, K, D, w)
+        m = _ref_models.mith(N, K, D, w)
         buf = buf0.clone()
         m.img_buffer_cls = m.txt_buffer_cls = m.img_buffer_tokens = m.txt_buffer_tokens = buf     # the device branch's outcome
         out[name + "_meta"] = np.array([N, B, K, D, len(steps)] + [w[k] for k in WEIGHTS], dtype=np.float64)
@@ -144,7 +128,7 @@ def main():
             out[p + "buf"] = buf.numpy().copy()
             out[p + "terms"] = np.array([float(v) for v in leaves(d)], dtype=np.float64)
             print(name, s, "terms", out[p + "terms"])
-    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "loss_mith.npz"), **out)
+    np.savez_compressed(out_path("loss_mith.npz"), **out)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """GPU: train-mode forward and backward of the DCMHT / DSPH hash heads (xmh_head_grad.hip behind torch.autograd in
 xmh/models/heads.py) against the goldens of the reference's own HashLayer classes in .train() mode and against the float64
-restatement of test_head_grad_cpu on other shapes; relu-mask consistency, exact zeros in the q / k thirds, BatchNorm running
+restatement of oracle/heads_train.py on other shapes; relu-mask consistency, exact zeros in the q / k thirds, BatchNorm running
 statistics, the untouched eval path, frozen parameters, accumulation, bit-reproducibility, no host synchronisation, and a few SGD
 steps of the heads behind a frozen synthetic backbone.
 
@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_head_grad_cpu as T
+from oracle import heads_train as T
 
 pytestmark = pytest.mark.gpu
 
@@ -533,7 +533,7 @@ def test_dcmht_sgd_steps_on_the_heads_track_the_restatement():
 
 def test_dsph_sgd_steps_on_the_heads_track_the_restatement():
     """runners/DSPH/runner.py:118-125 with the backbone frozen: the two fc layers and the proxies stepped by a stock SGD"""
-    from test_hyp_loss_cpu import hyp_terms
+    from oracle.losses import hyp_terms
     from xmh.models.dsph import DSPH
     from xmh.utils.config import Config
     B, K, C = 12, 16, 10

@@ -1,12 +1,13 @@
 """GPU: DSPH's HyP loss (xmh_hyp.hip behind HyPProxies.forward / DSPH.object_function) against the goldens the reference's own
 HyP produced (loss and loss.backward() into the codes and the proxies), and against the float64 restatement of
-test_hyp_loss_cpu on other shapes, thresholds and label dtypes; NaN cases, accumulation, bit-reproducibility, no host
+oracle/losses.py on other shapes, thresholds and label dtypes; NaN cases, accumulation, bit-reproducibility, no host
 synchronisation, and a few SGD steps of the proxies and codes."""
 import numpy as np
 import pytest
 import torch
 
-from test_hyp_loss_cpu import CASES, TERMS, grads_close, hyp_oracle, hyp_terms, load
+from oracle.fixtures import grads_close_rows as grads_close
+from oracle.losses import HYP_CASES as CASES, HYP_TERMS as TERMS, hyp_oracle, hyp_terms, load_hyp as load
 
 pytestmark = pytest.mark.gpu
 

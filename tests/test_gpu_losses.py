@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_oracle_losses import CASES, ORDER, grads_close, load, load_grads
+from oracle.fixtures import grads_close
+from oracle.losses import DCMHT_CASES as CASES, DCMHT_TERMS as ORDER, load_dcmht as load, load_dcmht_grads as load_grads
 
 pytestmark = pytest.mark.gpu
 

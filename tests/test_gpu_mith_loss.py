@@ -1,6 +1,6 @@
 """GPU: MITH's training objective (xmh_mith_loss.hip behind MITH.object_function) against the goldens the reference's own MITH
 produced (buffer, loss_dict and loss.backward() into the eight inputs, step after step on one instance), and against the float64
-restatement of test_mith_loss_cpu at the production shapes; accumulation, bit-reproducibility, no host synchronisation, autograd's
+restatement of oracle/losses.py at the production shapes; accumulation, bit-reproducibility, no host synchronisation, autograd's
 version check and double backward, the trainer, and a few SGD steps."""
 import ctypes
 
@@ -9,7 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_mith_loss_cpu import CASES, INPUTS, WEIGHTS, grads_close, load, mith_oracle, mith_terms
+from oracle.fixtures import grads_close
+from oracle.losses import MITH_CASES as CASES, MITH_INPUTS as INPUTS, MITH_WEIGHTS as WEIGHTS, load_mith as load, mith_oracle, mith_terms
 
 pytestmark = pytest.mark.gpu
 

@@ -1,74 +1,17 @@
 """CPU: DSPH's HyP loss -- a float64 restatement of the reference expression (models/DSPH/loss/HyP.py:18-70) against goldens written by
-the reference itself (tools/make_golden_hyp.py), the codetable reader, the threshold's resolution order, and the argument checks of
+the reference itself (oracle/make_golden_hyp.py), the codetable reader, the threshold's resolution order, and the argument checks of
 xmh_hyp_loss / xmh_hyp_loss_grad, which run before any HIP call."""
 import ctypes
-import os
 import zipfile
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import GOLDEN
+from oracle.fixtures import aligned_host as _host, grads_close_rows as grads_close
+from oracle.losses import HYP_CASES as CASES, hyp_oracle, load_hyp as load
 
-CASES = ["b100_k16_c80", "b64_k128_c80", "b64_k16_c80_alpha0", "b48_k16_c80_single", "b48_k16_c80_shared", "b40_k16_c80_zero_row",
-         "b24_k16_c24_nolabels"]
-TERMS = ["loss", "pos", "neg", "pos_t", "neg_t", "reg", "reg_t", "reg_xt"]          # the order of xmh_hyp_loss's out8
 SYNTH_CLIP = "synthetic:1814:vision_layers=1,transformer_layers=1"
-
-
-def hyp_terms(x, y, P, labels, threshold, alpha):
-    """The reference expression restated in the caller's dtype (float64 for an oracle): a dict of TERMS, differentiable.  `labels`
-    [B, C] holds 0/1; nonzero counts as 1."""
-    L = labels != 0
-    zero = torch.zeros((), dtype=x.dtype)
-    nP = F.normalize(P, p=2, dim=1)
-    cos, cos_t = F.normalize(x, p=2, dim=1) @ nP.T, F.normalize(y, p=2, dim=1) @ nP.T
-    p_num, n_num = L.sum().to(x.dtype), (~L).sum().to(x.dtype)
-    t = {"pos": torch.where(L, 1 - cos, zero).sum() / p_num, "neg": torch.where(~L, F.relu(cos - threshold), zero).sum() / n_num,
-         "pos_t": torch.where(L, 1 - cos_t, zero).sum() / p_num, "neg_t": torch.where(~L, F.relu(cos_t - threshold), zero).sum() / n_num}
-    t["reg"] = t["reg_t"] = t["reg_xt"] = zero
-    if alpha > 0:
-        M = L.sum(1) > 1
-        Lm = L[M].to(x.dtype)
-        pairs = (Lm @ Lm.T) == 0
-        Z = int(pairs.sum())
-        if Z > 0:
-            xm, ym = F.normalize(x[M], p=2, dim=1), F.normalize(y[M], p=2, dim=1)
-            for key, sim in (("reg", xm @ xm.T), ("reg_t", ym @ ym.T), ("reg_xt", xm @ ym.T)):
-                t[key] = torch.where(pairs, alpha * F.relu(sim - threshold), zero).sum() / Z
-    t["loss"] = t["pos"] + t["neg"] + t["pos_t"] + t["neg_t"] + t["reg"] + t["reg_t"] + t["reg_xt"]
-    return t
-
-
-def hyp_oracle(x, y, P, labels, threshold, alpha):
-    """float64 terms (numpy [8], TERMS order) and the gradients of the loss with respect to x, y, P (float64 numpy)"""
-    x, y, P = (torch.as_tensor(v).double().requires_grad_(True) for v in (x, y, P))
-    t = hyp_terms(x, y, P, torch.as_tensor(labels), threshold, alpha)
-    t["loss"].backward()
-    return np.array([float(t[k].detach()) for k in TERMS]), x.grad.numpy(), y.grad.numpy(), P.grad.numpy()
-
-
-def load(name):
-    """x, y, proxies, labels (None: the reference's identity default), threshold, alpha, loss, (gx, gy, gproxies)"""
-    g = np.load(os.path.join(GOLDEN, "loss_dsph.npz"))
-    K, C, alpha, threshold = g[name + "_meta"]
-    labels = g[name + "_labels"] if name + "_labels" in g.files else None
-    return (g[name + "_x"], g[name + "_y"], g[name + "_proxies"], labels, float(threshold), float(alpha), float(g[name + "_loss"]),
-            (g[name + "_gx"], g[name + "_gy"], g[name + "_gproxies"]))
-
-
-def grads_close(got, ref):
-    """relative to the largest entry of the matrix (test_oracle_losses.grads_close); a row clamped by F.normalize's eps (its
-    gradient ~1e12 larger) is compared on its own, so that it does not loosen the comparison of the others"""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    big = np.abs(ref).max(axis=1) > 1e6 * max(np.median(np.abs(ref).max(axis=1)), 1e-30)
-    ok = True
-    for rows in (big, ~big):
-        if rows.any():
-            ok &= float(np.abs(got[rows] - ref[rows]).max()) <= 2e-5 * float(np.abs(ref[rows]).max()) + 1e-9
-    return ok
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -172,12 +115,6 @@ def test_hyp_loss_rejects_cpu_tensors():
 
 
 # ---- C ABI argument checks (no GPU involved: each call returns before its first HIP call) ------------------------------------
-def _host(n):
-    """a 256-byte aligned host address with n bytes behind it (never dereferenced by a call that fails its checks)"""
-    buf = np.zeros(n + 256, dtype=np.uint8)
-    return buf, ctypes.c_void_p((buf.ctypes.data + 255) & ~255)
-
-
 def test_argument_errors_are_reported_without_a_gpu():
     from xmh._lib import lib
     assert lib.xmh_hyp_loss_ws_bytes(100, 16, 80) > 0 and lib.xmh_hyp_loss_ws_bytes(4096, 4096, 1024) > 0

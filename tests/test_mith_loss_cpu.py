@@ -1,5 +1,5 @@
 """CPU: MITH's training objective -- a float64 restatement of the reference expression (models/MITH/MITH.py:116-232) against goldens
-written by the reference itself (tools/make_golden_mith_loss.py), the model-side contract (one buffer under four names, weights,
+written by the reference itself (oracle/make_golden_mith_loss.py), the model-side contract (one buffer under four names, weights,
 state_dict, the errors raised before any launch) and the argument checks of xmh_mith_loss / xmh_mith_loss_grad, which run before
 any HIP call."""
 import ctypes
@@ -8,72 +8,12 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import GOLDEN
+from oracle.fixtures import aligned_host as _host, grads_close
+from oracle.losses import MITH_CASES as CASES, MITH_INPUTS as INPUTS, MITH_WEIGHTS as WEIGHTS, load_mith as load, mith_oracle
 
-CASES = ["consecutive", "clamp", "sign0", "float_sim", "weights", "odd"]
-INPUTS = ["res_img_cls", "res_txt_cls", "img_cls_hash", "txt_cls_hash", "tokens_hash_i", "tokens_hash_t", "trans_tokens_i",
-          "trans_tokens_t"]
-WEIGHTS = ["hyper_tokens_intra", "hyper_distill", "hyper_info_nce", "hyper_cls_inter", "hyper_quan", "hyper_alpha", "hyper_lambda"]
-TERMS = ["loss", "intra_i", "intra_t", "i2t", "t2i", "quan_i", "quan_t", "nce_cls", "nce_tokens", "distillation"]   # out10
 SYNTH_CLIP = "synthetic:1814:vision_layers=1,transformer_layers=1"
-
-
-def mith_terms(xs, Y, S, w, tau=0.07):
-    """The reference expression restated in the inputs' dtype (float64 for an oracle): the TERMS as a list, differentiable in xs.
-    Y is the one buffer after the step's row write.  sign() is taken on fp32 codes, op for op, as the reference takes it."""
-    rc_i, rc_t, c_i, c_t, t_i, t_t, T_i, T_t = xs
-    lam = w["hyper_lambda"]
-
-    def bayes(b):
-        s = 0.5 * (Y @ b.T).clamp(min=-64, max=64)
-        return -torch.mean(S * s - torch.log(1 + torch.exp(s)))
-
-    def nce(s):                                   # s [n, m, m] logits; rows and columns against the diagonal
-        n, m = s.shape[0], s.shape[1]
-        tgt = torch.arange(m).repeat(n)
-        return 0.5 * (F.cross_entropy(s.reshape(n * m, m), tgt) + F.cross_entropy(s.transpose(1, 2).reshape(n * m, m), tgt))
-
-    f = [t.detach().float() for t in (c_i, t_i, c_t, t_t)]
-    Bs = torch.sign((f[0] * lam + f[1] * (1 - lam)) + (f[2] * lam + f[3] * (1 - lam))).to(c_i.dtype)
-    B, K = c_i.shape
-    t = [None, bayes(t_i), bayes(t_t), bayes(c_t), bayes(c_i),
-         ((c_i * 0.5 + t_i * 0.5 - Bs) ** 2).sum() / B / K, ((c_t * 0.5 + t_t * 0.5 - Bs) ** 2).sum() / B / K,
-         nce((rc_i @ rc_t.T / tau)[None]), nce(torch.bmm(T_i.permute(1, 0, 2), T_t.permute(1, 2, 0)) / tau)]
-    t.append(w["hyper_distill"] * (((c_i.detach() - t_i) ** 2).sum() + ((c_t.detach() - t_t) ** 2).sum()
-                                   + 0.1 * (((c_i - t_i.detach()) ** 2).sum() + ((c_t - t_t.detach()) ** 2).sum())) / B)
-    t[0] = (w["hyper_tokens_intra"] * (t[1] + t[2]) + w["hyper_cls_inter"] * (t[3] + t[4]) + w["hyper_quan"] * (t[5] + t[6])
-            + w["hyper_info_nce"] * (t[7] + w["hyper_alpha"] * t[8]) + t[9])
-    return t
-
-
-def mith_oracle(xs, Y, S, w):
-    """float64 terms (numpy [10], TERMS order) and the eight gradients of the loss (float64 numpy)"""
-    xs = [torch.as_tensor(np.asarray(x)).double().requires_grad_(True) for x in xs]
-    t = mith_terms(xs, torch.as_tensor(np.asarray(Y)).double(), torch.as_tensor(np.asarray(S)).double(), w)
-    t[0].backward()
-    return np.array([float(v.detach()) for v in t]), [x.grad.numpy() for x in xs]
-
-
-def load(name):
-    """(N, B, K, D, weights dict, buf0, [step dicts with the inputs list, indexs, label_sim, buf, terms, grads list])"""
-    g = np.load(os.path.join(GOLDEN, "loss_mith.npz"))
-    meta = g[name + "_meta"]
-    N, B, K, D, steps = (int(v) for v in meta[:5])
-    w = dict(zip(WEIGHTS, (float(v) for v in meta[5:])))
-    out = []
-    for s in range(steps):
-        p = "%s_s%d_" % (name, s)
-        out.append({"inputs": [g[p + k] for k in INPUTS], "indexs": g[p + "indexs"], "label_sim": g[p + "label_sim"], "buf": g[p + "buf"],
-                    "terms": g[p + "terms"], "grads": [g[p + "g_" + k] for k in INPUTS]})
-    return N, B, K, D, w, g[name + "_buf0"], out
-
-
-def grads_close(got, ref):
-    """relative to the largest entry of the matrix (test_oracle_losses.grads_close)"""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float(np.abs(got - ref).max()) <= 2e-5 * float(np.abs(ref).max()) + 1e-9
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -168,12 +108,6 @@ def test_errors_before_any_launch():
 
 
 # ---- C ABI argument checks (no GPU involved: each call returns before its first HIP call) ------------------------------------
-def _host(n):
-    """a 256-byte aligned host address with n bytes behind it (never dereferenced by a call that fails its checks)"""
-    buf = np.zeros(n + 256, dtype=np.uint8)
-    return buf, ctypes.c_void_p((buf.ctypes.data + 255) & ~255)
-
-
 def test_argument_errors_are_reported_without_a_gpu():
     from xmh import _lib
     lib = _lib.lib
