@@ -1,14 +1,14 @@
-// Pass 1 of the fused ranking scan for 128- and 256-bit binary codes with the MFMA operands built IN REGISTERS from the packed
-// bits (round 3; the boundary, the tables and pass 2 are those of xmh_scan.hip -- this file only replaces k_scan_hist_m there).
+// Pass 1 of the fused ranking scan for 129..256-bit binary codes and for ternary codes with the MFMA operands built IN REGISTERS from the
+// packed bits (round 3; the boundary, the tables and pass 2 are those of xmh_scan.hip, whose scan_route sends these shapes here).
 //
-// k_scan_hist_m stages a pre-expanded int8 image of the gallery (8 bytes per code bit and label bit, built by k_scan_expand, 1 KB
-// pieces through a two-deep LDS ring by LDS-DMA, two barriers per 64-item batch) and at 129 / 257 bucket rows per wave its LDS
-// footprint leaves one block per CU.  Here nothing is staged: as in k_topk_filter_mfma (xmh_topk.hip), `word & (0x01010101 << p)`
+// The kernel it replaced (round 2's k_scan_hist_m, removed in round 5) staged a pre-expanded int8 image of the gallery (8 bytes per code
+// bit and label bit, 1 KB pieces through a two-deep LDS ring by LDS-DMA, two barriers per 64-item batch) and at 129 / 257 bucket rows per
+// wave its LDS footprint left one block per CU.  Here nothing is staged: as in k_topk_filter_mfma (xmh_topk.hip), `word & (0x01010101 << p)`
 // leaves bits p, p + 8, p + 16, p + 24 of a packed word each alone in its byte, worth 2^p there (p = 7 through
 // `(word >> 1) & 0x40404040`), 9 VALU operations for 32 bits; the query side (B operand, built once per wave, kept in registers)
 // carries the matching weight s_i * 64 / 2^p with s_i = 1 - 2 q_i, so every product is 64 s_i x_i and an accumulator started at
 // (LDS address of this lane's bucket-0 counter) + 64 * popcount(q) ends as the ADDRESS of counter [distance][query] -- counter rows
-// are 64 bytes (16 queries x u32), exactly the layout of k_scan_hist_m.  Lane (row = l & 15, quarter = l >> 4) loads the quarter
+// are 64 bytes (16 queries x u32), exactly the layout of k_scan_hist_r2 (xmh_scan_mfma.h).  Lane (row = l & 15, quarter = l >> 4) loads the quarter
 // `quarter` of the code words of its item straight from the packed gallery (one or two words), and the label word `quarter` (labels:
 // up to 128 classes = 4 words = two label tiles; their B bytes are 64 / 2^p where the query has the label, so the label chain ends
 // as 0x10000 + 64 * (common labels) and min(., 0x10001) is the counter increment (all << 16 | relevant)).  No operand image, no
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64 * NW * NSH / NQT) void k_scan_hist_b(xmh::ScanBi
     const int64_t lo = (int64_t)chunk_id * a.chunk;
     const int64_t hi = (lo + a.chunk < a.R) ? lo + a.chunk : a.R;
     const int nbat = (int)((hi - lo + 63) >> 6);
-    // A rows: row r of group g is item 16 g + 4 (r & 3) + (r >> 2) (k_scan_hist_m's image order: C register j of lane (slot, query)
+    // A rows: row r of group g is item 16 g + 4 (r & 3) + (r >> 2) (the order of k_scan_hist_r2's operands: C register j of lane (slot, query)
     // is item 16 g + 4 j + slot, which is what the pair-cache layout below and the cached pass 2 count on)
     const int rowitem = 4 * (ql & 3) + (ql >> 2);
     uint32_t* crow[NQT];                                             // this lane's first 12-bit record (xmh_common.h) of each tile; the other one 32 records on
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(64 * NW * NSH / NQT) void k_scan_hist_b(xmh::ScanBi
                         __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t*)(uintptr_t)(uint32_t)acc[n][u][j], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         if (CACHE) e[j] = (inc & 1u) | ((uint32_t)(acc[n][u][j] - lanebase[n]) >> 5);    // entry: distance << 1 | relevant (16 bits)
                     }
-                    if (CACHE) {                                     // steps 2g, 2g+1 of the two 8-slot lanes this lane feeds (k_scan_hist_m): entries 2g, 2g+1
+                    if (CACHE) {                                     // steps 2g, 2g+1 of the two 8-slot lanes this lane feeds (the cached k_scan_ap_s): entries 2g, 2g+1
                         auto put = [&](uint32_t (&d)[3], uint32_t x, uint32_t y) {      // of their records, appended 12 bits each (g is a constant after unrolling)
                             if (g == 0) d[0] = x | (y << 12);
                             else if (g == 1) { d[0] |= x << 24; d[1] = (x >> 8) | (y << 4); }

@@ -1,7 +1,7 @@
 // The MFMA-evaluated scan kernels of xmh_scan.hip and the few definitions they share with the VALU kernels (ScanArgs, the block -> (chunk,
 // query tile) maps, the float-bit constants): k_scan_touch, k_scan_hist_r2, k_scan_hist_r2w, k_scan_ap_c, k_scan_ap_r2.  A header so that
 // tools/proto_scan_ablate.hip can compile exactly this code, with its ablation macros, in seconds (xmh_scan.hip instantiates several
-// hundred VALU kernels: two minutes); included by xmh_scan.hip inside its anonymous namespace scope -- nothing else includes it.
+// hundred VALU kernels: two minutes); in the library only xmh_scan.hip includes it (and xmh_scan_kernels.h, the VALU kernels, behind it).
 #pragma once
 #include "xmh_common.h"
 #include <type_traits>
@@ -37,24 +37,26 @@ __device__ __forceinline__ bool map_block(const ScanArgs& a, int& chunk_id, int&
 }
 
 // ===================================================================================================
-// MFMA-evaluated scan (binary codes of 33..128 bits in pass 1, at most 64 in pass 2; at most 128 classes).
+// MFMA-evaluated scan (binary codes of at most 128 bits in pass 1, at most 64 in pass 2; at most 128 classes).
 //
-// Hamming distance and label overlap of 16 gallery items x 16 queries are two i8 dot-product tiles -- literally what the
+// Hamming distance and label overlap of 16 gallery items x 16 queries are i8 dot-product tiles -- literally what the
 // reference computes, B1 @ B2^T and query_L @ retrieval_L^T (common/calc_utils.py:51-56, :72) -- so they go to
 // v_mfma_i32_16x16x64_i8 instead of 8 VALU instructions per pair:
-//   * code tile: item bytes +-1, query bytes -+SCALE (SCALE = bytes of one bucket row of the LDS counters); started from the lane's
-//     counter base, the accumulator IS the LDS byte address of counter [distance][query]:  base + SCALE*K/2 - (SCALE/2)*dot;
-//   * label tile: item bytes 127, query bytes 64; pass 1 starts it at 1 so that min(acc, 1 + 8128) is the add operand
-//     1 + relevant * 8128 (counters hold all + relevant * 8128; a chunk has at most 8064 items), pass 2 takes min(acc, 1).
-// Per pair the VALU does ONE instruction in pass 1 (v_min) and the credit arithmetic in pass 2.
-// Geometry = the slotted scheme with S = 4: lane = slot * 16 + query, and MFMA row 4*slot + j of a 16-item group holds item
-// 4*j + slot, so accumulator register j of a lane is its step j and same-query lanes of one LDS instruction are consecutive
-// items in lane order -- exactly what pass 2's returning adds need (lane_order_ok).
-// Operand images (built per call by two small kernels, in the workspace): gallery [64-item batch][16-item group][tile m][lane][16 B],
-// i.e. every MFMA A operand is one contiguous KB = one global_load_lds piece and one conflict-free ds_read_b128 per lane; the
-// NW waves of a block (NW * 16 queries) share each staged batch (2-deep ring, LDS-DMA issued one batch ahead).
-// The LDS atomics are inline asm: hipcc would drain the LDS-DMA (vmcnt(0)) before any LDS atomic it cannot prove disjoint from
-// the ring.  Returning adds are waited for with counted lgkmcnt statements naming their destinations (LDS returns in order).
+//   * address chain: item bytes 0 / 1 (2 in the odd registers of a tile), query bytes +-SCALE (SCALE = bytes of one bucket row of the LDS
+//     counters, halved against the item bytes worth 2); started from the lane's counter base + SCALE * popcount(query), the accumulator
+//     IS the LDS byte address of counter [distance][query], since distance = popcount(q) + sum x_i (1 - 2 q_i);
+//   * 2 * distance chain (pass 1 with a pair cache): the same item bytes against query bytes +-2; its low byte is the distance half of the
+//     cache entry (distance << 1 | relevant);
+//   * label chain: item and query label bits as bytes 0 / 1.  Pass 1 starts it at 0x10000, so that min(acc, 0x10001) is the add operand of
+//     (all << 16 | relevant) counters and its low byte the relevance bit (a chunk has at most kMaxChunk items: the 16-bit halves hold).
+//     Pass 2 (k_scan_ap_r2) has query label bytes 0 / -1 and takes max(acc, -1) as the mask 0 / ~0.
+// Per pair the VALU does two instructions in pass 1 (v_min, the SDWA OR of the cache byte), the credit arithmetic in pass 2.  Geometry = the
+// slotted scheme with S = 4: lane = slot * 16 + query, and MFMA row 4*slot + j of a 16-item group holds item 4*j + slot, so accumulator register j
+// of a lane is its step j and same-query lanes of one LDS instruction are consecutive items in lane order -- what pass 2's returning adds need.
+// Operands are built in registers from the packed words, per wave: lane (row, slot) loads the word of its item that holds its 16 bits, one
+// batch ahead, and spreads it with a few VALU operations per tile.  No operand image, no LDS-DMA, no ring, no barrier: waves are independent
+// and LDS holds the counters only.  The LDS atomics sit inside the asm statements of the MFMAs they consume (hazard list: scan_hist_r2_body);
+// returning adds are waited for with counted lgkmcnt statements naming their destinations (LDS returns in order).
 // ===================================================================================================
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -94,6 +96,22 @@ __device__ __forceinline__ bool mfma_map_block(const MfmaArgs& a, int& chunk_id,
 // Counter rows are 64 bytes (16 queries x u32); chunks hold up to 32768 items (16-bit halves).  Round 3's form of the same statements
 // (k_scan_hist_m2: operand images through a 3-deep LDS ring) and round 2's k_scan_hist_m were removed in round 5 (DESIGN 3.1 keeps their
 // measurements).
+//
+// THE HAZARD LIST of the hand-written MFMA statements (this body, scan_hist_r2w_body, k_scan_ap_r2).  One asm statement = the MFMAs of one
+// (16-item group, 16-query group) with the consumer instructions of the PREVIOUS group between them.  hipcc sees none of the following,
+// and each item was a wrong result on hardware before it was a rule:
+//   (i)   an MFMA result needs 8 wait states before a VALU / DS read: consumers read the PREVIOUS statement's results, and where no
+//         consumers of an earlier group sit in between a statement closes with s_nop 7 (XMH_R2_EVAL_CLOSE / XMH_R2_TAIL);
+//   (ii)  SDWA byte inserts into one register have a dst_sel forwarding hazard (one wait state): an add or an MFMA sits between them
+//         (k_scan_hist_r2w: even and odd bytes go to two registers, OR-ed at the end);
+//   (iii) a VALU write directly in front of an MFMA was read stale as srcC (hipcc had re-materialised a constant accumulator quad with
+//         v_mov_b64 there; it spaces that for its own MFMAs only): every statement opens with s_nop 3 (XMH_R2_OPEN), and the constant
+//         quads are made opaque to hipcc (asm volatile("" : "+v"(quad))) so that they stay in VGPRs and are never re-materialised;
+//   (iv)  a VALU write landing on the A / B registers of an MFMA issued two or three instructions earlier corrupted its operand: all
+//         results are early-clobber outputs of the statement that also names the A tiles as inputs;
+//   (v)   hipcc pads every asm result with s_nop before an asm reader and does not count asm statements as wait states: hence whole
+//         stages per statement.  MFMA -> MFMA srcC dependencies are interlocked in hardware.
+// tools/isa_hazards.py (tests/test_isa_hazards.py) checks the emitted ISA of every build for the wait states of (i) and (iii).
 // ---------------------------------------------------------------------------------------------------
 template <int NML, int NW, int NQ, bool CACHE>
 __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* __restrict__ chunk_hist, uint4* __restrict__ pair_cache) {
@@ -242,14 +260,8 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
         // One asm statement = the MFMAs of (group g, query group h) with the consumer instructions of the PREVIOUS pair between them:
         // an MFMA occupies the matrix pipe for 16 cycles, the three VALU / DS instructions behind it issue meanwhile, so a wave
         // keeps the pipe busy by itself (four MFMAs then twelve consumers left it idle half the time: 1830 cycles per batch measured
-        // against 512 of MFMA work per wave).  Inside a statement the hazards are handled by hand (hipcc does not see them):
-        //   * MFMA result -> VALU / DS read needs 8 wait states: the consumers read the PREVIOUS statement's results;
-        //   * the SDWA byte inserts into w have a dst_sel forwarding hazard (one wait state): an add or an MFMA sits between them;
-        //   * a VALU write directly in front of an MFMA was read stale as srcC (seen on hardware with a v_mov_b64 hipcc had placed
-        //     there): every statement opens with s_nop 3, and the constant accumulator quads are opaque to hipcc (no re-materialising);
-        //   * a VALU write landing on the A / B registers of an MFMA issued two or three instructions earlier corrupted its operand:
-        //     all results are early-clobber outputs of the statement that also names the A tiles as inputs;
-        //   * MFMA -> MFMA srcC dependencies are interlocked in hardware.
+        // against 512 of MFMA work per wave).  Inside a statement the hazards are handled by hand (hipcc does not see them): hazards
+        // (i)-(v) of the list above this function.
         // The consumers: inc = min(label overlap chain, 0x10001) in place; cache byte j = byte0(2 * distance) | byte0(inc); the add.
 // ablation switches of tools/proto_scan_ablate.hip (-DXMH_ABL_NOADD: the LDS adds become s_nop; -DXMH_ABL_NOMFMA: the MFMAs do; results are
 // wrong then, only the time means something): never set in the library build
@@ -381,7 +393,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
                              : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]));
             }
         };
-        auto consume = [&](uint32_t& w, const v4i (&live)[NMI]) {        // the last pair of a batch (live: see the hazard list above)
+        auto consume = [&](uint32_t& w, const v4i (&live)[NMI]) {        // the last pair of a batch (live: hazard (iv) of the list above this function)
             uint32_t i0, i1, i2, i3;
             if (CACHE) {
                 asm volatile(
@@ -500,9 +512,9 @@ __global__ __launch_bounds__(256) void k_scan_touch(const uint32_t* __restrict__
     asm volatile("" ::"v"(acc));
 }
 
-// k_scan_hist_r2 (round 4): k_scan_hist_m2's statements fed from registers.  The skeleton around the MFMA statements of k_scan_hist_m2 --
-// LDS-DMA issue, waiting for pieces, the barrier, the A-tile reads: a third of a wave's cycles (tools/stamp_m2.hip) -- and the 36 KB ring
-// that holds a block to two per CU exist only to bring 16 bytes per lane and tile that are a function of ONE packed word: here each lane
+// k_scan_hist_r2 (round 4): the MFMA statements fed from registers.  Round 3's kernel (k_scan_hist_m2, removed in round 5) staged operand
+// images through an LDS ring -- LDS-DMA issue, waiting for pieces, a barrier, A-tile reads: a third of a wave's cycles, and 36 KB that held a
+// block to two per CU -- only to bring 16 bytes per lane and tile that are a function of ONE packed word: here each lane
 // loads that word (4 bytes per tile; a wave's 16 items x 24 bytes per group, L2-resident) one batch ahead and spreads it with 8 VALU
 // operations per tile.  Waves are independent (no barrier, no shared staging); LDS holds the counters only.
 #ifndef XMH_R2_ATTR
@@ -517,11 +529,11 @@ __global__ __launch_bounds__(64 * NW) XMH_R2_ATTR void k_scan_hist_r2(MfmaArgs a
 // k_scan_hist_r2w (round 4): k_scan_hist_r2 for codes of 65..128 bits -- TWO code tiles per chain (six MFMAs per (16 items x 16 queries):
 // label, label, address, address, 2 * distance, 2 * distance), 129 bucket rows, 2 query groups per wave (66 KB of counters per block of four
 // waves, two blocks per CU), one-byte pair-cache entries in the layout of the shorter codes.  Same operand construction, same pipeline of
-// statements one (item group, query group) behind their MFMAs, same hazards (see k_scan_hist_m2).  Two differences in form: the operands
+// statements one (item group, query group) behind their MFMAs, same hazards (the list above scan_hist_r2_body).  Two differences in form: the operands
 // are named (a statement has 28 of the 30 an asm may take), and the cache word is assembled by a second, small statement -- byte j of the
 // word = byte0(2 * distance) | byte0(increment), the even bytes into one register and the odd ones into another so that no two SDWA
 // inserts into one register follow each other (the dst_sel hazard), OR-ed at the end.  A distance of 128 makes 2 * distance = 256, whose
-// byte wraps to 0: the same statement keeps the largest 2 * distance seen, and the kernel raises *ovf as k_scan_hist_m<.., BYTE> does.
+// byte wraps to 0: the same statement keeps the largest 2 * distance seen, and the kernel raises *ovf (kGateWrapped: pass 2 then evaluates the pairs from the codes).
 // ---------------------------------------------------------------------------------------------------
 #define XMH_W_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 %[" D "], %[" A "], %[" B "], %[" C "]\n\t"
 #define XMH_W_MIN(I, L) "v_min_u32 %[" I "], 0x10001, %[" L "]\n\t"
@@ -854,7 +866,7 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
     int chunk_id, qtile;
     if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts QW-query tiles here
     if (items_total && (int64_t)*items_total > kFloatBitsMaxItems) return;      // sharded call: the integer-counter kernel takes it
-    if (skip_if && *skip_if != 0u) return;                           // a distance wrapped in the one-byte cache of 65..128-bit codes: see k_scan_hist_m
+    if (skip_if && *skip_if != 0u) return;                           // a distance wrapped in the one-byte cache of 65..128-bit codes: see k_scan_hist_r2w
     // two-byte entries (129..256 bits, round 6): the packed 32-bit k_scan_ap_s is launched beside this kernel and takes the call when the
     // shard's ranks and relevant counts fit its counters (the same test, on the same device word, as in k_scan_ap_s)
     if (nrel_max && rank_bits > 0 && (uint64_t)(*nrel_max) + 2 < (1ull << (32 - rank_bits))) return;
@@ -1119,7 +1131,7 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
 // the (weighted) number of common labels and v_max_i32(acc, -1) is the mask 0 / ~0 -- which is both the high half of the 64-bit
 // increment {1, -relevant} of k_scan_ap_c's float-bit counters and the AND mask of its credit.  One statement per (16 items x 16
 // queries) holds that pair's MFMAs with the consumers of the PREVIOUS pair between them (four v_max, four ds_add_rtn_u64), as in
-// k_scan_hist_m2 (same hazards, same spacing: see there); the returns are credited two statements later behind a counted lgkmcnt
+// k_scan_hist_r2 (same hazards, same spacing: the list above scan_hist_r2_body); the returns are credited two statements later behind a counted lgkmcnt
 // (k_scan_ap_c's arithmetic in k_scan_ap_c's order per lane: lane (slot, query) still owns the items = slot mod 4, ascending, so the
 // per-chunk sums are bit-identical to the cached path's).  Nothing crosses a batch: an iteration ends drained (tools/isa_hazards.py R5).
 //   * the increment pairs {1, mask} live in PINNED registers (v[112:127], two sets used in turn): the statement writes the high halves by
@@ -1223,7 +1235,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
         }
         const int c0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) u64*)(cnt + h * ncell) + ql * 8 + (valid ? 128 * pcq : 0);
         cq[h] = v4i{c0, c0, c0, c0};
-        asm volatile("" : "+v"(cq[h]));                                // opaque: kept in VGPRs (see k_scan_hist_m2, hazard iii)
+        asm volatile("" : "+v"(cq[h]));                                // opaque: kept in VGPRs (hazard (iii), scan_hist_r2_body)
         capf[h] = CAPPED ? (float)min(cap_ws[q], kcap) : 0.0f;         // exact: below 2^23
         acc[h] = 0.0f;
     }

@@ -865,6 +865,52 @@ def test_sharded_all_to_all_exchange_by_query_slice(xr, Q, R, K, C, world, k):
     assert abs(got - want) < 1e-7 and abs(got - got_gather) < 1e-12          # vs unsharded: fp32 credits summed per chunk, another chunking
 
 
+@pytest.mark.parametrize("cache_mb", [None, "0"])
+@pytest.mark.parametrize("K", [64, 256])
+def test_pass2_modes_with_and_without_a_pair_cache(xr, monkeypatch, K, cache_mb):
+    """The four places pass 2 takes its offsets from -- k_scan_below of the same workspace (unsharded), the caller (ap_sums with base_all),
+    the gathered totals tables (map_partial), the all-to-all offset slices (map_partial_offsets) -- each with the pair cache and without
+    it (XMH_SCAN_CACHE_MB=0: k_scan_ap_r2 at 64 bits, the k_scan_ap_s that evaluates the pairs from the codes at 256).  Unsharded against
+    the oracle; the shards' divisors bit for bit, their sums at the tolerances of the tests above."""
+    from xmh import _lib, sharded
+    Q, R, C, world, k = 70, 21000, 24, 4, 37
+    if cache_mb is not None:
+        monkeypatch.setenv("XMH_SCAN_CACHE_MB", cache_mb)
+    b = sharded.shard_bounds(R, world)
+    for n in [R] + [b[i + 1] - b[i] for i in range(world)]:
+        assert (int(_lib.lib.xmh_scan_pair_cache_bytes(Q, n, K, 0)) > 0) == (cache_mb is None)
+    qB, rB, qL, rL = _synth(Q, R, K, C, seed=Q + R + K)
+    qL[:, 0] = 1
+    rL[::3, 0] = 1
+    q, ql = xr.pack_sign(qB.cuda()), xr.pack_labels(qL.cuda())
+    r, rl = xr.pack_sign(rB.cuda()), xr.pack_labels(rL.cuda())
+    whole = xr.RankingScan(q, ql, r, rl, C)
+    whole.histograms(False)
+    ap_ref, cap_ref = (t.clone() for t in whole.ap_sums(k))
+    want = float(_orc().map_k(qB, rB, qL, rL, k, stable=True))
+    got_whole = float(whole.map_all(k)[0].item())
+    assert abs(got_whole - want) < MAP_TOL and abs(float((ap_ref / cap_ref.double()).mean()) - got_whole) < 1e-12
+    shards = [sharded.HipShardOps(q, ql, r.rows(b[i], b[i + 1]), rl[b[i]:b[i + 1]].contiguous(), C) for i in range(world)]
+    gathered = torch.stack([torch.stack(o.histograms()) for o in shards]).contiguous()
+    ap = torch.zeros(Q, dtype=torch.float64, device="cuda")
+    for s, o in enumerate(shards):                                                    # the caller's offsets
+        part, cap = o.ap_sums(k, *o.offsets(gathered, s))
+        assert torch.equal(cap, cap_ref)
+        ap += part
+    assert torch.allclose(ap, ap_ref, rtol=1e-6, atol=1e-9)
+    tables = [o.totals().clone() for o in shards]                                     # [nb, qpad, 2] each
+    nb, qpad = tables[0].shape[0], tables[0].shape[1]
+    assert qpad % world == 0
+    sends = [t.view(nb, world, qpad // world, 2).permute(1, 0, 2, 3).contiguous() for t in tables]
+    offs = [xr.slice_offsets(torch.stack([sends[w][j] for w in range(world)]).contiguous()) for j in range(world)]
+    tg = torch.stack(tables).contiguous()
+    got = got_gather = 0.0
+    for w, o in enumerate(shards):
+        got += float(o.map_partial_offsets(k, torch.stack([offs[j][w] for j in range(world)]).contiguous()).item())      # the offset slices
+        got_gather += float(o.map_partial(k, tg, w).item())                                                                # the gathered totals
+    assert abs(got - got_whole) < 1e-7 and abs(got - got_gather) < 1e-12 and abs(got_gather - want) < MAP_TOL
+
+
 def test_sharded_driver_over_rccl_world_one_plain_and_query_blocks():
     """xmh.sharded.map_k_sharded through a real RCCL process group (world size 1, fresh process): the one-shot form and the
     query-block pipeline (asynchronous gathers) against the unsharded scan."""
