@@ -9,3 +9,5 @@ or calling an op without a GPU, raises.
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"
+
+from . import optim  # noqa: E402,F401  (registers "BertAdam": every config names it, so the registry knows it after `import xmh`)

@@ -10,8 +10,8 @@ keys and dtypes :397-404, ``model-<epoch>.pth`` :379-384).  What changes underne
 * distributed eval keeps the gallery sharded (contiguous index ranges, one per rank) instead of all-reducing dense
   zero-initialised buffers (runners/base.py:259-264): packed query codes are all-gathered, per-shard bucket
   histograms are exchanged, every rank ranks its own shard (xmh/sharded.py);
-* optimisation (``train_epoch``) is outside the encode-and-retrieve path and raises, exactly like the reference's
-  own base class does (:296-297).
+* ``build_optimizer`` returns the reference's BertAdam (xmh/optim.py, one fused HIP step); the training loop itself
+  (``train_epoch``) raises, exactly like the reference's own base class does (:296-297).
 """
 from __future__ import annotations
 
@@ -126,7 +126,32 @@ class BaseTrainer:
         self.logger.info(f"Output dim: {self.output_dim}")
 
     def build_optimizer(self, cfg_optimizer=None, parameters=None):
-        raise NotImplementedError("optimisation is outside the encode-and-retrieve path (SURVEY 2.1 #13)")
+        """runners/base.py:120-142 -- the same config keys and defaults; default groups: the backbone at ``backbone_lr``, ``model.hash``
+        at ``lr``; the schedule spans len(train_loader) * epochs steps.  -> (optimizer, None).  No constructor calls this yet."""
+        cfg_optimizer = cfg_optimizer if cfg_optimizer is not None else {}
+        arch = cfg_optimizer.get("arch", "BertAdam")
+        backbone_lr = cfg_optimizer.get("backbone_lr", 0.00001)
+        lr = cfg_optimizer.get("lr", 0.001)
+        warmup_proportion = cfg_optimizer.get("warmup_proportion", 0.1)
+        schedule = cfg_optimizer.get("schedule", "warmup_cosine")
+        b1 = cfg_optimizer.get("b1", 0.9)
+        b2 = cfg_optimizer.get("b2", 0.98)
+        e = cfg_optimizer.get("e", 0.000001)
+        max_grad_norm = cfg_optimizer.get("max_grad_norm", 1.0)
+        weight_decay = cfg_optimizer.get("weight_decay", 0.2)
+        if getattr(self, "train_loader", None) is None:
+            raise RuntimeError("build_optimizer needs the training loader: the schedule's t_total is len(train_loader) * epochs "
+                               "(build the dataset with a training split first)")
+        cls = registry.get_optimizer_class(arch)
+        if cls is None:
+            raise NotImplementedError("optimizer '%s' is not registered (known: %s)" % (arch, registry.list_optimizers()))
+        if parameters is None:
+            parameters = [{"params": self.model.backbone.parameters(), "lr": backbone_lr},
+                          {"params": self.model.hash.parameters(), "lr": lr}]
+        optimizer = cls(parameters, lr=lr, warmup=warmup_proportion, schedule=schedule, b1=b1, b2=b2, e=e,
+                        t_total=len(self.train_loader) * self.epochs, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        self.logger.info("Building optimizer!")
+        return optimizer, None
 
     def build_dataset(self, cfg, train_num=10000, query_num=5000, batch_size=128, num_workers=4, pin_memory=True, shuffle=True):
         arch = cfg.get("arch", "transformer_dataset")
@@ -186,9 +211,9 @@ class BaseTrainer:
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t}, mAP: {self.max_mapt2i}")
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("train_epoch is not built: the losses and the DCMHT / DSPH hash heads have their backward (a frozen "
-                                  "backbone trains the heads with a stock torch optimiser), but the backward of the CLIP towers and of "
-                                  "MITH's / TwDH's heads, and the BertAdam optimiser, are still missing")
+        raise NotImplementedError("train_epoch is not built: the losses and the DCMHT / DSPH hash heads have their backward and "
+                                  "build_optimizer gives the reference's BertAdam (a frozen backbone trains the heads), but the "
+                                  "backward of the CLIP towers and of MITH's / TwDH's heads is still missing")
 
     def compute_loss(self, *a, **k):
         raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")

@@ -79,6 +79,17 @@ class DSPHTrainer(_MethodTrainer):
     """runners/DSPH/runner.py: base generate_hash + sign quantiser."""
 
     hash_scale = 1                                              # runners/DSPH/runner.py:38
+    loss_type = "l1"                                            # runners/DSPH/runner.py:27-31: only named in the display line
+
+    def build_optimizer(self, cfg_optimizer=None, parameters=None):
+        """runners/DSPH/runner.py:83-91: BertAdam as in the base class, and a stock SGD over the HyP proxies from the config's
+        ``hyp`` sub-section -> (optimizer, optimizer_loss, None)"""
+        optimizer, lr_schedu = super().build_optimizer(cfg_optimizer=cfg_optimizer, parameters=parameters)
+        hyp = (cfg_optimizer.get("hyp") if cfg_optimizer is not None else None) or {}
+        optimizer_loss = torch.optim.SGD(params=self.model.hyp.parameters(), lr=hyp.get("lr", 0.02), momentum=hyp.get("momentum", 0.9),
+                                         weight_decay=hyp.get("weight_decay", 0.0005))
+        self.logger.info("Building optimizer!")
+        return optimizer, optimizer_loss, lr_schedu
 
     def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
         """runners/DSPH/runner.py:93-101: the HyP objective of one batch (xmh_hyp.hip behind torch.autograd), differentiable with

@@ -648,6 +648,40 @@ int xmh_head_dsph_backward(const float* w, const float* x, const float* y, const
                            int64_t B, int E, int K, float* d_w, float* d_b, float* d_x, int accumulate, void* workspace,
                            size_t workspace_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BertAdam (models/common/optimizer.py:50-167): one optimiser step over any number of fp32 tensors in two launches.
+ * Per tensor: norm = |g|_2; coef = min(1, max_grad_norm / (norm + 1e-6)) when max_grad_norm > 0, else 1; g' = g coef;
+ * m = m b1 + (1 - b1) g'; v = v b2 + (1 - b2) g' g'; u = m / (sqrt(v) + e), plus weight_decay p when weight_decay > 0; p -= lr u.
+ * p, m, v are written; g' is written back only where coef < 1 (or NaN).  No bias correction.  A NaN or infinite gradient follows
+ * IEEE as the reference does (NaN norm -> NaN coef -> that tensor's p, m, v, g NaN) and touches that tensor only.
+ * table [n_tensors] and chunk_map [total_chunks] are DEVICE arrays the caller fills; the call does not read them on the host.
+ *   chunk_map lists the chunks of tensor 0, then of tensor 1, ...: tensor t has ceil(numel / xmh_bertadam_chunk()) chunks, its
+ *   j-th chunk is {start = j * chunk, tensor = t, first_chunk = index of the tensor's chunk 0 in the map}.
+ * Limits: numel >= 1 per tensor (leave empty tensors out), total_chunks <= 2^31 - 1 (XMH_ENOTSUP beyond); p, g, m, v need 4-byte
+ * alignment only (16-byte accesses where all four are 16-byte aligned, dword accesses otherwise) and must not overlap.
+ * No host synchronisation, no allocation, no atomics, fixed summation order (two calls on the same inputs agree to the bit).
+ * Workspace: xmh_bertadam_ws_bytes(n_tensors, total_chunks) bytes of device memory, 256-byte aligned (0 for bad counts).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_bertadam_tensor {
+    float *p, *g, *m, *v;                              /* parameter, its gradient, next_m, next_v: numel fp32 each, contiguous */
+    int64_t numel;
+    float lr;                                          /* this tensor's SCHEDULED rate (the host's double, cast) */
+    float b1, b2;
+    float one_minus_b1, one_minus_b2;                  /* (float)(1.0 - b1) of the host's doubles, as the reference's alpha / value */
+    float e, weight_decay, max_grad_norm;
+} xmh_bertadam_tensor;                                 /* 72 bytes */
+typedef struct xmh_bertadam_chunk_ref {
+    int64_t start;                                     /* first element of the chunk within its tensor */
+    int32_t tensor;                                    /* index into table */
+    int32_t first_chunk;                               /* map index of this tensor's first chunk */
+} xmh_bertadam_chunk_ref;                              /* 16 bytes */
+/* elements per chunk (one block each); fixed for a build */
+int64_t xmh_bertadam_chunk(void);
+size_t xmh_bertadam_ws_bytes(int64_t n_tensors, int64_t total_chunks);
+/* n_tensors == 0 is a successful no-op; negative counts, null pointers, a short or misaligned workspace are XMH_EINVAL. */
+int xmh_bertadam_step(const xmh_bertadam_tensor* table, int64_t n_tensors, const xmh_bertadam_chunk_ref* chunk_map,
+                      int64_t total_chunks, void* ws, size_t ws_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
