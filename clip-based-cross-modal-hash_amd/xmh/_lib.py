@@ -87,6 +87,10 @@ class DcmhtGrads(C.Structure):                 # xmh_dcmht_grads
                 ("d_b2", vp), ("d_x", vp)]
 
 
+class ClipBlockGrads(C.Structure):             # xmh_clip_block_grads
+    _fields_ = [(n, vp) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")]
+
+
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
 PROTOTYPES = {
     "xmh_version": (i32, []),
@@ -139,6 +143,9 @@ PROTOTYPES = {
     "xmh_clip_blocks_forward": (i32, [C.POINTER(ClipBlock), i32, i32, i32, vp, i64, i32, i32, vp, i32, vp, sz, vp]),
     "xmh_clip_saved_bytes": (sz, [i64, i32, i32, i32]),
     "xmh_clip_blocks_forward_saved": (i32, [C.POINTER(ClipBlock), i32, i32, i32, vp, i64, i32, i32, vp, i32, vp, sz, vp, sz, vp]),
+    "xmh_clip_blocks_backward_ws_bytes": (sz, [i64, i32, i32]),
+    "xmh_clip_blocks_backward": (i32, [C.POINTER(ClipBlock), i32, i32, i32, i64, i32, i32, vp, vp, sz, vp, i32, C.POINTER(ClipBlockGrads), i32,
+                                       vp, sz, vp]),
     "xmh_vit_b32_forward": (i32, [C.POINTER(VitWeights), vp, i64, i32, vp, vp, vp, sz, vp]),
     "xmh_text_forward": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "xmh_text_forward_packed": (i32, [C.POINTER(TextWeights), vp, vp, i64, i64, i32, i32, vp, vp, sz, vp]),

@@ -169,6 +169,97 @@ class Transformer(nn.Module):
             saved.append(rec)
         return x, saved
 
+    # the twelve parameters of a block in the member order of xmh_clip_block_grads (include/xmh.h)
+    @staticmethod
+    def _train_params(blk):
+        return (blk.ln_1.weight, blk.ln_1.bias, blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj.weight,
+                blk.attn.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, blk.mlp.c_proj.weight,
+                blk.mlp.c_proj.bias)
+
+    def run_train(self, x: torch.Tensor, causal: bool = False, key_padding_mask=None) -> torch.Tensor:
+        """The block stack in exact fp32 behind torch.autograd: x [B, L, D] is copied, never written; the result carries
+        a graph whose backward is ONE call of xmh_clip_blocks_backward over the record xmh_clip_blocks_forward_saved kept.  Gradients
+        go to exactly the parameters with requires_grad (and to x if it requires grad).  With nothing to differentiate -- under
+        no_grad, or nothing requires grad -- this is `run` in exact mode on a copy, and no record is kept."""
+        if not x.is_cuda or x.dim() != 3:
+            raise ValueError("run_train takes a [B, L, D] tensor on the GPU; there is no CPU fallback")
+        params = [p for blk in self.resblocks for p in self._train_params(blk)]
+        kpm = None if key_padding_mask is None else key_padding_mask.to(device=x.device, dtype=torch.uint8).contiguous()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            return _BlocksTrain.apply(self, bool(causal), kpm, x, *params)
+        return _train_forward(self, x, bool(causal), kpm, params, keep_record=False)[0]
+
+
+def _exact_desc(tr, params, keep: list):
+    """xmh_clip_block array over the parameters IN PLACE (fp32 weights only: no operand planes, nothing cached across steps)"""
+    for p in params:
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("run_train needs contiguous fp32 CUDA/HIP parameters (got %s %s); there is no CPU fallback" % (p.dtype, p.device))
+    arr = (_lib.ClipBlock * len(tr.resblocks))()
+    for i in range(len(tr.resblocks)):
+        l1w, l1b, qw, qb, ow, ob, l2w, l2b, fw, fb, pw, pb = (p.detach() for p in params[12 * i:12 * i + 12])
+        lin = lambda w, b: _lib.Linear(w.data_ptr(), None, None, b.data_ptr(), w.shape[0], w.shape[1])      # noqa: E731
+        arr[i] = _lib.ClipBlock(l1w.data_ptr(), l1b.data_ptr(), l2w.data_ptr(), l2b.data_ptr(), lin(qw, qb), lin(ow, ob), lin(fw, fb), lin(pw, pb))
+    keep.extend(params)
+    return arr
+
+
+def _train_forward(tr, x, causal, kpm, params, keep_record=True):
+    """-> (y, record buffer or None): exact-mode forward on a copy of x"""
+    y = x.detach().to(torch.float32).contiguous()
+    y = y.clone() if y.data_ptr() == x.data_ptr() else y
+    B, L, D = y.shape
+    layers = len(tr.resblocks)
+    heads = tr.resblocks[0].heads if layers else 1
+    keep = []
+    blocks = _exact_desc(tr, params, keep)
+    nbytes = lib.xmh_clip_workspace_bytes(B, L, D, 0, 0, ops.PREC_F32X)
+    ws = _workspace(nbytes, y.device)
+    if not keep_record:
+        check(lib.xmh_clip_blocks_forward(blocks, layers, D, heads, ptr(y), B, L, int(causal), ptr(kpm), ops.PREC_F32X, ptr(ws), nbytes,
+                                          current_stream()), "xmh_clip_blocks_forward")
+        return y, None
+    sbytes = lib.xmh_clip_saved_bytes(B, L, D, layers)
+    buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=y.device)
+    check(lib.xmh_clip_blocks_forward_saved(blocks, layers, D, heads, ptr(y), B, L, int(causal), ptr(kpm), ops.PREC_F32X, ptr(ws), nbytes,
+                                            ptr(buf), sbytes, current_stream()), "xmh_clip_blocks_forward_saved")
+    return y, buf
+
+
+class _BlocksTrain(torch.autograd.Function):
+    """forward = xmh_clip_blocks_forward_saved (exact mode), backward = xmh_clip_blocks_backward"""
+
+    @staticmethod
+    def forward(ctx, tr, causal, kpm, x, *params):
+        y, buf = _train_forward(tr, x, causal, kpm, params)
+        ctx.tr, ctx.causal, ctx.kpm, ctx.meta = tr, causal, kpm, (x.shape, x.dtype)
+        ctx.save_for_backward(buf, *params)             # saved parameters: autograd notices an in-place change before backward
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernels are not themselves differentiable
+    def backward(ctx, g):
+        buf, *params = ctx.saved_tensors
+        tr = ctx.tr
+        B, L, D = ctx.meta[0]
+        layers = len(tr.resblocks)
+        need = ctx.needs_input_grad
+        gp = [torch.empty_like(p) if need[4 + i] else None for i, p in enumerate(params)]
+        grads = (_lib.ClipBlockGrads * max(layers, 1))()
+        for i in range(layers):
+            grads[i] = _lib.ClipBlockGrads(*[_addr(t) for t in gp[12 * i:12 * i + 12]])
+        dy = g.detach().to(torch.float32).contiguous()
+        dy = dy.clone() if dy.data_ptr() == g.data_ptr() else dy      # updated in place: never the caller's tensor
+        keep = []
+        blocks = _exact_desc(tr, params, keep)
+        nbytes = lib.xmh_clip_blocks_backward_ws_bytes(B, L, D)
+        ws = _workspace(nbytes, dy.device)
+        check(lib.xmh_clip_blocks_backward(blocks, layers, D, tr.resblocks[0].heads if layers else 1, B, L, int(ctx.causal), ptr(ctx.kpm),
+                                           ptr(buf), buf.numel() * 4 if layers else 0, ptr(dy), int(need[3]), grads, 0, ptr(ws), nbytes,
+                                           current_stream()), "xmh_clip_blocks_backward")
+        gx = dy.reshape(ctx.meta[0]).to(ctx.meta[1]) if need[3] else None
+        return (None, None, None, gx, *gp)
+
 
 class VisionTransformer(nn.Module):
     def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim, return_patches=False):

@@ -410,6 +410,26 @@ size_t xmh_clip_saved_bytes(int64_t B, int L, int width, int layers);
 int xmh_clip_blocks_forward_saved(const xmh_clip_block* blocks, int layers, int width, int heads, float* x, int64_t B, int L,
                                   int causal, const uint8_t* key_padding_mask, int precision, void* workspace,
                                   size_t workspace_bytes, float* saved, size_t saved_bytes, xmh_stream_t stream);
+/* Backward of the block stack from the record of xmh_clip_blocks_forward_saved: exact fp32 products, the fp32 weights
+ * (w_f32) of the descriptors, the record layout above exactly as it stands.
+ * xmh_clip_block_grads: where the gradients of one layer's twelve parameters go (device pointers, the parameters' own shapes:
+ * qkv_w [3D, D], out_w [D, D], fc_w [4D, D], proj_w [D, 4D]); NULL = a frozen parameter, and a product nothing downstream needs is
+ * not launched.  dy [B, L, width] is the gradient of the stack's output; it is updated in place and holds dx, the gradient of the
+ * residual stream entering the stack, on return (need_dx != 0).  accumulate != 0: every parameter gradient is added to what its
+ * buffer holds, else overwritten.  need_dx == 0: the walk stops at the lowest layer with any non-NULL gradient pointer -- nothing
+ * below it is read, neither its record nor its weights nor its descriptor -- and inside that layer the products that only feed dx
+ * are skipped; dy is then scratch.  Limits as the forward's: width % 4 == 0, width / heads == 64, L <= 128 (XMH_ENOTSUP beyond;
+ * B * L <= 2^21); -12 for a short saved buffer or workspace, -22 for null or misfitting arguments.  A key padding mask that hides
+ * every key of a query gives NaN, as in the reference.  No host synchronisation, no allocation, no float atomics: every reduction
+ * is summed in one fixed order, two calls on equal inputs agree to the bit. */
+typedef struct xmh_clip_block_grads {
+    float *ln1_w, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ln2_w, *ln2_b, *fc_w, *fc_b, *proj_w, *proj_b;
+} xmh_clip_block_grads;
+size_t xmh_clip_blocks_backward_ws_bytes(int64_t B, int L, int width);
+int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers, int width, int heads, int64_t B, int L, int causal,
+                             const uint8_t* key_padding_mask, const float* saved, size_t saved_bytes, float* dy, int need_dx,
+                             const xmh_clip_block_grads* grads, int accumulate, void* workspace, size_t workspace_bytes,
+                             xmh_stream_t stream);
 /* VisionTransformer.forward: image [B, 3, r, r] f32 -> out_cls [B, out_dim]; out_tokens [B, L, out_dim] (L = patches + 1,
  * every token through ln_post and proj: the return_patches mode, row 0 of each item = the cls feature) or NULL.
  * Exactly one of out_cls / out_tokens may be NULL. */
