@@ -3,7 +3,7 @@
 //
 // The kernel it replaced (round 2's k_scan_hist_m, removed in round 5) staged a pre-expanded int8 image of the gallery (8 bytes per code
 // bit and label bit, 1 KB pieces through a two-deep LDS ring by LDS-DMA, two barriers per 64-item batch) and at 129 / 257 bucket rows per
-// wave its LDS footprint left one block per CU.  Here nothing is staged: as in k_topk_filter_mfma (xmh_topk.hip), `word & (0x01010101 << p)`
+// wave its LDS footprint left one block per CU.  Here nothing is staged: as in k_topk_filter_mfma (xmh_topk_kernels.h), `word & (0x01010101 << p)`
 // leaves bits p, p + 8, p + 16, p + 24 of a packed word each alone in its byte, worth 2^p there (p = 7 through
 // `(word >> 1) & 0x40404040`), 9 VALU operations for 32 bits; the query side (B operand, built once per wave, kept in registers)
 // carries the matching weight s_i * 64 / 2^p with s_i = 1 - 2 q_i, so every product is 64 s_i x_i and an accumulator started at

@@ -10,8 +10,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
-#ifdef WITH_LIB                                                  // -DWITH_LIB -I clip-based-cross-modal-hash_amd/csrc -I include: the library's own filter kernels in the same loop
-#include "xmh_topk.hip"
+#ifdef WITH_LIB                                                  // -DWITH_LIB -I clip-based-cross-modal-hash_amd/csrc: the library's own filter kernels in the same loop
+#include "xmh_topk_kernels.h"
 #endif
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -157,11 +157,12 @@ int main(int argc, char** argv) {
         CK(hipMalloc(&cnt, 4096)); CK(hipMalloc(&cand, (size_t)kCandCap * 8 * 2));
         const uint32_t th = (uint32_t)(getenv("LIB_THR") ? atoi(getenv("LIB_THR")) : thr);
         CK(hipMemcpy(t_est, &th, 4, hipMemcpyHostToDevice));
+        const uint32_t* nozero = nullptr;                        // binary codes: the per-piece filter takes no zero planes and no padding
         auto runlib = [&](const char* name, auto kern, int grid) {
-            for (int i = 0; i < 2 * ngal; ++i) { CK(hipMemsetAsync(cnt, 0, 4096, 0)); hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, (const uint32_t*)dq, (const uint32_t*)gal[i % ngal], 1, R, (const uint32_t*)t_est, (const uint32_t*)bnd, cnt, cand); }
+            for (int i = 0; i < 2 * ngal; ++i) { CK(hipMemsetAsync(cnt, 0, 4096, 0)); hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, (const uint32_t*)dq, nozero, (const uint32_t*)gal[i % ngal], nozero, 0, 1, R, (const uint32_t*)t_est, (const uint32_t*)bnd, cnt, cand); }
             CK(hipDeviceSynchronize());
             CK(hipEventRecord(e0));
-            for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, (const uint32_t*)dq, (const uint32_t*)gal[i % ngal], 1, R, (const uint32_t*)t_est, (const uint32_t*)bnd, cnt, cand);
+            for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, (const uint32_t*)dq, nozero, (const uint32_t*)gal[i % ngal], nozero, 0, 1, R, (const uint32_t*)t_est, (const uint32_t*)bnd, cnt, cand);
             CK(hipEventRecord(e1));
             CK(hipEventSynchronize(e1));
             float ms = 0;
@@ -172,7 +173,7 @@ int main(int argc, char** argv) {
             printf("%-28s grid %5d  %7.2f us  %5.2f TB/s  (%.3f of 8)  candidates %u (over %d launches)\n", name, grid, t * 1e6, bytes / t / 1e12, bytes / t / 8e12, got, iters);
         };
         for (int grid : {512, 1024, 2048}) {
-            runlib("LIB k_topk_filter_seq<8,4,1>", k_topk_filter_seq<8, 4, 1>, grid);
+            runlib("LIB k_topk_filter_seq<8,4,1,false>", k_topk_filter_seq<8, 4, 1, false>, grid);
         }
         // the same bytes as 64-bit and 32-bit codes (4 x / 8 x the items; thresholds low enough for a few hundred candidates)
         const int64_t R8 = R;
