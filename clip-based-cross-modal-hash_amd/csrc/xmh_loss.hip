@@ -10,6 +10,8 @@
 //                              euclidean: grad a_i = sum_j r_ij (a_i - b_j),  r_ij = 2/B^2 (L - (m/s - 1)(1 - L)[s <= m]), 0 where s = 0
 //                                         (torch.cdist's backward masks zero distances the same way);
 //                              cosine:    grad a_i = sum_j h_ij (b^_j - c_ij a^_i) / |a_i|,  h_ij = 2/B^2 (-L/s + (1 - L)/(1 - s))[t <= c_ij <= 1 - t]
+//                              A NaN distance or cosine (a NaN entry, a zero row under cosine) passes through the clamps of the forward
+//                              and the masks of the gradient as it does through the reference's clip and autograd: NaN terms, NaN rows.
 //                              The gradient with respect to b is the same call with a and b swapped (s, c and L are symmetric), and
 //                              for a term with a == b the caller passes scale = 2.
 //   xmh_quant_loss_grad        d/dcode = -4 (2 c - 1) / n
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256) void k_pair_similarity_loss(const float* __res
                 nb = fmaf(bj[c], bj[c], nb);
             }
             float s = dot / (sqrtf(na) * sqrtf(nb));
-            s = fminf(fmaxf(s, threshold), 1.0f - threshold);
+            if (!isnan(s)) s = fminf(fmaxf(s, threshold), 1.0f - threshold);   // fminf / fmaxf drop a NaN, the reference's clip keeps it
             const float l = -L * logf(s) - (1.0f - L) * logf(1.0f - s);
             pos += (double)l;
             neg += (double)l;
@@ -70,7 +72,8 @@ __global__ __launch_bounds__(256) void k_pair_similarity_loss(const float* __res
             }
             const float s = sqrtf(d2);
             const float p = s * L;
-            float n = fminf(s * (1.0f - L), max_value);
+            float n = s * (1.0f - L);
+            if (!isnan(n)) n = fminf(n, max_value);
             n = max_value * (1.0f - L) - n;
             pos += (double)p * (double)p;
             neg += (double)n * (double)n;
@@ -130,6 +133,9 @@ __global__ __launch_bounds__(256) void k_pair_similarity_grad(const float* __res
                 const float h = w * (rel ? -1.0f / cs : 1.0f / (1.0f - cs));
                 cf = h * inv_na * inv_nb;
                 hc += (double)h * (double)cs;
+            } else if (isnan(cs)) {                              // a zero row or a NaN entry: the reference's gradient is NaN, not masked
+                cf = cs;
+                hc += (double)cs;
             }
         } else {
             float d2 = 0.0f;
@@ -139,6 +145,7 @@ __global__ __launch_bounds__(256) void k_pair_similarity_grad(const float* __res
             }
             const float s = sqrtf(d2);
             if (s > 0.0f) cf = rel ? w : (s <= max_value ? -w * (max_value / s - 1.0f) : 0.0f);
+            else if (isnan(s)) cf = s;                           // NaN fails both comparisons; the reference's cdist backward passes it on
         }
         coef[j] = cf;
     }

@@ -547,7 +547,8 @@ int xmh_float_sort_ap(const float* dist, const uint32_t* qlab, const uint32_t* r
 /* similarity_loss (models/DCMHT/DCMHT.py:72-98) of one pair of code matrices a, b [B, D] with packed multi-hot labels lab
  * [B][ceil(C/32)] (label_sim = calc_label_sim(labels, labels), common/calc_utils.py:8-10).  cosine == 0: euclidean branch with
  * max_value = sqrt(2 K vartheta) (:81-88); cosine != 0: the cosine branch with `threshold` (:92-95).
- * out2 (device, 2 doubles) = (positive_loss, negative_loss). */
+ * out2 (device, 2 doubles) = (positive_loss, negative_loss).  A NaN distance or cosine (a NaN entry, a zero row under cosine) makes
+ * both outputs NaN, as the reference's clip does; the gradient below is then NaN in every row that pairs with it.  D <= 12288. */
 int xmh_pair_similarity_loss(const float* a, const float* b, int64_t B, int D, const uint32_t* lab, int C, int cosine,
                              float max_value, float threshold, double* out2, xmh_stream_t stream);
 /* soft_argmax_hash_loss (models/DCMHT/DCMHT.py:100-105): out (device, 1 double) = 1 - mean((2 code - 1)^2) over n elements */
@@ -555,7 +556,8 @@ int xmh_quant_loss(const float* code, int64_t n, double* out, xmh_stream_t strea
 /* d(positive_loss + negative_loss)/da of xmh_pair_similarity_loss, as autograd derives it from models/DCMHT/DCMHT.py:72-98
  * (torch.cdist's backward: zero distances contribute nothing; clip passes the gradient on the closed interval).  grad_a [B, D]
  * (device) is written, or added to when accumulate != 0, with scale * upstream[0] (upstream: device float, NULL = 1) folded in.
- * The gradient with respect to b is the same call with a and b exchanged; for a term with a == b pass scale = 2. */
+ * The gradient with respect to b is the same call with a and b exchanged; for a term with a == b pass scale = 2.
+ * (D + B) * 4 <= 65536 (one code row and one row of pair weights in LDS; XMH_ENOTSUP beyond). */
 int xmh_pair_similarity_loss_grad(const float* a, const float* b, int64_t B, int D, const uint32_t* lab, int C, int cosine,
                                   float max_value, float threshold, float scale, const float* upstream, float* grad_a,
                                   int accumulate, xmh_stream_t stream);
