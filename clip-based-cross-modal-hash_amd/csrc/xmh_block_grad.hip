@@ -16,6 +16,7 @@
 // One product kernel, C[i][j] = sum_k A(i, k) B(j, k) over strided views (as k_mm of xmh_head_grad.hip), on v_mfma_f32_32x32x2_f32:
 // an exact fmaf chain per 32 consecutive k, the 32-blocks added in index order.  Every reduction here runs in one fixed order (no
 // float atomics), so two calls on equal inputs agree to the bit; no host synchronisation, no allocation.
+#include "xmh_clip_record.h"
 #include "xmh_common.h"
 #include "xmh_device.h"
 
@@ -23,7 +24,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr float kLnEps = 1e-5f;                  // nn.LayerNorm default, as in the forward
-constexpr int kSavedFloatsPerElement = 16;       // the record of xmh_clip_blocks_forward_saved (xmh_forward.hip)
 constexpr int kTile = 64, kBK = 32, kLd = kTile + 1;
 constexpr int kMaxSplits = 16, kTilesWanted = 512;
 constexpr int kCols = 32, kGroups = kThreads / kCols;
@@ -32,6 +32,7 @@ constexpr int64_t kMaxRows = 1ll << 21;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+using xmh::group_sum;
 using xmh::wave_sum;
 
 // d/dx [x sigmoid(1.702 x)] = s (1 + 1.702 x (1 - s))
@@ -151,16 +152,6 @@ __global__ __launch_bounds__(kThreads) void k_reduce_parts(const float* __restri
         for (int z = 1; z < splits; ++z) s += bpart[(int64_t)z * nb + e];
         bout[e] = accumulate ? bout[e] + (float)s : (float)s;
     }
-}
-
-// fixed-order sum of the row groups' partials of one column; valid on every thread of the column
-__device__ __forceinline__ double group_sum(double v, double (*sh)[kCols], int col, int grp) {
-    sh[grp][col] = v;
-    __syncthreads();
-    double s = sh[0][col];
-    for (int g = 1; g < kGroups; ++g) s += sh[g][col];
-    __syncthreads();
-    return s;
 }
 
 // bias gradient alone (its weight is frozen): column sums of dy [M, N] in double, in the very order of the TN kernel's rowsum -- the
@@ -540,7 +531,7 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
     if (B * L > kMaxRows) return xmh::fail(XMH_ENOTSUP, "%s: %lld x %d tokens (at most 2^21)", who, (long long)B, L);
     const int64_t M = B * L;
     const int D = width;
-    const size_t need = (size_t)layers * kSavedFloatsPerElement * (size_t)M * D * sizeof(float);
+    const size_t need = xmh::saved_record_bytes(layers, M, D);
     if (saved_bytes < need) return xmh::fail(-12, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, need);
     Work wk;
     const size_t ws_need = work_layout(M, D, workspace, &wk);
@@ -554,8 +545,7 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
     }
     for (int i = lowest; i < layers; ++i) {
         const xmh_clip_block& b = blocks[i];
-        if (b.qkv.n != 3 * D || b.qkv.k != D || b.out.n != D || b.out.k != D || b.fc.k != D || b.fc.n != 4 * D || b.proj.n != D || b.proj.k != b.fc.n)
-            return xmh::fail(-22, "%s: block %d has layer shapes that do not fit width %d", who, i, D);
+        if (!xmh::block_fits(b, D)) return xmh::fail(-22, "%s: block %d has layer shapes that do not fit width %d", who, i, D);
         if (!b.qkv.w_f32 || !b.out.w_f32 || !b.fc.w_f32 || !b.proj.w_f32 || !b.ln1_w || !b.ln2_w)
             return xmh::fail(-22, "%s: block %d lacks fp32 weights", who, i);
     }
@@ -563,10 +553,7 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
     for (int i = layers - 1; i >= lowest; --i) {
         const xmh_clip_block& b = blocks[i];
         const xmh_clip_block_grads& g = grads[i];
-        const float* rec = saved + (size_t)i * kSavedFloatsPerElement * (size_t)M * D;
-        const size_t md = (size_t)M * D;
-        const float *x_in = rec, *ln1 = rec + md, *qkv = rec + 2 * md, *attn = rec + 5 * md, *x_mid = rec + 6 * md, *ln2 = rec + 7 * md,
-                    *fc_pre = rec + 8 * md, *fc_act = rec + 12 * md;
+        const xmh::SavedRecord<const float> r = xmh::saved_record(saved, i, M, D);
         // what has to exist for what is asked for: each stage is needed by everything upstream of it
         const bool need_in = i > lowest || need_dx;
         const bool need_dln1 = g.ln1_w || g.ln1_b || need_in;
@@ -574,22 +561,22 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
         const bool need_dxmid = g.out_w || g.out_b || need_dqkv;
         const bool need_dln2 = g.ln2_w || g.ln2_b || need_dxmid;
         const bool need_dfc = g.fc_w || g.fc_b || need_dln2;
-        weight_grads(st, wk, dy, fc_act, M, D, 4 * D, g.proj_w, g.proj_b, accumulate);
+        weight_grads(st, wk, dy, r.fc_act, M, D, 4 * D, g.proj_w, g.proj_b, accumulate);
         if (!need_dfc) continue;
-        launch_nn(st, dy, b.proj.w_f32, M, D, 4 * D, wk.t4, fc_pre);                           // dfc_pre
-        weight_grads(st, wk, wk.t4, ln2, M, 4 * D, D, g.fc_w, g.fc_b, accumulate);
+        launch_nn(st, dy, b.proj.w_f32, M, D, 4 * D, wk.t4, r.fc_pre);                         // dfc_pre
+        weight_grads(st, wk, wk.t4, r.ln2, M, 4 * D, D, g.fc_w, g.fc_b, accumulate);
         if (!need_dln2) continue;
         launch_nn(st, wk.t4, b.fc.w_f32, M, 4 * D, D, wk.t1, nullptr);                         // dln2
-        ln_bwd(st, wk, x_mid, wk.t1, b.ln2_w, dy, need_dxmid, g.ln2_w, g.ln2_b, M, D, accumulate);    // dy = dx_mid
+        ln_bwd(st, wk, r.x_mid, wk.t1, b.ln2_w, dy, need_dxmid, g.ln2_w, g.ln2_b, M, D, accumulate);    // dy = dx_mid
         if (!need_dxmid) continue;
-        weight_grads(st, wk, dy, attn, M, D, D, g.out_w, g.out_b, accumulate);
+        weight_grads(st, wk, dy, r.attn, M, D, D, g.out_w, g.out_b, accumulate);
         if (!need_dqkv) continue;
         launch_nn(st, dy, b.out.w_f32, M, D, D, wk.t1, nullptr);                               // dattn
-        if (int rc = attn_bwd(st, qkv, wk.t1, wk.t4, B, L, heads, causal, key_padding_mask)) return rc;      // dqkv [M, 3D]
-        weight_grads(st, wk, wk.t4, ln1, M, 3 * D, D, g.qkv_w, g.qkv_b, accumulate);
+        if (int rc = attn_bwd(st, r.qkv, wk.t1, wk.t4, B, L, heads, causal, key_padding_mask)) return rc;      // dqkv [M, 3D]
+        weight_grads(st, wk, wk.t4, r.ln1, M, 3 * D, D, g.qkv_w, g.qkv_b, accumulate);
         if (!need_dln1) continue;
         launch_nn(st, wk.t4, b.qkv.w_f32, M, 3 * D, D, wk.t1, nullptr);                        // dln1
-        ln_bwd(st, wk, x_in, wk.t1, b.ln1_w, dy, need_in, g.ln1_w, g.ln1_b, M, D, accumulate);  // dy = dx
+        ln_bwd(st, wk, r.x_in, wk.t1, b.ln1_w, dy, need_in, g.ln1_w, g.ln1_b, M, D, accumulate);  // dy = dx
     }
     XMH_LAUNCH_CHECK(who);
     return XMH_OK;

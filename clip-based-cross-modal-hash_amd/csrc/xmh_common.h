@@ -35,6 +35,12 @@ inline int fail(int code, const char* fmt, ...) {
         if (e__ != hipSuccess) return ::xmh::fail(XMH_EHIP, "%s: %s", #call, hipGetErrorString(e__));          \
     } while (0)
 
+// a chain of calls that each return a status: the first non-zero one is the caller's result
+#define XMH_TRY(expr)                       \
+    do {                                    \
+        if (int rc__ = (expr)) return rc__; \
+    } while (0)
+
 inline hipStream_t as_stream(xmh_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

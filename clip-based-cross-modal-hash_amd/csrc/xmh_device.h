@@ -1,6 +1,6 @@
-// Device helpers shared by the training kernels (xmh_hyp, xmh_mith_loss, xmh_head_grad), xmh_encode and xmh_dense, and the workspace
-// carver of the host entry points.  The scan, top-k and GEMM kernels keep their own hand-scheduled idioms; xmh_loss.hip keeps its
-// block_sum, whose result lives on thread 0 only.
+// Device helpers shared by the training kernels (xmh_hyp, xmh_mith_loss, xmh_head_grad, xmh_block_grad), xmh_encode and xmh_dense, and
+// the workspace carver of the host entry points: wave and block reductions, the column kernels' group_sum.  The scan, top-k and GEMM
+// kernels keep their own hand-scheduled idioms; xmh_loss.hip keeps its block_sum, whose result lives on thread 0 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -47,6 +47,18 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
     __syncthreads();
     T s = sh[0];
     for (int w = 1; w < kWaves; ++w) s += sh[w];
+    __syncthreads();
+    return s;
+}
+
+// Column kernels (kCols adjacent columns x kGroups interleaved row groups per block): fixed-order sum of the row groups' partials of
+// one column; valid on every thread of the column
+template <int kGroups, int kCols>
+__device__ __forceinline__ double group_sum(double v, double (&sh)[kGroups][kCols], int col, int grp) {
+    sh[grp][col] = v;
+    __syncthreads();
+    double s = sh[0][col];
+    for (int g = 1; g < kGroups; ++g) s += sh[g][col];
     __syncthreads();
     return s;
 }

@@ -5,7 +5,20 @@
 //
 //   image: im2col -> GEMM(conv1) -> cls/pos/ln_pre -> blocks -> ln_post -> GEMM proj   (cls row only, or every token)
 //   text : embed + pos -> blocks (causal [+ key padding]) -> ln_final -> GEMM text_projection -> EOS row
-//   block: LN, GEMM qkv, attention, GEMM out + residual, LN, GEMM c_fc + QuickGELU, GEMM c_proj + residual
+//
+// The residual block is enqueued in ONE place, as two halves over a bundle of buffers (BlockBufs):
+//   attention half   ln1 = LN(x_in), qkv = GEMM(ln1), attn = attention(qkv)
+//   row-wise half    x_mid = x_in + GEMM(attn), ln2 = LN(x_mid), fc = QuickGELU(GEMM(ln2)), x_out = x_mid + GEMM(fc)
+// and its three callers only choose the buffers:
+//   plain, every row   x_in = x_mid = x_out = x (in place); ln1 = ln2 = h, attn = a, fc = f of the shared scratch (BlockScratch).
+//   tail rows          the last block of a tower that returns one row per sequence: the attention half as above, then the kept rows of
+//                      a are gathered into h and those of x into x_tail, and the row-wise half runs on these B rows with attn = h,
+//                      ln2 = a, fc = f and x_in = x_mid = x_out = x_tail.
+//   saved              the fields of layer i's record (xmh_clip_record.h) are the fp32 buffers, the scratch keeps the operand planes;
+//                      x_out is the next record's x_in (the last layer writes x), and QuickGELU runs as a pass of its own between
+//                      c_fc and c_proj (xmh::quickgelu_planes: the epilogue's function on the stored fc_pre), so both sides are kept.
+// Same wrappers, same kernels, same order in all three, so they agree bit for bit.
+#include "xmh_clip_record.h"
 #include "xmh_common.h"
 #include "xmh_device.h"
 #include "xmh_planes.h"
@@ -18,12 +31,18 @@ constexpr float kLnEps = 1e-5f;                      // nn.LayerNorm default, as
 
 using xmh::Arena;                                    // the same arithmetic sizes the workspace (xmh_clip_workspace_bytes) and hands out the pieces
 
-// Parity and fast mode keep every GEMM input as fp16 operand planes (xmh_planes.h), written by the kernel that produces it:
-// LayerNorm -> qkv / c_fc, attention -> out_proj, the c_fc epilogue (QuickGELU) -> c_proj.  Only the residual stream x and the
-// qkv rows the attention kernel reads stay fp32.  Exact mode (fp32 MFMA) keeps the fp32 buffers.
+// One intermediate of the chain: its fp32 buffer and / or its fp16 operand planes (xmh_planes.h); what is not kept is null.
+// Parity and fast mode keep every GEMM input as planes, written by the kernel that produces it: LayerNorm -> qkv / c_fc,
+// attention -> out_proj, the c_fc epilogue (QuickGELU) -> c_proj.  Only the residual stream x and the qkv rows the attention kernel
+// reads stay fp32.  Exact mode (fp32 MFMA) keeps the fp32 buffers and no planes.
+struct Act {
+    float* f;
+    xmh::Planes p;
+};
+
 struct BlockScratch {
-    float *h, *qkv, *a, *f;                          // exact mode: fp32 activations
-    xmh::Planes hP, aP, fP;                          // parity / fast mode
+    float* qkv;
+    Act h, a, f;                                     // LayerNorm output, attention output, c_fc output
     xmh::Planes any;                                 // planes of an fp32 activation that was not produced as planes (linear_any)
 };
 
@@ -39,14 +58,14 @@ BlockScratch carve_blocks(Arena& ar, int64_t M, int width, int precision) {
     BlockScratch s{};
     s.qkv = ar.take<float>((size_t)M * width * 3);
     if (precision == kPrecExact) {
-        s.h = ar.take<float>((size_t)M * width);
-        s.a = ar.take<float>((size_t)M * width);
-        s.f = ar.take<float>((size_t)M * width * 4);
+        s.h.f = ar.take<float>((size_t)M * width);
+        s.a.f = ar.take<float>((size_t)M * width);
+        s.f.f = ar.take<float>((size_t)M * width * 4);
     } else {
-        s.hP = carve_planes(ar, (size_t)M, (size_t)width, precision);
-        s.aP = carve_planes(ar, (size_t)M, (size_t)width, precision);
-        s.fP = carve_planes(ar, (size_t)M, (size_t)width * 4, precision);
-        s.any = s.fP;                                // free between blocks: the towers' other GEMMs run before / after the stack
+        s.h.p = carve_planes(ar, (size_t)M, (size_t)width, precision);
+        s.a.p = carve_planes(ar, (size_t)M, (size_t)width, precision);
+        s.f.p = carve_planes(ar, (size_t)M, (size_t)width * 4, precision);
+        s.any = s.f.p;                               // free between blocks: the towers' other GEMMs run before / after the stack
     }
     return s;
 }
@@ -75,12 +94,86 @@ int linear_any(const xmh_linear& l, const float* A, int64_t lda, const float* re
     const int64_t N = l.n, K = l.k;
     if (precision != kPrecExact && planes_layer(l) && scratch.hi && lda % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0) {
         xmh::Planes p{scratch.hi, precision == kPrecParity ? scratch.lo : nullptr, K};
-        int rc = xmh::split_planes(A, lda, M, K, p, xmh::as_stream(st));
-        if (rc) return rc;
+        XMH_TRY(xmh::split_planes(A, lda, M, K, p, xmh::as_stream(st)));
         return linear_p(l, p, residual, ldr, C, ldc, nullptr, M, act, precision, st);
     }
     if (!l.w_f32) return xmh::fail(-22, "xmh forward: a %lld x %lld layer needs its fp32 weight for this shape / precision", (long long)N, (long long)K);
     return xmh_gemm_nt_f32(A, lda, l.w_f32, K, l.bias, residual, ldr, C, ldc, M, N, K, act, precision == kPrecFast ? 1 : 0, st);
+}
+
+// ---- the three stages of the chain, each over Acts: dense rows (ld = D, or the layer's N / K) -----------------------------------
+
+// m_dev (xmh_text_forward_packed_dev): the real row count lives in a device word and `rows` is its upper bound, which sizes the
+// launch -- the row-wise kernels return on the rows behind the real count.  Parity / fast mode only.
+int layernorm(const float* x, const float* gamma, const float* beta, const Act& out, int64_t rows, int D, xmh_stream_t st,
+              const int32_t* m_dev = nullptr) {
+    return xmh::layernorm_planes(x, D, gamma, beta, kLnEps, out.f, out.f ? D : 0, out.p, rows, D, xmh::as_stream(st), m_dev);
+}
+
+// act(in @ W^T + bias) (+ residual [rows, N]) -> out.f [rows, N] and / or out.p: the fp32 MFMA on in.f in exact mode, the fp16 MFMA
+// on in.p otherwise
+int linear(const xmh_linear& l, const Act& in, const float* residual, const Act& out, int64_t rows, int act, int precision, xmh_stream_t st,
+           const int32_t* m_dev = nullptr) {
+    const int64_t ldr = residual ? l.n : 0, ldc = out.f ? l.n : 0;
+    if (precision == kPrecExact) return xmh_gemm_nt_f32(in.f, l.k, l.w_f32, l.k, l.bias, residual, ldr, out.f, ldc, rows, l.n, l.k, act, 0, st);
+    return linear_p(l, in.p, residual, ldr, out.f, ldc, out.p.hi ? &out.p : nullptr, rows, act, precision, st, m_dev);
+}
+
+// What every launch of one block stack shares.  offs (device, [B + 1]): packed sequences (xmh_text_forward_packed) -- the row-wise
+// kernels see the packed rows, attention finds sequence b at rows [offs[b], offs[b + 1]).
+struct Stack {
+    int D, heads;
+    int64_t B;
+    int L, causal;
+    const uint8_t* kpm;
+    const int32_t* offs;
+    int precision;
+    xmh_stream_t st;
+};
+
+int attention(const Stack& c, const float* qkv, const Act& out) {
+    return xmh::attention_planes(qkv, c.B, c.L, c.heads, c.D / c.heads, c.causal, c.kpm, out.f, out.p, c.precision != kPrecExact,
+                                 xmh::as_stream(c.st), c.offs);
+}
+
+// ---- the residual block -----------------------------------------------------------------------------------------------------
+
+struct BlockBufs {
+    const float* x_in;                               // the residual stream in front of the block,
+    float *x_mid, *x_out;                            // between its halves and behind it (may all be one buffer)
+    float* qkv;
+    Act ln1, attn, ln2, fc;
+    float* fc_pre;                                   // null: QuickGELU rides the c_fc epilogue; else c_fc's output is kept and QuickGELU is a pass of its own
+};
+
+int check_block(const xmh_clip_block& b, int i, int D, int precision, const int32_t* m_dev) {
+    if (!xmh::block_fits(b, D)) return xmh::fail(-22, "xmh forward: block %d has layer shapes that do not fit width %d", i, D);
+    if (precision == kPrecExact) {
+        if (m_dev) return xmh::fail(-95, "xmh forward: a device-side row count needs parity or fast mode");
+        if (!b.qkv.w_f32 || !b.out.w_f32 || !b.fc.w_f32 || !b.proj.w_f32) return xmh::fail(-22, "xmh forward: block %d lacks fp32 weights (exact mode)", i);
+    } else if (!planes_layer(b.qkv) || !planes_layer(b.out) || !planes_layer(b.fc) || !planes_layer(b.proj)) {
+        return xmh::fail(-22, "xmh forward: block %d lacks fp16 weights (w_hi) for width %d", i, D);
+    }
+    return 0;
+}
+
+int attention_half(const Stack& c, const xmh_clip_block& b, const BlockBufs& u, int64_t rows, const int32_t* m_dev) {
+    XMH_TRY(layernorm(u.x_in, b.ln1_w, b.ln1_b, u.ln1, rows, c.D, c.st, m_dev));
+    XMH_TRY(linear(b.qkv, u.ln1, nullptr, Act{u.qkv}, rows, kActNone, c.precision, c.st, m_dev));
+    return attention(c, u.qkv, u.attn);
+}
+
+// everything behind the attention works row by row, so `rows` may be any subset of the stack's rows (TailRows)
+int rowwise_half(const Stack& c, const xmh_clip_block& b, const BlockBufs& u, int64_t rows, const int32_t* m_dev) {
+    XMH_TRY(linear(b.out, u.attn, u.x_in, Act{u.x_mid}, rows, kActNone, c.precision, c.st, m_dev));
+    XMH_TRY(layernorm(u.x_mid, b.ln2_w, b.ln2_b, u.ln2, rows, c.D, c.st, m_dev));
+    if (u.fc_pre) {
+        XMH_TRY(linear(b.fc, u.ln2, nullptr, Act{u.fc_pre}, rows, kActNone, c.precision, c.st, m_dev));
+        XMH_TRY(xmh::quickgelu_planes(u.fc_pre, rows, 4 * c.D, u.fc.f, u.fc.p, xmh::as_stream(c.st)));
+    } else {
+        XMH_TRY(linear(b.fc, u.ln2, nullptr, u.fc, rows, kActQuickGelu, c.precision, c.st, m_dev));
+    }
+    return linear(b.proj, u.fc, u.x_mid, Act{u.x_out}, rows, kActNone, c.precision, c.st, m_dev);
 }
 
 // Which rows of the stack's output the caller keeps.  A tower that returns one embedding per sequence (cls / EOS, return_patches =
@@ -93,172 +186,58 @@ struct TailRows {
     float* x_tail = nullptr;       // [B, width] fp32: the kept rows of the stack's output (x itself is then stale in the last block)
 };
 
-// offs / M_packed: packed sequences (xmh_text_forward_packed) -- the row-wise kernels see M_packed rows, attention finds sequence b at
-// rows [offs[b], offs[b + 1])
-int run_blocks(const xmh_clip_block* blocks, int layers, int width, int heads, float* x, int64_t B, int L, int causal,
-               const uint8_t* kpm, int precision, const BlockScratch& s, xmh_stream_t st, const int32_t* offs = nullptr, int64_t M_packed = 0,
+// M_packed: the row count of packed sequences (c.offs), or with m_dev its upper bound B * L
+int run_blocks(const xmh_clip_block* blocks, int layers, const Stack& c, float* x, const BlockScratch& s, int64_t M_packed = 0,
                TailRows tail = TailRows{}, const int32_t* m_dev = nullptr) {
-    // m_dev (xmh_text_forward_packed_dev): the packed row count lives in a device word; M_packed is then its upper bound (B * L), which
-    // sizes the launches -- the row-wise kernels return on the rows behind the real count.  Parity / fast mode only.
     static const bool tail_off = xmh_experiment_env("XMH_TAIL_ROWS") && atoi(xmh_experiment_env("XMH_TAIL_ROWS")) == 0;      // A/B switch: 0 = the full last block + a gather
+    const int D = c.D;
     const bool want_tail = tail.mode != 0;
-    const bool tail_fused = want_tail && !tail_off && width % 2 == 0;
+    const bool tail_fused = want_tail && !tail_off && D % 2 == 0;
     // rows of a float-typed [*, cols] view (fp16 planes: two halves per float) -> the B kept rows
     auto keep_rows = [&](const void* src, int64_t ld_f, void* dst, int cols_f) -> int {
-        if (tail.mode == 3) return xmh::gather_last_rows(static_cast<const float*>(src), ld_f, offs, static_cast<float*>(dst), B, cols_f, xmh::as_stream(st));
-        return xmh_gather_rows(static_cast<const float*>(src), ld_f, tail.mode == 2 ? tail.idx : nullptr, 0, L, static_cast<float*>(dst), B, cols_f, st);
+        if (tail.mode == 3) return xmh::gather_last_rows(static_cast<const float*>(src), ld_f, c.offs, static_cast<float*>(dst), c.B, cols_f, xmh::as_stream(c.st));
+        return xmh_gather_rows(static_cast<const float*>(src), ld_f, tail.mode == 2 ? tail.idx : nullptr, 0, c.L, static_cast<float*>(dst), c.B, cols_f, c.st);
     };
-    const int64_t M = offs ? M_packed : B * L;
-    const int D = width;
-    hipStream_t hs = xmh::as_stream(st);
-    const xmh::Planes none{nullptr, nullptr, 0};
+    auto keep_act = [&](const Act& src, const Act& dst) -> int {      // whichever of the fp32 buffer and the planes the mode keeps
+        if (src.f) XMH_TRY(keep_rows(src.f, D, dst.f, D));
+        if (src.p.hi) XMH_TRY(keep_rows(src.p.hi, src.p.ld / 2, dst.p.hi, D / 2));
+        if (src.p.lo) XMH_TRY(keep_rows(src.p.lo, src.p.ld / 2, dst.p.lo, D / 2));
+        return 0;
+    };
+    const int64_t M = c.offs ? M_packed : c.B * c.L;
+    const BlockBufs every{x, x, x, s.qkv, s.h, s.a, s.h, s.f, nullptr};
     for (int i = 0; i < layers; ++i) {
         const xmh_clip_block& b = blocks[i];
-        if (b.qkv.n != 3 * D || b.qkv.k != D || b.out.n != D || b.out.k != D || b.fc.k != D || b.fc.n != 4 * D || b.proj.n != D || b.proj.k != b.fc.n)
-            return xmh::fail(-22, "xmh forward: block %d has layer shapes that do not fit width %d", i, D);
-        int rc;
-        if (precision == kPrecExact) {
-            if (m_dev) return xmh::fail(-95, "xmh forward: a device-side row count needs parity or fast mode");
-            if (!b.qkv.w_f32 || !b.out.w_f32 || !b.fc.w_f32 || !b.proj.w_f32) return xmh::fail(-22, "xmh forward: block %d lacks fp32 weights (exact mode)", i);
-            rc = xmh_layernorm_f32(x, D, b.ln1_w, b.ln1_b, kLnEps, s.h, D, M, D, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(s.h, D, b.qkv.w_f32, D, b.qkv.bias, nullptr, 0, s.qkv, 3 * D, M, 3 * D, D, kActNone, 0, st);
-            if (rc) return rc;
-            rc = offs ? xmh::attention_planes(s.qkv, B, L, heads, D / heads, causal, kpm, s.a, none, false, hs, offs)
-                      : xmh_attention_f32(s.qkv, B, L, heads, D / heads, causal, kpm, s.a, st);
-            if (rc) return rc;
-            if (tail_fused && i == layers - 1) {             // the last block's row-wise half on the kept rows only
-                float* xt = tail.x_tail;
-                if ((rc = keep_rows(s.a, D, s.h, D))) return rc;
-                if ((rc = keep_rows(x, D, xt, D))) return rc;
-                if ((rc = xmh_gemm_nt_f32(s.h, D, b.out.w_f32, D, b.out.bias, xt, D, xt, D, B, D, D, kActNone, 0, st))) return rc;
-                if ((rc = xmh_layernorm_f32(xt, D, b.ln2_w, b.ln2_b, kLnEps, s.a, D, B, D, st))) return rc;
-                if ((rc = xmh_gemm_nt_f32(s.a, D, b.fc.w_f32, D, b.fc.bias, nullptr, 0, s.f, 4 * D, B, 4 * D, D, kActQuickGelu, 0, st))) return rc;
-                if ((rc = xmh_gemm_nt_f32(s.f, 4 * D, b.proj.w_f32, 4 * D, b.proj.bias, xt, D, xt, D, B, D, 4 * D, kActNone, 0, st))) return rc;
-                return 0;
-            }
-            rc = xmh_gemm_nt_f32(s.a, D, b.out.w_f32, D, b.out.bias, x, D, x, D, M, D, D, kActNone, 0, st);
-            if (rc) return rc;
-            rc = xmh_layernorm_f32(x, D, b.ln2_w, b.ln2_b, kLnEps, s.h, D, M, D, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(s.h, D, b.fc.w_f32, D, b.fc.bias, nullptr, 0, s.f, 4 * D, M, 4 * D, D, kActQuickGelu, 0, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(s.f, 4 * D, b.proj.w_f32, 4 * D, b.proj.bias, x, D, x, D, M, D, 4 * D, kActNone, 0, st);
-            if (rc) return rc;
-            continue;
-        }
-        if (!planes_layer(b.qkv) || !planes_layer(b.out) || !planes_layer(b.fc) || !planes_layer(b.proj))
-            return xmh::fail(-22, "xmh forward: block %d lacks fp16 weights (w_hi) for width %d", i, D);
-        rc = xmh::layernorm_planes(x, D, b.ln1_w, b.ln1_b, kLnEps, nullptr, 0, s.hP, M, D, hs, m_dev);
-        if (rc) return rc;
-        rc = linear_p(b.qkv, s.hP, nullptr, 0, s.qkv, 3 * D, nullptr, M, kActNone, precision, st, m_dev);
-        if (rc) return rc;
-        rc = xmh::attention_planes(s.qkv, B, L, heads, D / heads, causal, kpm, nullptr, s.aP, true, hs, offs);
-        if (rc) return rc;
-        if (tail_fused && i == layers - 1) {                 // the last block's row-wise half on the kept rows only
+        XMH_TRY(check_block(b, i, D, c.precision, m_dev));
+        XMH_TRY(attention_half(c, b, every, M, m_dev));
+        if (tail_fused && i == layers - 1) {                 // the last block's row-wise half on the kept rows only (h is free: a -> h)
             float* xt = tail.x_tail;
-            const xmh::Planes hc{s.hP.hi, s.hP.lo, D}, ac{s.aP.hi, s.aP.lo, D}, fc{s.fP.hi, s.fP.lo, 4 * (int64_t)D};
-            if ((rc = keep_rows(s.aP.hi, s.aP.ld / 2, hc.hi, D / 2))) return rc;       // attention output planes -> the kept rows (hP is free)
-            if (s.aP.lo && (rc = keep_rows(s.aP.lo, s.aP.ld / 2, hc.lo, D / 2))) return rc;
-            if ((rc = keep_rows(x, D, xt, D))) return rc;
-            if ((rc = linear_p(b.out, hc, xt, D, xt, D, nullptr, B, kActNone, precision, st))) return rc;
-            if ((rc = xmh::layernorm_planes(xt, D, b.ln2_w, b.ln2_b, kLnEps, nullptr, 0, ac, B, D, hs))) return rc;
-            if ((rc = linear_p(b.fc, ac, nullptr, 0, nullptr, 0, &fc, B, kActQuickGelu, precision, st))) return rc;
-            if ((rc = linear_p(b.proj, fc, xt, D, xt, D, nullptr, B, kActNone, precision, st))) return rc;
-            return 0;
+            XMH_TRY(keep_act(s.a, s.h));
+            XMH_TRY(keep_rows(x, D, xt, D));
+            const BlockBufs kept{xt, xt, xt, nullptr, Act{}, s.h, s.a, s.f, nullptr};
+            return rowwise_half(c, b, kept, c.B, nullptr);
         }
-        rc = linear_p(b.out, s.aP, x, D, x, D, nullptr, M, kActNone, precision, st, m_dev);
-        if (rc) return rc;
-        rc = xmh::layernorm_planes(x, D, b.ln2_w, b.ln2_b, kLnEps, nullptr, 0, s.hP, M, D, hs, m_dev);
-        if (rc) return rc;
-        rc = linear_p(b.fc, s.hP, nullptr, 0, nullptr, 0, &s.fP, M, kActQuickGelu, precision, st, m_dev);
-        if (rc) return rc;
-        rc = linear_p(b.proj, s.fP, x, D, x, D, nullptr, M, kActNone, precision, st, m_dev);
-        if (rc) return rc;
+        XMH_TRY(rowwise_half(c, b, every, M, m_dev));
     }
-    (void)none;
     if (want_tail) return keep_rows(x, D, tail.x_tail, D);    // no block ran its tail on the kept rows (switched off, or no layers): gather them
     return 0;
 }
 
-// ---- the block stack with saved activations ----------------------------------------------------------------
-// What a backward pass of ResidualAttentionBlock (models/CLIP/model.py:167-197) needs from the forward, kept per layer instead
-// of living in the shared scratch: one record of 16 * M * D floats per layer, fields in this order (xmh.h, xmh_clip_saved):
-//   x_in [M,D] | ln1 [M,D] | qkv [M,3D] | attn [M,D] | x_mid [M,D] | ln2 [M,D] | fc_pre [M,4D] | fc_act [M,4D]
-// Same kernels, same order and the same numbers as run_blocks: the producers write their fp32 result next to the operand planes
-// (LayerNorm, attention), the GEMMs write straight into the record, the residual stream hops from record to record (x_in of
-// layer i+1 is the output of layer i; the last layer writes x), and QuickGELU runs as its own elementwise pass between c_fc and
-// c_proj (xmh::quickgelu_planes: the epilogue's function on the stored pre-activation) so that both sides of it are kept.
-struct SavedRecord {
-    float *x_in, *ln1, *qkv, *attn, *x_mid, *ln2, *fc_pre, *fc_act;
-};
-
-constexpr int kSavedFloatsPerElement = 16;           // per (token, channel): 1 + 1 + 3 + 1 + 1 + 1 + 4 + 4
-
-SavedRecord saved_record(float* base, int layer, int64_t M, int D) {
-    float* p = base + (size_t)layer * kSavedFloatsPerElement * (size_t)M * D;
-    const size_t md = (size_t)M * D;
-    SavedRecord r;
-    r.x_in = p; r.ln1 = p + md; r.qkv = p + 2 * md; r.attn = p + 5 * md; r.x_mid = p + 6 * md; r.ln2 = p + 7 * md;
-    r.fc_pre = p + 8 * md; r.fc_act = p + 12 * md;
-    return r;
-}
-
-int run_blocks_saved(const xmh_clip_block* blocks, int layers, int width, int heads, float* x, int64_t B, int L, int causal,
-                     const uint8_t* kpm, int precision, const BlockScratch& s, float* saved, xmh_stream_t st) {
-    const int64_t M = B * L;
-    const int D = width;
-    hipStream_t hs = xmh::as_stream(st);
-    const xmh::Planes none{nullptr, nullptr, 0};
+// the stack with every layer's record kept: the residual stream hops from record to record
+int run_blocks_saved(const xmh_clip_block* blocks, int layers, const Stack& c, float* x, const BlockScratch& s, float* saved) {
+    const int64_t M = c.B * c.L;
     if (layers > 0) {
-        hipError_t e = hipMemcpyAsync(saved_record(saved, 0, M, D).x_in, x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, hs);
+        hipError_t e = hipMemcpyAsync(xmh::saved_record(saved, 0, M, c.D).x_in, x, (size_t)M * c.D * sizeof(float), hipMemcpyDeviceToDevice, xmh::as_stream(c.st));
         if (e != hipSuccess) return xmh::fail(-5, "xmh_clip_blocks_forward_saved: copy of x failed: %s", hipGetErrorString(e));
     }
     for (int i = 0; i < layers; ++i) {
         const xmh_clip_block& b = blocks[i];
-        if (b.qkv.n != 3 * D || b.qkv.k != D || b.out.n != D || b.out.k != D || b.fc.k != D || b.fc.n != 4 * D || b.proj.n != D || b.proj.k != b.fc.n)
-            return xmh::fail(-22, "xmh forward: block %d has layer shapes that do not fit width %d", i, D);
-        const SavedRecord r = saved_record(saved, i, M, D);
-        float* x_out = i + 1 < layers ? saved_record(saved, i + 1, M, D).x_in : x;
-        int rc;
-        if (precision == kPrecExact) {
-            if (!b.qkv.w_f32 || !b.out.w_f32 || !b.fc.w_f32 || !b.proj.w_f32) return xmh::fail(-22, "xmh forward: block %d lacks fp32 weights (exact mode)", i);
-            rc = xmh_layernorm_f32(r.x_in, D, b.ln1_w, b.ln1_b, kLnEps, r.ln1, D, M, D, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(r.ln1, D, b.qkv.w_f32, D, b.qkv.bias, nullptr, 0, r.qkv, 3 * D, M, 3 * D, D, kActNone, 0, st);
-            if (rc) return rc;
-            rc = xmh_attention_f32(r.qkv, B, L, heads, D / heads, causal, kpm, r.attn, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(r.attn, D, b.out.w_f32, D, b.out.bias, r.x_in, D, r.x_mid, D, M, D, D, kActNone, 0, st);
-            if (rc) return rc;
-            rc = xmh_layernorm_f32(r.x_mid, D, b.ln2_w, b.ln2_b, kLnEps, r.ln2, D, M, D, st);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(r.ln2, D, b.fc.w_f32, D, b.fc.bias, nullptr, 0, r.fc_pre, 4 * D, M, 4 * D, D, kActNone, 0, st);
-            if (rc) return rc;
-            rc = xmh::quickgelu_planes(r.fc_pre, M, 4 * D, r.fc_act, none, hs);
-            if (rc) return rc;
-            rc = xmh_gemm_nt_f32(r.fc_act, 4 * D, b.proj.w_f32, 4 * D, b.proj.bias, r.x_mid, D, x_out, D, M, D, 4 * D, kActNone, 0, st);
-            if (rc) return rc;
-            continue;
-        }
-        if (!planes_layer(b.qkv) || !planes_layer(b.out) || !planes_layer(b.fc) || !planes_layer(b.proj))
-            return xmh::fail(-22, "xmh forward: block %d lacks fp16 weights (w_hi) for width %d", i, D);
-        rc = xmh::layernorm_planes(r.x_in, D, b.ln1_w, b.ln1_b, kLnEps, r.ln1, D, s.hP, M, D, hs);
-        if (rc) return rc;
-        rc = linear_p(b.qkv, s.hP, nullptr, 0, r.qkv, 3 * D, nullptr, M, kActNone, precision, st);
-        if (rc) return rc;
-        rc = xmh::attention_planes(r.qkv, B, L, heads, D / heads, causal, kpm, r.attn, s.aP, true, hs);
-        if (rc) return rc;
-        rc = linear_p(b.out, s.aP, r.x_in, D, r.x_mid, D, nullptr, M, kActNone, precision, st);
-        if (rc) return rc;
-        rc = xmh::layernorm_planes(r.x_mid, D, b.ln2_w, b.ln2_b, kLnEps, r.ln2, D, s.hP, M, D, hs);
-        if (rc) return rc;
-        rc = linear_p(b.fc, s.hP, nullptr, 0, r.fc_pre, 4 * D, nullptr, M, kActNone, precision, st);
-        if (rc) return rc;
-        rc = xmh::quickgelu_planes(r.fc_pre, M, 4 * D, r.fc_act, s.fP, hs);
-        if (rc) return rc;
-        rc = linear_p(b.proj, s.fP, r.x_mid, D, x_out, D, nullptr, M, kActNone, precision, st);
-        if (rc) return rc;
+        XMH_TRY(check_block(b, i, c.D, c.precision, nullptr));
+        const xmh::SavedRecord<float> r = xmh::saved_record(saved, i, M, c.D);
+        float* x_out = i + 1 < layers ? xmh::saved_record(saved, i + 1, M, c.D).x_in : x;
+        const BlockBufs u{r.x_in, r.x_mid, x_out, r.qkv, Act{r.ln1, s.h.p}, Act{r.attn, s.a.p}, Act{r.ln2, s.h.p}, Act{r.fc_act, s.f.p}, r.fc_pre};
+        XMH_TRY(attention_half(c, b, u, M, nullptr));
+        XMH_TRY(rowwise_half(c, b, u, M, nullptr));
     }
     return 0;
 }
@@ -292,18 +271,26 @@ TowerScratch carve_tower(Arena& ar, int64_t B, int L, int width, int conv_k, int
 // LayerNorm + projection of `rows` rows (the tail of both towers): planes straight out of the LayerNorm when the layer allows
 int ln_linear(const float* x, int64_t rows, int D, const float* gamma, const float* beta, const xmh_linear& l, float* ytmp, float* C,
               int precision, const BlockScratch& blk, xmh_stream_t st) {
-    if (precision != kPrecExact && planes_layer(l) && blk.hP.hi) {
-        int rc = xmh::layernorm_planes(x, D, gamma, beta, kLnEps, nullptr, 0, blk.hP, rows, D, xmh::as_stream(st));
-        if (rc) return rc;
-        return linear_p(l, blk.hP, nullptr, 0, C, l.n, nullptr, rows, kActNone, precision, st);
+    if (precision != kPrecExact && planes_layer(l) && blk.h.p.hi) {
+        XMH_TRY(layernorm(x, gamma, beta, blk.h, rows, D, st));
+        return linear(l, blk.h, nullptr, Act{C}, rows, kActNone, precision, st);
     }
-    int rc = xmh_layernorm_f32(x, D, gamma, beta, kLnEps, ytmp, D, rows, D, st);
-    if (rc) return rc;
+    XMH_TRY(xmh_layernorm_f32(x, D, gamma, beta, kLnEps, ytmp, D, rows, D, st));
     return linear_any(l, ytmp, D, nullptr, 0, C, l.n, rows, kActNone, precision, blk.any, st);
 }
 
 int check_precision(int precision) {
     if (precision != kPrecParity && precision != kPrecFast && precision != kPrecExact) return xmh::fail(-22, "xmh forward: precision must be 0 (parity), 1 (fast) or 2 (exact), got %d", precision);
+    return 0;
+}
+
+// what the text entry points check alike: the token count against the positional embedding (packed attention: 64 keys at most) and
+// the tower's own shapes
+int check_text(const char* who, const xmh_text_weights* w, int L, bool packed) {
+    if (L <= 0 || L > w->context || (packed && L > 64))
+        return packed ? xmh::fail(-22, "%s: %d tokens (positional embedding %d, packed attention 64)", who, L, w->context)
+                      : xmh::fail(-22, "%s: %d tokens, the positional embedding holds %d", who, L, w->context);
+    if (w->heads <= 0 || w->width % w->heads || w->proj.n != w->out_dim || w->proj.k != w->width) return xmh::fail(-22, "%s: shapes do not fit the tower", who);
     return 0;
 }
 
@@ -320,26 +307,26 @@ extern "C" int xmh_clip_blocks_forward(const xmh_clip_block* blocks, int layers,
                                        int causal, const uint8_t* key_padding_mask, int precision, void* workspace,
                                        size_t workspace_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_clip_blocks_forward");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!blocks || !x || !workspace || layers < 0 || heads <= 0 || width % heads) return xmh::fail(-22, "xmh_clip_blocks_forward: bad arguments");
     Arena ar(workspace);
     const BlockScratch s = carve_blocks(ar, B * L, width, precision);
     if (ar.used > workspace_bytes)
         return xmh::fail(-12, "xmh_clip_blocks_forward: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
-    return run_blocks(blocks, layers, width, heads, x, B, L, causal, key_padding_mask, precision, s, stream);
+    return run_blocks(blocks, layers, Stack{width, heads, B, L, causal, key_padding_mask, nullptr, precision, stream}, x, s);
 }
 
 extern "C" size_t xmh_clip_saved_bytes(int64_t B, int L, int width, int layers) {
     if (B <= 0 || L <= 0 || width <= 0 || layers <= 0) return 0;
-    return (size_t)layers * kSavedFloatsPerElement * (size_t)B * L * width * sizeof(float);
+    return xmh::saved_record_bytes(layers, B * L, width);
 }
 
 extern "C" int xmh_clip_blocks_forward_saved(const xmh_clip_block* blocks, int layers, int width, int heads, float* x, int64_t B, int L,
                                              int causal, const uint8_t* key_padding_mask, int precision, void* workspace,
                                              size_t workspace_bytes, float* saved, size_t saved_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_clip_blocks_forward_saved");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!blocks || !x || !workspace || !saved || layers < 0 || heads <= 0 || width % heads)
         return xmh::fail(-22, "xmh_clip_blocks_forward_saved: bad arguments");
@@ -350,13 +337,13 @@ extern "C" int xmh_clip_blocks_forward_saved(const xmh_clip_block* blocks, int l
     const BlockScratch s = carve_blocks(ar, B * L, width, precision);
     if (ar.used > workspace_bytes)
         return xmh::fail(-12, "xmh_clip_blocks_forward_saved: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
-    return run_blocks_saved(blocks, layers, width, heads, x, B, L, causal, key_padding_mask, precision, s, saved, stream);
+    return run_blocks_saved(blocks, layers, Stack{width, heads, B, L, causal, key_padding_mask, nullptr, precision, stream}, x, s, saved);
 }
 
 extern "C" int xmh_vit_b32_forward(const xmh_vit_weights* w, const float* image, int64_t B, int precision, float* out_cls,
                                    float* out_tokens, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_vit_b32_forward (image tower)");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!w || !image || !workspace || (!out_cls && !out_tokens)) return xmh::fail(-22, "xmh_vit_b32_forward: bad arguments");
     if (w->patch <= 0 || w->resolution % w->patch || w->heads <= 0 || w->width % w->heads)
@@ -368,29 +355,21 @@ extern "C" int xmh_vit_b32_forward(const xmh_vit_weights* w, const float* image,
     const TowerScratch t = carve_tower(ar, B, L, D, conv_k, out_tokens ? w->out_dim : 0, precision);
     if (ar.used > workspace_bytes) return xmh::fail(-12, "xmh_vit_b32_forward: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
     const int64_t M = B * L;
-    int rc;
     if (t.colsP.hi && planes_layer(w->conv1)) {
-        rc = xmh::im2col_planes(image, B, 3, w->resolution, w->patch, nullptr, t.colsP, xmh::as_stream(stream));
-        if (rc) return rc;
-        rc = linear_p(w->conv1, t.colsP, nullptr, 0, t.patches, D, nullptr, B * P, kActNone, precision, stream);
+        XMH_TRY(xmh::im2col_planes(image, B, 3, w->resolution, w->patch, nullptr, t.colsP, xmh::as_stream(stream)));
+        XMH_TRY(linear_p(w->conv1, t.colsP, nullptr, 0, t.patches, D, nullptr, B * P, kActNone, precision, stream));
     } else {
         if (!t.cols) return xmh::fail(-22, "xmh_vit_b32_forward: conv1 lacks fp16 weights (w_hi) for a %d-wide patch row", conv_k);
-        rc = xmh_im2col_patch(image, B, 3, w->resolution, w->patch, t.cols, stream);
-        if (rc) return rc;
-        rc = linear_any(w->conv1, t.cols, conv_k, nullptr, 0, t.patches, D, B * P, kActNone, precision, t.blk.any, stream);
+        XMH_TRY(xmh_im2col_patch(image, B, 3, w->resolution, w->patch, t.cols, stream));
+        XMH_TRY(linear_any(w->conv1, t.cols, conv_k, nullptr, 0, t.patches, D, B * P, kActNone, precision, t.blk.any, stream));
     }
-    if (rc) return rc;
-    rc = xmh_vit_assemble(t.patches, w->cls, w->pos, w->ln_pre_w, w->ln_pre_b, kLnEps, t.x, B, P, D, stream);
-    if (rc) return rc;
+    XMH_TRY(xmh_vit_assemble(t.patches, w->cls, w->pos, w->ln_pre_w, w->ln_pre_b, kLnEps, t.x, B, P, D, stream));
     TailRows tail;
     if (!out_tokens) { tail.mode = 1; tail.x_tail = t.row_a; }      // the cls row is all the caller keeps
-    rc = run_blocks(w->blocks, w->layers, D, w->heads, t.x, B, L, 0, nullptr, precision, t.blk, stream, nullptr, 0, tail);
-    if (rc) return rc;
+    XMH_TRY(run_blocks(w->blocks, w->layers, Stack{D, w->heads, B, L, 0, nullptr, nullptr, precision, stream}, t.x, t.blk, 0, tail));
     if (out_tokens) {                                 // return_patches: ln_post + proj on every token (model.py:257-265)
-        rc = ln_linear(t.x, M, D, w->ln_post_w, w->ln_post_b, w->proj, t.y, out_tokens, precision, t.blk, stream);
-        if (rc) return rc;
-        if (out_cls) rc = xmh_gather_rows(out_tokens, w->out_dim, nullptr, 0, L, out_cls, B, w->out_dim, stream);
-        return rc;
+        XMH_TRY(ln_linear(t.x, M, D, w->ln_post_w, w->ln_post_b, w->proj, t.y, out_tokens, precision, t.blk, stream));
+        return out_cls ? xmh_gather_rows(out_tokens, w->out_dim, nullptr, 0, L, out_cls, B, w->out_dim, stream) : 0;
     }
     return ln_linear(t.row_a, B, D, w->ln_post_w, w->ln_post_b, w->proj, t.row_b, out_cls, precision, t.blk, stream);
 }
@@ -399,28 +378,23 @@ extern "C" int xmh_text_forward(const xmh_text_weights* w, const int64_t* ids, c
                                 int precision, float* out_eos, float* out_tokens, int32_t* eos_index, void* workspace,
                                 size_t workspace_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_text_forward (text tower)");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!w || !ids || !workspace || (!out_eos && !out_tokens)) return xmh::fail(-22, "xmh_text_forward: bad arguments");
-    if (L <= 0 || L > w->context) return xmh::fail(-22, "xmh_text_forward: %d tokens, the positional embedding holds %d", L, w->context);
+    XMH_TRY(check_text("xmh_text_forward", w, L, false));
     const int D = w->width;
-    if (w->heads <= 0 || D % w->heads || w->proj.n != w->out_dim || w->proj.k != D) return xmh::fail(-22, "xmh_text_forward: shapes do not fit the tower");
     Arena ar(workspace);
     const TowerScratch t = carve_tower(ar, B, L, D, 0, out_tokens ? w->out_dim : 0, precision);
     if (ar.used > workspace_bytes) return xmh::fail(-12, "xmh_text_forward: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
     const int64_t M = B * L;
     int32_t* eos = eos_index ? eos_index : t.eos;
-    int rc = xmh_text_embed(ids, w->tok_emb, w->pos, t.x, eos, B, L, D, w->vocab, stream);
-    if (rc) return rc;
+    XMH_TRY(xmh_text_embed(ids, w->tok_emb, w->pos, t.x, eos, B, L, D, w->vocab, stream));
     TailRows tail;
     if (!out_tokens) { tail.mode = 2; tail.idx = eos; tail.x_tail = t.row_a; }      // only the EOS row of every caption is kept
-    rc = run_blocks(w->blocks, w->layers, D, w->heads, t.x, B, L, 1, key_padding_mask, precision, t.blk, stream, nullptr, 0, tail);
-    if (rc) return rc;
+    XMH_TRY(run_blocks(w->blocks, w->layers, Stack{D, w->heads, B, L, 1, key_padding_mask, nullptr, precision, stream}, t.x, t.blk, 0, tail));
     if (out_tokens) {
-        rc = ln_linear(t.x, M, D, w->ln_final_w, w->ln_final_b, w->proj, t.y, out_tokens, precision, t.blk, stream);
-        if (rc) return rc;
-        if (out_eos) rc = xmh_gather_rows(out_tokens, w->out_dim, eos, 0, L, out_eos, B, w->out_dim, stream);
-        return rc;
+        XMH_TRY(ln_linear(t.x, M, D, w->ln_final_w, w->ln_final_b, w->proj, t.y, out_tokens, precision, t.blk, stream));
+        return out_eos ? xmh_gather_rows(out_tokens, w->out_dim, eos, 0, L, out_eos, B, w->out_dim, stream) : 0;
     }
     return ln_linear(t.row_a, B, D, w->ln_final_w, w->ln_final_b, w->proj, t.row_b, out_eos, precision, t.blk, stream);
 }
@@ -433,24 +407,20 @@ extern "C" int xmh_text_forward(const xmh_text_weights* w, const int64_t* ids, c
 extern "C" int xmh_text_forward_packed(const xmh_text_weights* w, const int64_t* ids, const int32_t* row_offsets, int64_t total_rows, int64_t B,
                                        int L, int precision, float* out_eos, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_text_forward_packed (text tower)");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!w || !ids || !row_offsets || !workspace || !out_eos) return xmh::fail(-22, "xmh_text_forward_packed: bad arguments");
-    if (L <= 0 || L > w->context || L > 64) return xmh::fail(-22, "xmh_text_forward_packed: %d tokens (positional embedding %d, packed attention 64)", L, w->context);
+    XMH_TRY(check_text("xmh_text_forward_packed", w, L, true));
     if (total_rows < B || total_rows > B * L) return xmh::fail(-22, "xmh_text_forward_packed: %lld rows for %lld captions of at most %d tokens", (long long)total_rows, (long long)B, L);
     const int D = w->width;
-    if (w->heads <= 0 || D % w->heads || w->proj.n != w->out_dim || w->proj.k != D) return xmh::fail(-22, "xmh_text_forward_packed: shapes do not fit the tower");
     Arena ar(workspace);
     const TowerScratch t = carve_tower(ar, B, L, D, 0, 0, precision);      // sized for B * L rows: total_rows <= that
     if (ar.used > workspace_bytes) return xmh::fail(-12, "xmh_text_forward_packed: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
-    hipStream_t hs = xmh::as_stream(stream);
-    int rc = xmh::text_embed_packed(ids, w->tok_emb, w->pos, t.x, row_offsets, B, L, D, w->vocab, hs);
-    if (rc) return rc;
+    XMH_TRY(xmh::text_embed_packed(ids, w->tok_emb, w->pos, t.x, row_offsets, B, L, D, w->vocab, xmh::as_stream(stream)));
     TailRows tail;
     tail.mode = 3;
     tail.x_tail = t.row_a;
-    rc = run_blocks(w->blocks, w->layers, D, w->heads, t.x, B, L, 1, nullptr, precision, t.blk, stream, row_offsets, total_rows, tail);
-    if (rc) return rc;
+    XMH_TRY(run_blocks(w->blocks, w->layers, Stack{D, w->heads, B, L, 1, nullptr, row_offsets, precision, stream}, t.x, t.blk, total_rows, tail));
     return ln_linear(t.row_a, B, D, w->ln_final_w, w->ln_final_b, w->proj, t.row_b, out_eos, precision, t.blk, stream);
 }
 
@@ -467,48 +437,37 @@ extern "C" int xmh_text_forward_packed_dev(const xmh_text_weights* w, const int6
                                            int precision, float* out_eos, float* out_tokens, void* workspace, size_t workspace_bytes,
                                            xmh_stream_t stream) {
     XMH_RANGE("xmh_text_forward_packed_dev (text tower)");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (precision == kPrecExact) return xmh::fail(-95, "xmh_text_forward_packed_dev: parity or fast mode only");
     if (B == 0) return 0;
     if (!w || !ids || !workspace || (!out_eos && !out_tokens)) return xmh::fail(-22, "xmh_text_forward_packed_dev: bad arguments");
-    if (L <= 0 || L > w->context || L > 64) return xmh::fail(-22, "xmh_text_forward_packed_dev: %d tokens (positional embedding %d, packed attention 64)", L, w->context);
+    XMH_TRY(check_text("xmh_text_forward_packed_dev", w, L, true));
     const int D = w->width;
-    if (w->heads <= 0 || D % w->heads || w->proj.n != w->out_dim || w->proj.k != D) return xmh::fail(-22, "xmh_text_forward_packed_dev: shapes do not fit the tower");
     Arena ar(workspace);
     const TowerScratch t = carve_tower(ar, B, L, D, 0, out_tokens ? w->out_dim : 0, precision);
     if (ar.used > workspace_bytes) return xmh::fail(-12, "xmh_text_forward_packed_dev: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
     hipStream_t hs = xmh::as_stream(stream);
     const int64_t Mub = B * L;
     const int32_t* m_dev = t.offs + B;
-    int rc = xmh::caption_offsets(ids, key_padding_mask, B, L, t.offs, t.eos, hs);
-    if (rc) return rc;
-    rc = xmh::text_embed_packed(ids, w->tok_emb, w->pos, t.x, t.offs, B, L, D, w->vocab, hs);
-    if (rc) return rc;
+    const Stack c{D, w->heads, B, L, 1, key_padding_mask, t.offs, precision, stream};
+    XMH_TRY(xmh::caption_offsets(ids, key_padding_mask, B, L, t.offs, t.eos, hs));
+    XMH_TRY(xmh::text_embed_packed(ids, w->tok_emb, w->pos, t.x, t.offs, B, L, D, w->vocab, hs));
     if (!out_tokens) {
         TailRows tail;
         if (key_padding_mask) { tail.mode = 0; }                     // the kept rows may run past EOS: the EOS row is picked by index below
         else { tail.mode = 3; tail.x_tail = t.row_a; }
-        rc = run_blocks(w->blocks, w->layers, D, w->heads, t.x, B, L, 1, key_padding_mask, precision, t.blk, stream, t.offs, Mub, tail, m_dev);
-        if (rc) return rc;
-        if (key_padding_mask) {
-            rc = xmh::gather_packed_rows(t.x, D, t.offs, t.eos, t.row_a, B, D, hs);
-            if (rc) return rc;
-        }
+        XMH_TRY(run_blocks(w->blocks, w->layers, c, t.x, t.blk, Mub, tail, m_dev));
+        if (key_padding_mask) XMH_TRY(xmh::gather_packed_rows(t.x, D, t.offs, t.eos, t.row_a, B, D, hs));
         return ln_linear(t.row_a, B, D, w->ln_final_w, w->ln_final_b, w->proj, t.row_b, out_eos, precision, t.blk, stream);
     }
-    rc = run_blocks(w->blocks, w->layers, D, w->heads, t.x, B, L, 1, key_padding_mask, precision, t.blk, stream, t.offs, Mub, TailRows{}, m_dev);
-    if (rc) return rc;
+    XMH_TRY(run_blocks(w->blocks, w->layers, c, t.x, t.blk, Mub, TailRows{}, m_dev));
     // ln_final + text_projection on the packed rows (t.y holds the projected rows, [rows, out_dim] inside its M * width floats), then the
     // reference's padded layout
-    if (!planes_layer(w->proj) || !t.blk.hP.hi || w->out_dim > D) return xmh::fail(-95, "xmh_text_forward_packed_dev: the projection needs fp16 weights and out_dim <= width");
-    rc = xmh::layernorm_planes(t.x, D, w->ln_final_w, w->ln_final_b, kLnEps, nullptr, 0, t.blk.hP, Mub, D, hs, m_dev);
-    if (rc) return rc;
-    rc = linear_p(w->proj, t.blk.hP, nullptr, 0, t.y, w->out_dim, nullptr, Mub, kActNone, precision, stream, m_dev);
-    if (rc) return rc;
-    rc = xmh::unpack_rows(t.y, w->out_dim, t.offs, out_tokens, B, L, w->out_dim, hs);
-    if (rc) return rc;
-    if (out_eos) rc = xmh::gather_packed_rows(t.y, w->out_dim, t.offs, t.eos, out_eos, B, w->out_dim, hs);
-    return rc;
+    if (!planes_layer(w->proj) || !t.blk.h.p.hi || w->out_dim > D) return xmh::fail(-95, "xmh_text_forward_packed_dev: the projection needs fp16 weights and out_dim <= width");
+    XMH_TRY(layernorm(t.x, w->ln_final_w, w->ln_final_b, t.blk.h, Mub, D, stream, m_dev));
+    XMH_TRY(linear(w->proj, t.blk.h, nullptr, Act{t.y}, Mub, kActNone, precision, stream, m_dev));
+    XMH_TRY(xmh::unpack_rows(t.y, w->out_dim, t.offs, out_tokens, B, L, w->out_dim, hs));
+    return out_eos ? xmh::gather_packed_rows(t.y, w->out_dim, t.offs, t.eos, out_eos, B, w->out_dim, hs) : 0;
 }
 
 // ---- hash heads ---------------------------------------------------------------------------------------
@@ -544,7 +503,7 @@ extern "C" size_t xmh_head_workspace_bytes(int64_t B, int E, int precision) {
 extern "C" int xmh_head_dcmht(const xmh_dcmht_head* h, const float* emb, int64_t B, int precision, float* probs, uint32_t* bits,
                               const int64_t* row_index, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
     XMH_RANGE("xmh_head_dcmht");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!h || !emb || !workspace || (!probs && !bits)) return xmh::fail(-22, "xmh_head_dcmht: bad arguments");
     const int E = (int)h->v_proj.k;
@@ -552,28 +511,22 @@ extern "C" int xmh_head_dcmht(const xmh_dcmht_head* h, const float* emb, int64_t
     if (h->v_proj.n != E || h->out_proj.n != E || h->out_proj.k != E || h->fc2.k != E || K2 % 2 || K2 > 2 * E)
         return xmh::fail(-22, "xmh_head_dcmht: layer shapes do not fit (E = %d, fc2 %lld x %lld)", E, (long long)K2, (long long)h->fc2.k);
     HeadScratch s;
-    if (int rc = carve_head(workspace, workspace_bytes, B, E, precision, s, "xmh_head_dcmht")) return rc;
-    int rc = linear_any(h->v_proj, emb, E, nullptr, 0, s.a, E, B, kActNone, precision, s.any, stream);
-    if (rc) return rc;
-    rc = linear_any(h->out_proj, s.a, E, nullptr, 0, s.b, E, B, kActNone, precision, s.any, stream);
-    if (rc) return rc;
-    rc = h->norm_is_batchnorm ? xmh_affine_cols(s.b, h->bn_mean, h->bn_var, h->norm_w, h->norm_b, h->norm_eps, s.a, B, E, stream)
-                              : xmh_layernorm_f32(s.b, E, h->norm_w, h->norm_b, h->norm_eps, s.a, E, B, E, stream);
-    if (rc) return rc;
-    rc = linear_any(h->fc2, s.a, E, nullptr, 0, s.wide, K2, B, kActRelu, precision, s.any, stream);
-    if (rc) return rc;
+    XMH_TRY(carve_head(workspace, workspace_bytes, B, E, precision, s, "xmh_head_dcmht"));
+    XMH_TRY(linear_any(h->v_proj, emb, E, nullptr, 0, s.a, E, B, kActNone, precision, s.any, stream));
+    XMH_TRY(linear_any(h->out_proj, s.a, E, nullptr, 0, s.b, E, B, kActNone, precision, s.any, stream));
+    XMH_TRY(h->norm_is_batchnorm ? xmh_affine_cols(s.b, h->bn_mean, h->bn_var, h->norm_w, h->norm_b, h->norm_eps, s.a, B, E, stream)
+                                 : xmh_layernorm_f32(s.b, E, h->norm_w, h->norm_b, h->norm_eps, s.a, E, B, E, stream));
+    XMH_TRY(linear_any(h->fc2, s.a, E, nullptr, 0, s.wide, K2, B, kActRelu, precision, s.any, stream));
     float* p = probs ? probs : s.wide2;
-    rc = xmh_pair_softmax(s.wide, p, B, (int)(K2 / 2), stream);
-    if (rc) return rc;
-    if (bits) rc = xmh_pack_pair_argmax(p, B, (int)(K2 / 2), row_index, bits, stream);
-    return rc;
+    XMH_TRY(xmh_pair_softmax(s.wide, p, B, (int)(K2 / 2), stream));
+    return bits ? xmh_pack_pair_argmax(p, B, (int)(K2 / 2), row_index, bits, stream) : 0;
 }
 
 extern "C" int xmh_head_dsph(const xmh_linear* fc, const float* emb, int64_t B, int precision, float* out, uint32_t* bits,
                              uint32_t* zero, int32_t* flags, const int64_t* row_index, void* workspace, size_t workspace_bytes,
                              xmh_stream_t stream) {
     XMH_RANGE("xmh_head_dsph");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!fc || !emb || (!out && !bits)) return xmh::fail(-22, "xmh_head_dsph: bad arguments");
     const int E = (int)fc->k;
@@ -582,13 +535,11 @@ extern "C" int xmh_head_dsph(const xmh_linear* fc, const float* emb, int64_t B, 
     HeadScratch s{};
     if (!out || precision != kPrecExact) {
         if (!workspace) return xmh::fail(-22, "xmh_head_dsph: workspace needed");
-        if (int rc = carve_head(workspace, workspace_bytes, B, E, precision, s, "xmh_head_dsph")) return rc;
+        XMH_TRY(carve_head(workspace, workspace_bytes, B, E, precision, s, "xmh_head_dsph"));
     }
     float* o = out ? out : s.wide;
-    int rc = linear_any(*fc, emb, E, nullptr, 0, o, K, B, kActTanh, precision, s.any, stream);
-    if (rc) return rc;
-    if (bits) rc = xmh_pack_sign(o, B, (int)K, row_index, bits, zero, flags, stream);
-    return rc;
+    XMH_TRY(linear_any(*fc, emb, E, nullptr, 0, o, K, B, kActTanh, precision, s.any, stream));
+    return bits ? xmh_pack_sign(o, B, (int)K, row_index, bits, zero, flags, stream) : 0;
 }
 
 // ---- MITH head ---------------------------------------------------------------------------------------------------------
@@ -626,23 +577,16 @@ int mith_gcl(const xmh_mith_head* h, const float* x, int64_t rows, float* y, flo
     for (int i = 0; i < h->res_layers; ++i) {
         const xmh_mith_mlp& m = h->mlps[i];
         if (m.fc1.k != D || m.fc2.n != D || m.fc2.k != m.fc1.n || m.fc1.n > 4 * D) return xmh::fail(-22, "xmh_head_mith: MLP %d shapes do not fit width %d", i, D);
-        int rc;
         if (precision != kPrecExact && planes_layer(m.fc1) && planes_layer(m.fc2)) {
-            rc = xmh::layernorm_planes(cur, D, m.ln_w, m.ln_b, m.ln_eps, nullptr, 0, s.hP, rows, D, xmh::as_stream(st));
-            if (rc) return rc;
+            XMH_TRY(xmh::layernorm_planes(cur, D, m.ln_w, m.ln_b, m.ln_eps, nullptr, 0, s.hP, rows, D, xmh::as_stream(st)));
             const xmh::Planes fo{s.fP.hi, s.fP.lo, m.fc1.n};
-            rc = linear_p(m.fc1, s.hP, nullptr, 0, nullptr, 0, &fo, rows, kActGeluErf, precision, st);
-            if (rc) return rc;
-            rc = linear_p(m.fc2, fo, cur, D, y, D, nullptr, rows, kActNone, precision, st);      // y = cur + fc2(..): no clone of x needed
-            if (rc) return rc;
+            XMH_TRY(linear_p(m.fc1, s.hP, nullptr, 0, nullptr, 0, &fo, rows, kActGeluErf, precision, st));
+            XMH_TRY(linear_p(m.fc2, fo, cur, D, y, D, nullptr, rows, kActNone, precision, st));      // y = cur + fc2(..): no clone of x needed
         } else {
             if (!hb || !f) return xmh::fail(-22, "xmh_head_mith: MLP %d lacks fp16 weights (w_hi)", i);
-            rc = xmh_layernorm_f32(cur, D, m.ln_w, m.ln_b, m.ln_eps, hb, D, rows, D, st);
-            if (rc) return rc;
-            rc = linear_any(m.fc1, hb, D, nullptr, 0, f, m.fc1.n, rows, kActGeluErf, precision, s.hP, st);
-            if (rc) return rc;
-            rc = linear_any(m.fc2, f, m.fc1.n, cur, D, y, D, rows, kActNone, precision, s.fP, st);
-            if (rc) return rc;
+            XMH_TRY(xmh_layernorm_f32(cur, D, m.ln_w, m.ln_b, m.ln_eps, hb, D, rows, D, st));
+            XMH_TRY(linear_any(m.fc1, hb, D, nullptr, 0, f, m.fc1.n, rows, kActGeluErf, precision, s.hP, st));
+            XMH_TRY(linear_any(m.fc2, f, m.fc1.n, cur, D, y, D, rows, kActNone, precision, s.fP, st));
         }
         cur = y;
     }
@@ -662,7 +606,7 @@ extern "C" int xmh_head_mith(const xmh_mith_head* h, const float* cls, const flo
                              int precision, float* cls_hash, float* tokens_hash, void* workspace, size_t workspace_bytes,
                              xmh_stream_t stream) {
     XMH_RANGE("xmh_head_mith");
-    if (int rc = check_precision(precision)) return rc;
+    XMH_TRY(check_precision(precision));
     if (B == 0) return 0;
     if (!h || !cls || !tokens || !cls_hash || !tokens_hash || !workspace || L <= 0) return xmh::fail(-22, "xmh_head_mith: bad arguments");
     const int D = h->width, K = h->k_bits;
@@ -672,13 +616,9 @@ extern "C" int xmh_head_mith(const xmh_mith_head* h, const float* cls, const flo
     MithScratch s;
     carve_mith(ar, B, L, D, K, precision, s);
     if (ar.used > workspace_bytes) return xmh::fail(-12, "xmh_head_mith: workspace of %zu bytes, %zu needed", workspace_bytes, ar.used);
-    int rc = mith_gcl(h, cls, B, s.ycls, s.hcls, s.fcls, cls_hash, precision, s, stream);
-    if (rc) return rc;
-    rc = mith_gcl(h, tokens, B * L, s.y, s.hbuf, s.f, s.scores, precision, s, stream);
-    if (rc) return rc;
-    rc = xmh_lta_aggregate(s.scores, tokens, token_mask, h->pos_enc, s.m, B, L, K, D, h->top_k, stream);
-    if (rc) return rc;
-    rc = run_blocks(h->blocks, h->layers, D, h->heads, s.m, B, K, 0, nullptr, precision, s.blk, stream);
-    if (rc) return rc;
+    XMH_TRY(mith_gcl(h, cls, B, s.ycls, s.hcls, s.fcls, cls_hash, precision, s, stream));
+    XMH_TRY(mith_gcl(h, tokens, B * L, s.y, s.hbuf, s.f, s.scores, precision, s, stream));
+    XMH_TRY(xmh_lta_aggregate(s.scores, tokens, token_mask, h->pos_enc, s.m, B, L, K, D, h->top_k, stream));
+    XMH_TRY(run_blocks(h->blocks, h->layers, Stack{D, h->heads, B, K, 0, nullptr, nullptr, precision, stream}, s.m, s.blk));
     return xmh_bitwise_hash(s.m, h->hash_w, h->hash_b, nullptr, tokens_hash, B, K, D, stream);
 }

@@ -28,6 +28,8 @@ constexpr int kT = 32;                           // product tile: 32 x 32 output
 constexpr int kPad = kT + 1;
 constexpr int kCols = 32, kGroups = kThreads / kCols;   // column kernels: 32 adjacent columns x 8 interleaved row groups per block
 
+using xmh::group_sum;
+
 // what forward keeps for backward (DCMHT)
 struct Saved {
     float* v;      // [B, E]
@@ -178,16 +180,6 @@ __global__ __launch_bounds__(kThreads) void k_mm(const float* __restrict__ A, in
             if (two) c[1] = tanhf(z1);
         }
     }
-}
-
-// fixed-order sum of the row groups' partials of one column; valid on every thread of the column
-__device__ __forceinline__ double group_sum(double v, double (*sh)[kCols], int col, int grp) {
-    sh[grp][col] = v;
-    __syncthreads();
-    double s = sh[0][col];
-    for (int g = 1; g < kGroups; ++g) s += sh[g][col];
-    __syncthreads();
-    return s;
 }
 
 // BatchNorm1d in training mode over o [B, E]: batch mean and BIASED variance (two passes, double), nhat, n, rstd per column, and the

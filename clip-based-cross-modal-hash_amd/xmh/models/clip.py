@@ -141,6 +141,7 @@ class Transformer(nn.Module):
 
 
     # per-layer record of xmh_clip_blocks_forward_saved (include/xmh.h): field -> width in units of D
+    # (the C side states the same layout once, in csrc/xmh_clip_record.h: saved_record)
     SAVED_FIELDS = (("x_in", 1), ("ln1", 1), ("qkv", 3), ("attn", 1), ("x_mid", 1), ("ln2", 1), ("fc_pre", 4), ("fc_act", 4))
 
     def run_saved(self, x: torch.Tensor, causal: bool = False, key_padding_mask=None):

@@ -405,7 +405,8 @@ int xmh_clip_blocks_forward(const xmh_clip_block* blocks, int layers, int width,
  *     x_in [M, D] | ln1 [M, D] | qkv [M, 3D] | attn [M, D] | x_mid [M, D] | ln2 [M, D] | fc_pre [M, 4D] | fc_act [M, 4D]      (M = B*L, D = width)
  * x_in = the residual stream entering the block, ln1 = ln_1(x_in), qkv = in_proj(ln1), attn = the heads' outputs before out_proj,
  * x_mid = x_in + out_proj(attn), ln2 = ln_2(x_mid), fc_pre = c_fc(ln2), fc_act = QuickGELU(fc_pre); the block's output is the
- * next record's x_in, the last block's output is x (in place, bit-identical to xmh_clip_blocks_forward in every precision). */
+ * next record's x_in, the last block's output is x (in place, bit-identical to xmh_clip_blocks_forward in every precision).
+ * The library's own statement of this layout, shared by the forward and the backward: csrc/xmh_clip_record.h. */
 size_t xmh_clip_saved_bytes(int64_t B, int L, int width, int layers);
 int xmh_clip_blocks_forward_saved(const xmh_clip_block* blocks, int layers, int width, int heads, float* x, int64_t B, int L,
                                   int causal, const uint8_t* key_padding_mask, int precision, void* workspace,

@@ -491,6 +491,75 @@ def test_whole_tower_entry_points_follow_weight_updates_and_reject_bad_input(ops
         C.check(lib.xmh_clip_blocks_forward(blk, 1, 64, 1, C.ptr(x), 1, 4, 0, None, 0, C.ptr(x), 16, C.current_stream()), "blocks")
 
 
+def _toy_stack(layers):
+    """Transformer(width 64, heads 1) with seeded random fp32 weights (not fp16 values: parity mode splits them too)"""
+    from xmh.models.clip import Transformer
+    T = Transformer(width=64, layers=layers, heads=1)
+    gen = g_(1814 + layers)
+    with torch.no_grad():
+        for name, p in T.named_parameters():
+            p.copy_(torch.randn(p.shape, generator=gen) * 0.1 + (1.0 if name.endswith(("ln_1.weight", "ln_2.weight")) else 0.0))
+    return T.cuda()
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("prec", ["f32", "f32x", "f16"])
+@pytest.mark.parametrize("layers", [1, 2])
+def test_block_stack_plain_and_saved_forwards_equal_the_primitive_chain(ops, layers, prec, masked):
+    """The residual block is enqueued in one place (csrc/xmh_forward.hip) for the plain and the saved forward, in planes and in exact
+    mode: on the smallest stack where those can still diverge -- width 64 (one head; K = 64 and 256 keep the planes route), B L = 15
+    rows, so every launch has a ragged last tile -- both equal the per-primitive chain bit for bit, and the record holds what the chain
+    computes: each layer's input, its first LayerNorm, and QuickGELU of the stored c_fc output."""
+    import xmh.models.clip as C
+    T = _toy_stack(layers)
+    x0 = torch.randn(3, 5, 64, generator=g_(7)).cuda()
+    kw = {}
+    if masked:                                                     # causal, and one trailing key hidden from every query
+        kpm = torch.zeros(3, 5, dtype=torch.bool)
+        kpm[:, -1] = True
+        kw = dict(causal=True, key_padding_mask=kpm.cuda())
+    eye = torch.eye(256, device="cuda")
+    before = ops.get_precision()
+    try:
+        ops.set_precision(prec)
+        assert C.NATIVE_FORWARD
+        native = T.run(x0.clone(), **kw)
+        y, saved = T.run_saved(x0.clone(), **kw)
+        C.NATIVE_FORWARD = False
+        try:
+            chain = T.run(x0.clone(), **kw)
+            outs, x = [], x0.clone()
+            for blk in T.resblocks:                                # the chain again, layer by layer
+                x = blk.run(x, kw.get("causal", False), kw.get("key_padding_mask"))
+                outs.append(x.clone())
+        finally:
+            C.NATIVE_FORWARD = True
+        assert torch.equal(native, chain) and torch.equal(y, chain) and torch.equal(outs[-1], chain)
+        assert len(saved) == layers and torch.equal(saved[0]["x_in"], x0)
+        for i, blk in enumerate(T.resblocks):
+            assert torch.equal(saved[i + 1]["x_in"] if i + 1 < layers else y, outs[i]), i
+            assert torch.equal(saved[i]["ln1"], ops.layernorm(saved[i]["x_in"], blk.ln_1.weight, blk.ln_1.bias)), i
+            # QuickGELU by ops: the GEMM epilogue behind an exact product with the identity
+            act = ops.gemm_nt(saved[i]["fc_pre"], eye, act=ops.ACT_QUICKGELU, precision=ops.PREC_F32X)
+            assert torch.equal(saved[i]["fc_act"], act), i
+    finally:
+        ops.set_precision(before)
+
+
+def test_block_stack_without_layers_leaves_x_alone(ops):
+    import xmh.models.clip as C
+    from xmh._lib import lib
+    x0 = torch.randn(3, 5, 64, generator=g_(8)).cuda()
+    x = x0.clone()
+    blk = (C._lib.ClipBlock * 1)()
+    for precision in (0, 1, 2):
+        nbytes = lib.xmh_clip_workspace_bytes(3, 5, 64, 0, 0, precision)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        assert lib.xmh_clip_blocks_forward(blk, 0, 64, 1, C.ptr(x), 3, 5, 0, None, precision, C.ptr(ws), nbytes, C.current_stream()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(x.view(torch.int32), x0.view(torch.int32))
+
+
 def test_head_entry_points_equal_the_primitive_chain_and_pack(ops):
     """xmh_head_dcmht / xmh_head_dsph against the per-primitive chain (bit for bit), and their packed outputs against
     xmh_pack_pair_argmax / xmh_pack_sign on the float outputs, including the row scatter."""
