@@ -96,7 +96,8 @@ struct WsLayout {
 // k_scan_hist_r2 / r2w keep hazards the compiler cannot see apart by hand (s_nop counts, early-clobber operands, statement order: see
 // the kernel), each of which was a wrong result on hardware before it was a comment.  A hipcc or ROCm change could break one of them
 // silently, so the kernels have to EARN their place once per device and process: r2_selfcheck_ok runs a small scan (several chunks,
-// ties, every geometry) with and without them and compares histograms and divisors bit for bit, AP sums to float rounding; a mismatch
+// ties, every geometry; 80 classes, and 128 with pairs whose only common class lies in label words 2 and 3 or that have none: the FP4
+// label tile and its denormal chain start) with and without them and compares histograms and divisors bit for bit, AP sums to float rounding; a mismatch
 // prints one line to stderr and every later plan of this process uses the VALU kernels, as XMH_SCAN_MFMA=0 does.
 // XMH_SCAN_M2_SELFCHECK=0 skips it, =2 runs it and pretends it failed (the test of the fallback); its own evaluations pin the answer
 // with Overrides::mfma.
@@ -389,7 +390,7 @@ struct Launch {                     // one kernel instance, template arguments a
     int W = 0, LW = 0;              // code / label words the launch dispatches on (dispatch_shape)
     bool tern = false, cache = false;
     int S = 0, NW = 1;              // VALU kernels and k_scan_ap_c: slots, waves per block; k_scan_hist_r2 / r2w / ap_r2: query groups per wave, waves; k_scan_hist_b: code tiles
-    int nml = 0;                    // k_scan_hist_r2 / r2w / ap_r2: label tiles
+    int nml = 0;                    // k_scan_hist_r2 / r2w / ap_r2: the label tile (1: i8, at most 64 classes; 2: FP4, 65-128 classes)
     int eb = 0; bool half = false;  // k_scan_ap_c: entry bits (8: one byte, 16: the 12-bit entries of the two-byte layout); 8 slots x 8 queries on one-byte entries
     bool p32 = false, masked = false;
     unsigned gate = 0;
@@ -937,9 +938,12 @@ bool r2_selfcheck_ok() {
     if (state[dev]) return state[dev] == 1;
     state[dev] = 1;                                       // the evaluations below pin Overrides::mfma and do not ask again
     const int64_t Q = 200, R = 9000;
-    const int C = 80, LW = 3;
     bool same = true, ran = true;
-    for (int K : {64, 40, 16, 100}) {                     // two code words, one + a partial one, <= 32 bits (all k_scan_hist_r2), 65..128 bits (k_scan_hist_r2w)
+    // two code words, one + a partial one, <= 32 bits (all k_scan_hist_r2), 65..128 bits (k_scan_hist_r2w), with 80 classes; then both
+    // kernels with 128 classes and labels made for the FP4 label tile (below)
+    const int cases[6][2] = {{64, 80}, {40, 80}, {16, 80}, {100, 80}, {64, 128}, {100, 128}};
+    for (const auto& kc : cases) {
+        const int K = kc[0], C = kc[1], LW = (C + 31) / 32;
         const int W = (K + 31) / 32;
         std::vector<uint32_t> qb(Q * W), ql(Q * LW), rb(R * W), rl(R * LW);
         uint64_t x = 0x9E3779B97F4A7C15ull ^ (uint64_t)K;
@@ -950,10 +954,24 @@ bool r2_selfcheck_ok() {
             for (int w = 0; w < W; ++w) rb[i * W + w] = (i > 64 && (rnd() & 3) == 0) ? rb[(rnd() % 64) * W + w] : rnd();
         for (int64_t i = 0; i < Q; ++i) qb[i * W + W - 1] &= last;
         for (int64_t i = 0; i < R; ++i) rb[i * W + W - 1] &= last;
-        for (int64_t i = 0; i < Q * LW; ++i) ql[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
-        for (int64_t i = 0; i < R * LW; ++i) rl[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? 0xffffu : 0xffffffffu);
-        for (int64_t i = 0; i < Q; ++i) ql[i * LW] |= 1u;                            // every query has a relevant item
-        for (int64_t i = 0; i < R; i += 7) rl[i * LW] |= 1u;
+        const uint32_t lastl = C % 32 ? (1u << (C % 32)) - 1 : 0xffffffffu;
+        for (int64_t i = 0; i < Q * LW; ++i) ql[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? lastl : 0xffffffffu);
+        for (int64_t i = 0; i < R * LW; ++i) rl[i] = rnd() & rnd() & rnd() & (i % LW == LW - 1 ? lastl : 0xffffffffu);
+        if (C == 80) {
+            for (int64_t i = 0; i < Q; ++i) ql[i * LW] |= 1u;                        // every query has a relevant item
+            for (int64_t i = 0; i < R; i += 7) rl[i * LW] |= 1u;
+        } else {
+            // 128 classes: the label overlap is ONE FP4 MFMA whose f32 chain starts at a denormal (xmh_scan_mfma.h, label_query_f4).  Every
+            // other query and two items of three carry a single class, mostly in words 2 and 3: pairs whose only common class lies in bits
+            // 64..127, pairs with none at all (every third item has no label), and full rows (count 128) next to the random ones
+            auto one = [&](uint32_t* l, int c) { for (int w = 0; w < LW; ++w) l[w] = 0u; l[c >> 5] = 1u << (c & 31); };
+            for (int64_t i = 0; i < Q; i += 2) one(&ql[i * LW], i % 8 == 0 ? (int)(i * 3 % 64) : 64 + (int)(i * 7 % 64));
+            for (int64_t i = 0; i < R; ++i) {
+                if (i % 3 == 0) one(&rl[i * LW], 64 + (int)(i * 5 % 64));
+                else if (i % 3 == 1) for (int w = 0; w < LW; ++w) rl[i * LW + w] = 0u;
+            }
+            for (int w = 0; w < LW; ++w) ql[1 * LW + w] = rl[2 * LW + w] = rl[5000 * LW + w] = 0xffffffffu;
+        }
         std::vector<uint32_t> h1, h0;
         std::vector<double> a1, a0;
         std::vector<int32_t> c1, c0;

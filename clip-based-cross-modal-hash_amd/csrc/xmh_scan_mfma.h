@@ -49,7 +49,8 @@ __device__ __forceinline__ bool map_block(const ScanArgs& a, int& chunk_id, int&
 //     cache entry (distance << 1 | relevant);
 //   * label chain: item and query label bits as bytes 0 / 1.  Pass 1 starts it at 0x10000, so that min(acc, 0x10001) is the add operand of
 //     (all << 16 | relevant) counters and its low byte the relevance bit (a chunk has at most kMaxChunk items: the 16-bit halves hold).
-//     Pass 2 (k_scan_ap_r2) has query label bytes 0 / -1 and takes max(acc, -1) as the mask 0 / ~0.
+//     Pass 2 (k_scan_ap_r2) has query label bytes 0 / -1 and takes max(acc, -1) as the mask 0 / ~0.  65-128 classes (three or four label
+//     words) are ONE FP4 tile with K = 128 on v_mfma_f32_16x16x128_f8f6f4 instead of two i8 tiles: label_query_f4 / label_item_f4 below.
 // Per pair the VALU does two instructions in pass 1 (v_min, the SDWA OR of the cache byte), the credit arithmetic in pass 2.  Geometry = the
 // slotted scheme with S = 4: lane = slot * 16 + query, and MFMA row 4*slot + j of a 16-item group holds item 4*j + slot, so accumulator register j
 // of a lane is its step j and same-query lanes of one LDS instruction are consecutive items in lane order -- what pass 2's returning adds need.
@@ -77,6 +78,26 @@ __device__ __forceinline__ bool mfma_map_block(const MfmaArgs& a, int& chunk_id,
     qtile = t % a.nqt;
     chunk_id = xcd + 8 * (t / a.nqt);
     return chunk_id < a.nchunk;
+}
+
+// The label tile of 65-128 classes (three or four label words; NML = 2 in the kernels below): ONE v_mfma_f32_16x16x128_f8f6f4 with FP4
+// (E2M1) operands, cbsz:4 blgp:4, instead of two i8 tiles of 64 classes.  Lane (row, slot) holds the 32 classes of label word `slot` as 32
+// nibbles in four registers: nibble n of register j stands for bit 4 n + j of the word -- on both sides, which is all a dot product
+// needs.  The query side sets a nibble to `one` (0x2 = +1.0, 0xA = -1.0).  The item side only has to tell an overlap from none, so its
+// bits stay where they stand in their nibble wherever that is a positive E2M1 value: bit 0 -> 0x1 = 0.5, bit 1 -> 0x2 = 1.0, bit 2 ->
+// 0x4 = 2.0; bit 3 would be the sign and moves down to 0x4 -- 5 operations per tile, and a sum of at most 128 x 2.0 in an exact f32.
+// The accumulator is f32: pass 1 starts it at the bit pattern 0x00010000, a denormal that the matrix pipe passes through unflushed (C and
+// D of an MFMA never flush; tools/ubench_mfma_label.hip shows it, the self-check of xmh_scan.hip holds every device to it): no overlap
+// leaves 0x10000, any overlap gives a normal float >= 0.5 whose bits are far above 0x10001, so min_u32(bits, 0x10001) is the same add
+// operand as that of the i8 chain.  A label word past LW is clamped on the item side and zero on the query side.
+__device__ __forceinline__ v4i label_query_f4(uint32_t w, uint32_t one) {
+    v4i r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = (int)(((w >> j) & 0x11111111u) * one);
+    return r;
+}
+__device__ __forceinline__ v4i label_item_f4(uint32_t w) {
+    return v4i{(int)(w & 0x11111111u), (int)(w & 0x22222222u), (int)(w & 0x44444444u), (int)((w >> 1) & 0x44444444u)};
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -115,7 +136,9 @@ __device__ __forceinline__ bool mfma_map_block(const MfmaArgs& a, int& chunk_id,
 // ---------------------------------------------------------------------------------------------------
 template <int NML, int NW, int NQ, bool CACHE>
 __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* __restrict__ chunk_hist, uint4* __restrict__ pair_cache) {
-    constexpr int NMI = 1 + NML, NMQ = 2 + NML;
+    static_assert(NML == 1 || NML == 2, "one i8 label tile (at most 64 classes) or one FP4 label tile (65-128 classes)");
+    constexpr bool F4 = NML == 2;                                    // the label tile is FP4 (E2M1) with K = 128: see label_query_f4 / label_item_f4
+    constexpr int NMI = 2, NMQ = 3;                                  // operand tiles per item group (code, label) and per query group (address, 2 * distance, label)
     constexpr bool REGS = true;                                      // (the operands come from the packed words; kept as a name in the expressions below)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters
     int chunk_id, qtile;
@@ -158,13 +181,14 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
                     bq[h][1][j] = on ? (int)(0x02020202u ^ (t * 0xfcu)) : 0;     // +2 / -2 (0xfe)
                 }
             }
-#pragma unroll
-            for (int m = 0; m < NML; ++m) {
+            if constexpr (F4) {
+                bq[h][2] = label_query_f4(valid[h] && slot < a.LW ? a.qlab[q * a.LW + slot] : 0u, 0x2u);
+            } else {
                 uint32_t lw = 0u;
-                if (valid[h] && 2 * m + rwi < a.LW) lw = a.qlab[q * a.LW + 2 * m + rwi];
+                if (valid[h] && rwi < a.LW) lw = a.qlab[q * a.LW + rwi];
                 lw >>= rsh;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bq[h][2 + m][j] = (int)((lw >> j) & 0x01010101u);
+                for (int j = 0; j < 4; ++j) bq[h][2][j] = (int)((lw >> j) & 0x01010101u);
             }
             const int k2 = 2 * pcq;
             kqv[h] = v4i{k2, k2, k2, k2};
@@ -195,19 +219,17 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
     // a word index past the end of the record is clamped to the last word: the query operand of that lane group is zero (above), so the
     // bits loaded in its place count for nothing
     const int wi_c = rwi < a.W ? rwi : a.W - 1;
-    int wi_l[NML];
-#pragma unroll
-    for (int m = 0; m < NML; ++m) wi_l[m] = 2 * m + rwi < a.LW ? 2 * m + rwi : (a.LW > 0 ? a.LW - 1 : 0);
+    const int lwi = F4 ? slot : rwi;                                 // the label word of this lane: an FP4 tile holds 32 classes per slot, an i8 tile 16
+    const int wi_l = lwi < a.LW ? lwi : (a.LW > 0 ? a.LW - 1 : 0);
     auto load_words = [&](int64_t batch, uint32_t (&w)[4][NMI]) {
         const int64_t first = batch * 64;
         if (first + 64 <= (int64_t)a.R) {                             // whole batch inside the gallery (wave-uniform): one address per array, constant strides
             const uint32_t* __restrict__ pc = a.rbits + (first + ritem) * a.W + wi_c;
-            const uint32_t* __restrict__ pl = a.rlab + (first + ritem) * a.LW;
+            const uint32_t* __restrict__ pl = a.rlab + (first + ritem) * a.LW + wi_l;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 w[g][0] = pc[g * 16 * a.W];
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][1 + m] = pl[g * 16 * a.LW + wi_l[m]];
+                w[g][1] = pl[g * 16 * a.LW];
             }
         } else {
 #pragma unroll
@@ -216,8 +238,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
                 const int64_t it = item < a.R ? item : (int64_t)a.R - 1;
                 const uint32_t ok = item < a.R ? 0xffffffffu : 0u;   // items past the end: all-zero codes, no labels (the epilogue takes them out again)
                 w[g][0] = a.rbits[it * a.W + wi_c] & ok;
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][1 + m] = a.rlab[it * a.LW + wi_l[m]] & ok;
+                w[g][1] = a.rlab[it * a.LW + wi_l] & ok;
             }
         }
     };
@@ -225,18 +246,20 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
     // pick them -- the odd ones worth 2 where they stand, which the halved query bytes above make up for (the products of both chains have
     // to be exact: they are an address and a cache byte).  The label tiles only have to tell an overlap from none, so their bits stay where
     // one shift leaves them: y & (0x01010101 << j) is worth 2^j (1, 2, 4, 8) in its byte, the sum over the common labels is positive
-    // exactly when there is one, and min(0x10000 + sum, 0x10001) is the add operand as before -- 5 operations.
+    // exactly when there is one, and min(0x10000 + sum, 0x10001) is the add operand as before -- 5 operations.  The FP4 tile of 65-128
+    // classes: label_item_f4, 5 operations as well (the two i8 tiles it replaces took 10).
     auto build = [&](v4i (&At)[NMI], const uint32_t (&w)[NMI]) {
         const uint32_t xa = w[0] >> rsh, xb = w[0] >> (rsh + 2);
         At[0][0] = (int)(xa & 0x01010101u);
         At[0][1] = (int)(xa & 0x02020202u);
         At[0][2] = (int)(xb & 0x01010101u);
         At[0][3] = (int)(xb & 0x02020202u);
+        if constexpr (F4) {
+            At[1] = label_item_f4(w[1]);
+        } else {
+            const uint32_t y = w[1] >> rsh;
 #pragma unroll
-        for (int m = 1; m < NMI; ++m) {
-            const uint32_t y = w[m] >> rsh;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) At[m][j] = (int)(y & (0x01010101u << j));
+            for (int j = 0; j < 4; ++j) At[1][j] = (int)(y & (0x01010101u << j));
         }
     };
     load_words(bat0, wcur);
@@ -306,92 +329,59 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
 #endif
 #ifdef XMH_ABL_NOMFMA
 #define XMH_MFMA(D, A, B, C) "s_nop 0\n\t"
+#define XMH_MFMA_F4(D, A, B, C) "s_nop 0\n\t"
 #else
 #define XMH_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 " D ", " A ", " B ", " C "\n\t"
+#define XMH_MFMA_F4(D, A, B, C) "v_mfma_f32_16x16x128_f8f6f4 " D ", " A ", " B ", " C " cbsz:4 blgp:4\n\t"
 #endif
 #define XMH_SDWA(J) "dst_sel:BYTE_" #J " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
+// The statements, once per label instruction (LAB = XMH_MFMA: the i8 tile of at most 64 classes; XMH_MFMA_F4: the FP4 tile of 65-128).
+// Both take four passes of the matrix pipe and need the same wait states in front of a VALU read, and both leave the bits the v_min reads.
+#define XMH_R2_FUSED_CACHE(LAB)                                                                                                                   \
+    asm volatile(XMH_R2_OPEN LAB("%0", "%8", "%9", "%10")                                                                                         \
+                 XMH_VMIN "%4, 0x10001, %24\n\t" XMH_VMIN "%5, 0x10001, %25\n\t" XMH_VMIN "%6, 0x10001, %26\n\t" XMH_VMIN "%7, 0x10001, %27\n\t" \
+                 "v_or_b32_sdwa %3, %16, %4 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"                            \
+                 XMH_ADD("%20", "%4")                                                                                                             \
+                 XMH_MFMA("%1", "%11", "%12", "%13")                                                                                              \
+                 "v_or_b32_sdwa %3, %17, %5 " XMH_SDWA(1) XMH_ADD("%21", "%5") "v_or_b32_sdwa %3, %18, %6 " XMH_SDWA(2)                           \
+                 XMH_MFMA("%2", "%11", "%14", "%15")                                                                                              \
+                 XMH_ADD("%22", "%6") "v_or_b32_sdwa %3, %19, %7 " XMH_SDWA(3) XMH_ADD("%23", "%7")                                               \
+                 : "=&v"(lab), "=&v"(addr), "=&v"(d2), "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)                                        \
+                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]),             \
+                   "v"(d2_p[0]), "v"(d2_p[1]), "v"(d2_p[2]), "v"(d2_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]),         \
+                   "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])                                                                      \
+                 : "memory")
+#define XMH_R2_FUSED_PLAIN(LAB)                                                                                                                   \
+    asm volatile(XMH_R2_OPEN LAB("%0", "%6", "%7", "%8")                                                                                          \
+                 XMH_VMIN "%2, 0x10001, %16\n\t" XMH_VMIN "%3, 0x10001, %17\n\t" XMH_VMIN "%4, 0x10001, %18\n\t" XMH_VMIN "%5, 0x10001, %19\n\t" \
+                 XMH_MFMA("%1", "%9", "%10", "%11")                                                                                               \
+                 XMH_ADD("%12", "%2") XMH_ADD("%13", "%3") XMH_ADD("%14", "%4") XMH_ADD("%15", "%5")                                              \
+                 : "=&v"(lab), "=&v"(addr), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)                                                             \
+                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]),                                                    \
+                   "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])      \
+                 : "memory")
+#define XMH_R2_EVAL_CACHE(LAB)                                                                                                                    \
+    asm volatile(XMH_R2_OPEN LAB("%0", "%3", "%4", "%5") XMH_MFMA("%1", "%6", "%7", "%8") XMH_MFMA("%2", "%6", "%9", "%10") XMH_R2_EVAL_CLOSE     \
+                 : "=&v"(lab), "=&v"(addr), "=&v"(d2)                                                                                             \
+                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]))
+#define XMH_R2_EVAL_PLAIN(LAB)                                                                                                                    \
+    asm volatile(XMH_R2_OPEN LAB("%0", "%2", "%3", "%4") XMH_MFMA("%1", "%5", "%6", "%7") XMH_R2_EVAL_CLOSE                                       \
+                 : "=&v"(lab), "=&v"(addr)                                                                                                        \
+                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]))
         auto fused = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab, uint32_t& w) {
             uint32_t i0, i1, i2, i3;                                  // min results: fresh registers (in-place on the MFMA's result tuple made hipcc copy them)
-            if (NML == 2 && CACHE) {
-                asm volatile(
-                    XMH_R2_OPEN XMH_MFMA("%0", "%8", "%9", "%10")
-                    XMH_VMIN "%4, 0x10001, %26\n\t" XMH_VMIN "%5, 0x10001, %27\n\t" XMH_VMIN "%6, 0x10001, %28\n\t"
-                    XMH_MFMA("%0", "%11", "%12", "%0")
-                    XMH_VMIN "%7, 0x10001, %29\n\t"
-                    "v_or_b32_sdwa %3, %18, %4 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-                    XMH_ADD("%22", "%4")
-                    XMH_MFMA("%1", "%13", "%14", "%15")
-                    "v_or_b32_sdwa %3, %19, %5 " XMH_SDWA(1) XMH_ADD("%23", "%5") "v_or_b32_sdwa %3, %20, %6 " XMH_SDWA(2)
-                    XMH_MFMA("%2", "%13", "%16", "%17")
-                    XMH_ADD("%24", "%6") "v_or_b32_sdwa %3, %21, %7 " XMH_SDWA(3) XMH_ADD("%25", "%7")
-                    : "=&v"(lab), "=&v"(addr), "=&v"(d2), "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
-                    : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[NMI - 1]), "v"(bq[h][NMQ - 1]), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]),
-                      "v"(d2_p[0]), "v"(d2_p[1]), "v"(d2_p[2]), "v"(d2_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]),
-                      "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])
-                    : "memory");
-            } else if (NML == 2) {
-                asm volatile(
-                    XMH_R2_OPEN XMH_MFMA("%0", "%6", "%7", "%8")
-                    XMH_VMIN "%2, 0x10001, %18\n\t" XMH_VMIN "%3, 0x10001, %19\n\t" XMH_VMIN "%4, 0x10001, %20\n\t"
-                    XMH_MFMA("%0", "%9", "%10", "%0")
-                    XMH_VMIN "%5, 0x10001, %21\n\t" XMH_ADD("%14", "%2") XMH_ADD("%15", "%3")
-                    XMH_MFMA("%1", "%11", "%12", "%13")
-                    XMH_ADD("%16", "%4") XMH_ADD("%17", "%5")
-                    : "=&v"(lab), "=&v"(addr), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
-                    : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[NMI - 1]), "v"(bq[h][NMQ - 1]), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]),
-                      "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])
-                    : "memory");
-            } else if (CACHE) {
-                asm volatile(
-                    XMH_R2_OPEN XMH_MFMA("%0", "%8", "%9", "%10")
-                    XMH_VMIN "%4, 0x10001, %24\n\t" XMH_VMIN "%5, 0x10001, %25\n\t" XMH_VMIN "%6, 0x10001, %26\n\t" XMH_VMIN "%7, 0x10001, %27\n\t"
-                    "v_or_b32_sdwa %3, %16, %4 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-                    XMH_ADD("%20", "%4")
-                    XMH_MFMA("%1", "%11", "%12", "%13")
-                    "v_or_b32_sdwa %3, %17, %5 " XMH_SDWA(1) XMH_ADD("%21", "%5") "v_or_b32_sdwa %3, %18, %6 " XMH_SDWA(2)
-                    XMH_MFMA("%2", "%11", "%14", "%15")
-                    XMH_ADD("%22", "%6") "v_or_b32_sdwa %3, %19, %7 " XMH_SDWA(3) XMH_ADD("%23", "%7")
-                    : "=&v"(lab), "=&v"(addr), "=&v"(d2), "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
-                    : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]),
-                      "v"(d2_p[0]), "v"(d2_p[1]), "v"(d2_p[2]), "v"(d2_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]),
-                      "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])
-                    : "memory");
-            } else {
-                asm volatile(
-                    XMH_R2_OPEN XMH_MFMA("%0", "%6", "%7", "%8")
-                    XMH_VMIN "%2, 0x10001, %16\n\t" XMH_VMIN "%3, 0x10001, %17\n\t" XMH_VMIN "%4, 0x10001, %18\n\t" XMH_VMIN "%5, 0x10001, %19\n\t"
-                    XMH_MFMA("%1", "%9", "%10", "%11")
-                    XMH_ADD("%12", "%2") XMH_ADD("%13", "%3") XMH_ADD("%14", "%4") XMH_ADD("%15", "%5")
-                    : "=&v"(lab), "=&v"(addr), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
-                    : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]),
-                      "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])
-                    : "memory");
-            }
+            if constexpr (F4 && CACHE) XMH_R2_FUSED_CACHE(XMH_MFMA_F4);
+            else if constexpr (F4) XMH_R2_FUSED_PLAIN(XMH_MFMA_F4);
+            else if constexpr (CACHE) XMH_R2_FUSED_CACHE(XMH_MFMA);
+            else XMH_R2_FUSED_PLAIN(XMH_MFMA);
         };
         // the first statement of a batch: nothing to consume yet.  Closed by 8 wait states: the next statement's consumers (and any
         // copy hipcc places in front of it) read these results, and its own MFMA is only one slot away
         auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab) {
-            if (NML == 2 && CACHE) {
-                asm volatile(XMH_R2_OPEN XMH_MFMA("%0", "%3", "%4", "%5") XMH_MFMA("%0", "%6", "%7", "%0")
-                             XMH_MFMA("%1", "%8", "%9", "%10") XMH_MFMA("%2", "%8", "%11", "%12") XMH_R2_EVAL_CLOSE
-                             : "=&v"(lab), "=&v"(addr), "=&v"(d2)
-                             : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[NMI - 1]), "v"(bq[h][NMQ - 1]), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]),
-                               "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]));
-            } else if (NML == 2) {
-                asm volatile(XMH_R2_OPEN XMH_MFMA("%0", "%2", "%3", "%4") XMH_MFMA("%0", "%5", "%6", "%0")
-                             XMH_MFMA("%1", "%7", "%8", "%9") XMH_R2_EVAL_CLOSE
-                             : "=&v"(lab), "=&v"(addr)
-                             : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[NMI - 1]), "v"(bq[h][NMQ - 1]), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]));
-            } else if (CACHE) {
-                asm volatile(XMH_R2_OPEN XMH_MFMA("%0", "%3", "%4", "%5") XMH_MFMA("%1", "%6", "%7", "%8")
-                             XMH_MFMA("%2", "%6", "%9", "%10") XMH_R2_EVAL_CLOSE
-                             : "=&v"(lab), "=&v"(addr), "=&v"(d2)
-                             : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]));
-            } else {
-                asm volatile(XMH_R2_OPEN XMH_MFMA("%0", "%2", "%3", "%4") XMH_MFMA("%1", "%5", "%6", "%7") XMH_R2_EVAL_CLOSE
-                             : "=&v"(lab), "=&v"(addr)
-                             : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]));
-            }
+            if constexpr (F4 && CACHE) XMH_R2_EVAL_CACHE(XMH_MFMA_F4);
+            else if constexpr (F4) XMH_R2_EVAL_PLAIN(XMH_MFMA_F4);
+            else if constexpr (CACHE) XMH_R2_EVAL_CACHE(XMH_MFMA);
+            else XMH_R2_EVAL_PLAIN(XMH_MFMA);
         };
         auto consume = [&](uint32_t& w, const v4i (&live)[NMI]) {        // the last pair of a batch (live: hazard (iv) of the list above this function)
             uint32_t i0, i1, i2, i3;
@@ -416,8 +406,13 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
                     : "memory");
             }
         };
+#undef XMH_R2_EVAL_PLAIN
+#undef XMH_R2_EVAL_CACHE
+#undef XMH_R2_FUSED_PLAIN
+#undef XMH_R2_FUSED_CACHE
 #undef XMH_SDWA
 #undef XMH_ADD
+#undef XMH_MFMA_F4
 #undef XMH_MFMA
         auto group = [&](auto gc) {
             constexpr int G = decltype(gc)::value;
@@ -526,8 +521,8 @@ __global__ __launch_bounds__(64 * NW) XMH_R2_ATTR void k_scan_hist_r2(MfmaArgs a
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_scan_hist_r2w (round 4): k_scan_hist_r2 for codes of 65..128 bits -- TWO code tiles per chain (six MFMAs per (16 items x 16 queries):
-// label, label, address, address, 2 * distance, 2 * distance), 129 bucket rows, 2 query groups per wave (66 KB of counters per block of four
+// k_scan_hist_r2w (round 4): k_scan_hist_r2 for codes of 65..128 bits -- TWO code tiles per chain (five MFMAs per (16 items x 16 queries):
+// label, address, address, 2 * distance, 2 * distance), 129 bucket rows, 2 query groups per wave (66 KB of counters per block of four
 // waves, two blocks per CU), one-byte pair-cache entries in the layout of the shorter codes.  Same operand construction, same pipeline of
 // statements one (item group, query group) behind their MFMAs, same hazards (the list above scan_hist_r2_body).  Two differences in form: the operands
 // are named (a statement has 28 of the 30 an asm may take), and the cache word is assembled by a second, small statement -- byte j of the
@@ -536,12 +531,37 @@ __global__ __launch_bounds__(64 * NW) XMH_R2_ATTR void k_scan_hist_r2(MfmaArgs a
 // byte wraps to 0: the same statement keeps the largest 2 * distance seen, and the kernel raises *ovf (kGateWrapped: pass 2 then evaluates the pairs from the codes).
 // ---------------------------------------------------------------------------------------------------
 #define XMH_W_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 %[" D "], %[" A "], %[" B "], %[" C "]\n\t"
+#define XMH_W_MFMA_F4(D, A, B, C) "v_mfma_f32_16x16x128_f8f6f4 %[" D "], %[" A "], %[" B "], %[" C "] cbsz:4 blgp:4\n\t"
 #define XMH_W_MIN(I, L) "v_min_u32 %[" I "], 0x10001, %[" L "]\n\t"
 #define XMH_W_ADD(A, D) "ds_add_u32 %[" A "], %[" D "]\n\t"
+// the statements of k_scan_hist_r2w, once per label instruction (LAB = XMH_W_MFMA: the i8 tile of at most 64 classes; XMH_W_MFMA_F4: the FP4
+// tile of 65-128 classes -- same passes, same wait states, same bits for the v_min)
+#define XMH_W_FUSED_CACHE(LAB) \
+    asm volatile("s_nop 3\n\t" LAB("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")                \
+                 XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap1", "i1")                         \
+                 XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_ADD("ap2", "i2") XMH_W_MFMA("d2", "a0", "bd0", "kq") XMH_W_ADD("ap3", "i3")          \
+                 XMH_W_MFMA("d2", "a1", "bd1", "d2")                                                                                                \
+                 : [lab] "=&v"(lab), [addr] "=&v"(addr), [d2] "=&v"(d2), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)             \
+                 : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bd0] "v"(bD[h][0]),               \
+                   [bd1] "v"(bD[h][1]), [bl0] "v"(bL[h]), [lab0] "v"(lab0), [cq] "v"(cq[h]), [kq] "v"(kq[h]), [lp0] "v"(lab_p[0]),                  \
+                   [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), \
+                   [ap3] "v"(addr_p[3])                                                                                                             \
+                 : "memory")
+#define XMH_W_FUSED_PLAIN(LAB) \
+    asm volatile("s_nop 3\n\t" LAB("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")                 \
+                 XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_ADD("ap1", "i1") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap2", "i2")   \
+                 XMH_W_ADD("ap3", "i3") XMH_W_MFMA("addr", "a1", "ba1", "addr")                                                                      \
+                 : [lab] "=&v"(lab), [addr] "=&v"(addr), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)                              \
+                 : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bl0] "v"(bL[h]), [lab0] "v"(lab0), \
+                   [cq] "v"(cq[h]), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]),        \
+                   [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3])                                                                  \
+                 : "memory")
 template <int NML, int NW, int NQ, bool CACHE>
 __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t* __restrict__ chunk_hist, uint4* __restrict__ pair_cache,
                                                            uint32_t* __restrict__ ovf) {
-    constexpr int NMC = 2, NMI = NMC + NML;
+    static_assert(NML == 1 || NML == 2, "one i8 label tile (at most 64 classes) or one FP4 label tile (65-128 classes)");
+    constexpr bool F4 = NML == 2;                                    // the label tile is FP4 with K = 128 (label_query_f4 / label_item_f4)
+    constexpr int NMC = 2, NMI = NMC + 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters (all << 16 | relevant)
     int chunk_id, qtile;
     if (!mfma_map_block(a, chunk_id, qtile)) return;                 // a.nqt counts tiles of NW * NQ * 16 queries here
@@ -552,7 +572,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
     uint32_t* cnt = lds + (wave * NQ) * ncell;
     for (int e = lane; e < NQ * ncell; e += 64) cnt[e] = 0u;
     const int rsh = 4 * (slot & 1), rwi = slot >> 1;                 // this lane's nibble of the 16 bits it owns; its word inside a 64-bit tile
-    v4i bA[NQ][NMC], bD[NQ][NMC], bL[NQ][NML], cq[NQ], kq[NQ];
+    v4i bA[NQ][NMC], bD[NQ][NMC], bL[NQ], cq[NQ], kq[NQ];
     bool valid[NQ];
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
@@ -578,13 +598,14 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
                 }
             }
         }
-#pragma unroll
-        for (int m = 0; m < NML; ++m) {
+        if constexpr (F4) {
+            bL[h] = label_query_f4(valid[h] && slot < a.LW ? a.qlab[q * a.LW + slot] : 0u, 0x2u);
+        } else {
             uint32_t lw = 0u;
-            if (valid[h] && 2 * m + rwi < a.LW) lw = a.qlab[q * a.LW + 2 * m + rwi];
+            if (valid[h] && rwi < a.LW) lw = a.qlab[q * a.LW + rwi];
             lw >>= rsh;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bL[h][m][j] = (int)((lw >> j) & 0x01010101u);
+            for (int j = 0; j < 4; ++j) bL[h][j] = (int)((lw >> j) & 0x01010101u);
         }
         const int c0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(cnt + h * ncell) + ql * 4 + (valid[h] ? 64 * pcq : 0);
         const int k2 = valid[h] ? 2 * pcq : 0;
@@ -605,11 +626,11 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
         crow[h] = CACHE ? pair_cache + ((int64_t)chunk_id * (a.qpad >> 4) + (t16 + h)) * ((a.chunk + 63) >> 6) * 64 + lane : nullptr;
     uint32_t wcur[4][NMI], wnxt[4][NMI];
     const int ritem = 4 * (lane & 3) + ((lane & 15) >> 2);           // row r of group g is item 16 g + 4 (r & 3) + (r >> 2)
-    int wi_c[NMC], wi_l[NML];
+    int wi_c[NMC];
 #pragma unroll
     for (int c = 0; c < NMC; ++c) wi_c[c] = 2 * c + rwi < a.W ? 2 * c + rwi : a.W - 1;
-#pragma unroll
-    for (int m = 0; m < NML; ++m) wi_l[m] = 2 * m + rwi < a.LW ? 2 * m + rwi : (a.LW > 0 ? a.LW - 1 : 0);
+    const int lwi = F4 ? slot : rwi;                                 // an FP4 label tile holds 32 classes per slot, an i8 tile 16
+    const int wi_l = lwi < a.LW ? lwi : (a.LW > 0 ? a.LW - 1 : 0);
     auto load_words = [&](int64_t batch, uint32_t (&w)[4][NMI]) {
         const int64_t first = batch * 64;
         if (first + 64 <= (int64_t)a.R) {                             // whole batch inside the gallery (wave-uniform)
@@ -619,8 +640,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
             for (int g = 0; g < 4; ++g) {
 #pragma unroll
                 for (int c = 0; c < NMC; ++c) w[g][c] = pc[g * 16 * a.W + wi_c[c]];
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][NMC + m] = pl[g * 16 * a.LW + wi_l[m]];
+                w[g][NMC] = pl[g * 16 * a.LW + wi_l];
             }
         } else {
 #pragma unroll
@@ -630,8 +650,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
                 const uint32_t ok = item < a.R ? 0xffffffffu : 0u;   // items past the end: all-zero codes, no labels (taken out again below)
 #pragma unroll
                 for (int c = 0; c < NMC; ++c) w[g][c] = a.rbits[it * a.W + wi_c[c]] & ok;
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][NMC + m] = a.rlab[it * a.LW + wi_l[m]] & ok;
+                w[g][NMC] = a.rlab[it * a.LW + wi_l] & ok;
             }
         }
     };
@@ -644,11 +663,12 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
             At[c][2] = (int)(xb & 0x01010101u);
             At[c][3] = (int)(xb & 0x02020202u);
         }
+        if constexpr (F4) {
+            At[NMC] = label_item_f4(w[NMC]);
+        } else {
+            const uint32_t y = w[NMC] >> rsh;
 #pragma unroll
-        for (int m = 0; m < NML; ++m) {
-            const uint32_t y = w[NMC + m] >> rsh;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) At[NMC + m][j] = (int)(y & (0x01010101u << j));
+            for (int j = 0; j < 4; ++j) At[NMC][j] = (int)(y & (0x01010101u << j));
         }
     };
     uint32_t dmax = 0u;                                              // largest 2 * distance this lane packed
@@ -660,47 +680,10 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
         v4i addr_p = {0, 0, 0, 0}, d2_p = {0, 0, 0, 0}, lab_p = {0, 0, 0, 0};
         // the MFMAs of (group g, query group h) with the increments and adds of the PREVIOUS pair between them
         auto fused = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab, uint32_t& i0, uint32_t& i1, uint32_t& i2, uint32_t& i3) {
-            if (NML == 2 && CACHE) {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")
-                             XMH_W_MFMA("lab", "al1", "bl1", "lab") XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_MFMA("addr", "a0", "ba0", "cq")
-                             XMH_W_ADD("ap1", "i1") XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_ADD("ap2", "i2") XMH_W_MFMA("d2", "a0", "bd0", "kq")
-                             XMH_W_ADD("ap3", "i3") XMH_W_MFMA("d2", "a1", "bd1", "d2")
-                             : [lab] "=&v"(lab), [addr] "=&v"(addr), [d2] "=&v"(d2), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [al1] "v"(At[NMI - 1]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]),
-                               [bd0] "v"(bD[h][0]), [bd1] "v"(bD[h][1]), [bl0] "v"(bL[h][0]), [bl1] "v"(bL[h][NML - 1]), [lab0] "v"(lab0), [cq] "v"(cq[h]),
-                               [kq] "v"(kq[h]), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]),
-                               [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3])
-                             : "memory");
-            } else if (NML == 2) {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")
-                             XMH_W_MFMA("lab", "al1", "bl1", "lab") XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_ADD("ap1", "i1")
-                             XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap2", "i2") XMH_W_ADD("ap3", "i3") XMH_W_MFMA("addr", "a1", "ba1", "addr")
-                             : [lab] "=&v"(lab), [addr] "=&v"(addr), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [al1] "v"(At[NMI - 1]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]),
-                               [bl0] "v"(bL[h][0]), [bl1] "v"(bL[h][NML - 1]), [lab0] "v"(lab0), [cq] "v"(cq[h]), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]),
-                               [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3])
-                             : "memory");
-            } else if (CACHE) {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")
-                             XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap1", "i1")
-                             XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_ADD("ap2", "i2") XMH_W_MFMA("d2", "a0", "bd0", "kq") XMH_W_ADD("ap3", "i3")
-                             XMH_W_MFMA("d2", "a1", "bd1", "d2")
-                             : [lab] "=&v"(lab), [addr] "=&v"(addr), [d2] "=&v"(d2), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bd0] "v"(bD[h][0]),
-                               [bd1] "v"(bD[h][1]), [bl0] "v"(bL[h][0]), [lab0] "v"(lab0), [cq] "v"(cq[h]), [kq] "v"(kq[h]), [lp0] "v"(lab_p[0]),
-                               [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]),
-                               [ap3] "v"(addr_p[3])
-                             : "memory");
-            } else {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")
-                             XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_ADD("ap1", "i1") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap2", "i2")
-                             XMH_W_ADD("ap3", "i3") XMH_W_MFMA("addr", "a1", "ba1", "addr")
-                             : [lab] "=&v"(lab), [addr] "=&v"(addr), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bl0] "v"(bL[h][0]), [lab0] "v"(lab0),
-                               [cq] "v"(cq[h]), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]),
-                               [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3])
-                             : "memory");
-            }
+            if constexpr (F4 && CACHE) XMH_W_FUSED_CACHE(XMH_W_MFMA_F4);
+            else if constexpr (F4) XMH_W_FUSED_PLAIN(XMH_W_MFMA_F4);
+            else if constexpr (CACHE) XMH_W_FUSED_CACHE(XMH_W_MFMA);
+            else XMH_W_FUSED_PLAIN(XMH_W_MFMA);
         };
         // the cache word of the pair whose increments the statement above just made (d: that pair's 2 * distance results, a statement old)
         auto pack = [&](uint32_t& w, const v4i& d, uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3) {
@@ -717,12 +700,10 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
         };
         // the first statement of a batch: nothing to consume yet; closed by 8 wait states (the next statement's consumers read these results)
         auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab) {
-            if (NML == 2) {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") XMH_W_MFMA("lab", "al1", "bl1", "lab")
-                             : [lab] "=&v"(lab)
-                             : [al0] "v"(At[2]), [al1] "v"(At[NMI - 1]), [bl0] "v"(bL[h][0]), [bl1] "v"(bL[h][NML - 1]), [lab0] "v"(lab0));
+            if constexpr (F4) {
+                asm volatile("s_nop 3\n\t" XMH_W_MFMA_F4("lab", "al0", "bl0", "lab0") : [lab] "=&v"(lab) : [al0] "v"(At[2]), [bl0] "v"(bL[h]), [lab0] "v"(lab0));
             } else {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") : [lab] "=&v"(lab) : [al0] "v"(At[2]), [bl0] "v"(bL[h][0]), [lab0] "v"(lab0));
+                asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") : [lab] "=&v"(lab) : [al0] "v"(At[2]), [bl0] "v"(bL[h]), [lab0] "v"(lab0));
             }
             if (CACHE) {
                 asm volatile("s_nop 3\n\t" XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_MFMA("d2", "a0", "bd0", "kq")
@@ -738,21 +719,12 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
         };
         // the last pair of a batch: its increments and adds (live: the tiles of the last statements stay untouched until here)
         auto consume = [&](uint32_t& i0, uint32_t& i1, uint32_t& i2, uint32_t& i3, const v4i (&live)[NMI]) {
-            if constexpr (NMI == 4) {
-                asm volatile(XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2") XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0")
-                             XMH_W_ADD("ap1", "i1") XMH_W_ADD("ap2", "i2") XMH_W_ADD("ap3", "i3")
-                             : [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]),
-                               [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[2]), "v"(live[3])
-                             : "memory");
-            } else {
-                asm volatile(XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2") XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0")
-                             XMH_W_ADD("ap1", "i1") XMH_W_ADD("ap2", "i2") XMH_W_ADD("ap3", "i3")
-                             : [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
-                             : [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]),
-                               [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[2])
-                             : "memory");
-            }
+            asm volatile(XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2") XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0")
+                         XMH_W_ADD("ap1", "i1") XMH_W_ADD("ap2", "i2") XMH_W_ADD("ap3", "i3")
+                         : [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
+                         : [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]),
+                           [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[2])
+                         : "memory");
         };
         auto group = [&](auto gc) {
             constexpr int G = decltype(gc)::value;
@@ -768,8 +740,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
                 }
                 addr_p = addr; d2_p = d2; lab_p = lab;
                 if (G > 0 && h == 0) {                                 // the previous group's tiles may be reused from here on, not earlier
-                    if constexpr (NMI == 4) asm volatile("" ::"v"(A[G > 0 ? G - 1 : 0][0]), "v"(A[G > 0 ? G - 1 : 0][1]), "v"(A[G > 0 ? G - 1 : 0][2]), "v"(A[G > 0 ? G - 1 : 0][3]));
-                    else asm volatile("" ::"v"(A[G > 0 ? G - 1 : 0][0]), "v"(A[G > 0 ? G - 1 : 0][1]), "v"(A[G > 0 ? G - 1 : 0][2]));
+                    asm volatile("" ::"v"(A[G > 0 ? G - 1 : 0][0]), "v"(A[G > 0 ? G - 1 : 0][1]), "v"(A[G > 0 ? G - 1 : 0][2]));
                 }
             }
         };
@@ -826,6 +797,9 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
     }
     if (CACHE && dmax >= 256u) *ovf = 1u;                            // every writer stores the same 1; read by the next launch
 }
+#undef XMH_W_FUSED_PLAIN
+#undef XMH_W_FUSED_CACHE
+#undef XMH_W_MFMA_F4
 #undef XMH_W_MFMA
 #undef XMH_W_MIN
 #undef XMH_W_ADD
@@ -1143,29 +1117,28 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
 #define XMH_AP2_SETA "v113", "v115", "v117", "v119", "v[112:113]", "v[114:115]", "v[116:117]", "v[118:119]"
 #define XMH_AP2_SETB "v121", "v123", "v125", "v127", "v[120:121]", "v[122:123]", "v[124:125]", "v[126:127]"
 #define XMH_AP2_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 %[" D "], %[" A "], %[" B "], " C "\n\t"
+#define XMH_AP2_MFMA_F4(D, A, B, C) "v_mfma_f32_16x16x128_f8f6f4 %[" D "], %[" A "], %[" B "], " C " cbsz:4 blgp:4\n\t"
 #define XMH_AP2_MAX(H, L) "v_max_i32 " H ", -1, %[" L "]\n\t"
 #define XMH_AP2_ADD(O, A, P) "ds_add_rtn_u64 %[" O "], %[" A "], " P "\n\t"
-// the consumers of the previous pair between the MFMAs of this one (two label tiles / one label tile), and alone (the last pair of a batch)
-#define XMH_AP2_FUSED2_(H0, H1, H2, H3, P0, P1, P2, P3)                                                                                   \
-    "s_nop 3\n\t" XMH_AP2_MFMA("lab", "a1", "q1", "0") XMH_AP2_MAX(H0, "l0") XMH_AP2_MAX(H1, "l1") XMH_AP2_MAX(H2, "l2")                \
-    XMH_AP2_MFMA("lab", "a2", "q2", "%[lab]") XMH_AP2_MAX(H3, "l3") XMH_AP2_ADD("o0", "p0", P0) XMH_AP2_ADD("o1", "p1", P1)            \
-    XMH_AP2_MFMA("addr", "a0", "q0", "%[c0]") XMH_AP2_ADD("o2", "p2", P2) XMH_AP2_ADD("o3", "p3", P3)
-#define XMH_AP2_FUSED1_(H0, H1, H2, H3, P0, P1, P2, P3)                                                                                   \
-    "s_nop 3\n\t" XMH_AP2_MFMA("lab", "a1", "q1", "0") XMH_AP2_MAX(H0, "l0") XMH_AP2_MAX(H1, "l1") XMH_AP2_MAX(H2, "l2") XMH_AP2_MAX(H3, "l3") \
+// the consumers of the previous pair between the MFMAs of this one (LAB: the label instruction, XMH_AP2_MFMA for the i8 tile of at most 64
+// classes, XMH_AP2_MFMA_F4 for the FP4 tile of 65-128), and alone (the last pair of a batch)
+#define XMH_AP2_FUSED_(LAB, H0, H1, H2, H3, P0, P1, P2, P3)                                                                              \
+    "s_nop 3\n\t" LAB("lab", "a1", "q1", "0") XMH_AP2_MAX(H0, "l0") XMH_AP2_MAX(H1, "l1") XMH_AP2_MAX(H2, "l2") XMH_AP2_MAX(H3, "l3")    \
     XMH_AP2_MFMA("addr", "a0", "q0", "%[c0]") XMH_AP2_ADD("o0", "p0", P0) XMH_AP2_ADD("o1", "p1", P1) XMH_AP2_ADD("o2", "p2", P2)       \
     XMH_AP2_ADD("o3", "p3", P3)
 #define XMH_AP2_TAIL_(H0, H1, H2, H3, P0, P1, P2, P3)                                                                                     \
     XMH_AP2_MAX(H0, "l0") XMH_AP2_MAX(H1, "l1") XMH_AP2_MAX(H2, "l2") XMH_AP2_MAX(H3, "l3") XMH_AP2_ADD("o0", "p0", P0)                   \
     XMH_AP2_ADD("o1", "p1", P1) XMH_AP2_ADD("o2", "p2", P2) XMH_AP2_ADD("o3", "p3", P3)
-#define XMH_AP2_FUSED2(...) XMH_AP2_FUSED2_(__VA_ARGS__)
-#define XMH_AP2_FUSED1(...) XMH_AP2_FUSED1_(__VA_ARGS__)
+#define XMH_AP2_FUSED(...) XMH_AP2_FUSED_(__VA_ARGS__)
 #define XMH_AP2_TAIL(...) XMH_AP2_TAIL_(__VA_ARGS__)
 template <int NML, int NW, int NQ, bool CAPPED>
 __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2* __restrict__ below, const uint2* __restrict__ dpre,
                                                         const uint32_t* __restrict__ cap_ws, float* __restrict__ ap_part,
                                                         const uint32_t* __restrict__ items_total, uint32_t kcap) {
     using u64 = unsigned long long;
-    constexpr int NMI = 1 + NML;
+    static_assert(NML == 1 || NML == 2, "one i8 label tile (at most 64 classes) or one FP4 label tile (65-128 classes)");
+    constexpr bool F4 = NML == 2;                                    // the label tile is FP4 with K = 128 (label_query_f4 / label_item_f4)
+    constexpr int NMI = 2;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] 64-bit float-bit counters
     int chunk_id, qtile;
     if (!mfma_map_block(a, chunk_id, qtile)) return;                 // a.nqt counts tiles of NW * NQ * 16 queries here
@@ -1203,8 +1176,9 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
         }
     }
     // query operands: the address chain with k_scan_hist_r2's query bytes (+-64 even registers, +-32 odd ones; the item bytes are doubled, see
-    // build), started 128 popcount(q) above the lane's counter; the label tiles 0 / -1
-    v4i bq[NQ], bl[NQ][NML], cq[NQ];
+    // build), started 128 popcount(q) above the lane's counter; the label tile 0 / -1 (FP4: nibbles 0xA = -1.0, the chain starts at +0.0, so the
+    // result is +0.0 or a negative float, whose bits are an int below -1: max(bits, -1) is the mask either way)
+    v4i bq[NQ], bl[NQ], cq[NQ];
     float capf[NQ], acc[NQ];
     const int rsh = 4 * (slot & 1), rwi = slot >> 1;
 #pragma unroll
@@ -1225,13 +1199,14 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
             if (j & 1) bq[h][j] = on ? (int)(0x20202020u ^ (t * 0xc0u)) : 0;       // +32 / -32
             else bq[h][j] = on ? (int)(0x40404040u ^ (t << 7)) : 0;                // +64 / -64
         }
-#pragma unroll
-        for (int m = 0; m < NML; ++m) {
+        if constexpr (F4) {
+            bl[h] = label_query_f4(valid && slot < a.LW ? a.qlab[q * a.LW + slot] : 0u, 0xAu);
+        } else {
             uint32_t lw = 0u;
-            if (valid && 2 * m + rwi < a.LW) lw = a.qlab[q * a.LW + 2 * m + rwi];
+            if (valid && rwi < a.LW) lw = a.qlab[q * a.LW + rwi];
             lw >>= rsh;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bl[h][m][j] = (int)(((lw >> j) & 0x01010101u) * 0xffu);
+            for (int j = 0; j < 4; ++j) bl[h][j] = (int)(((lw >> j) & 0x01010101u) * 0xffu);
         }
         const int c0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) u64*)(cnt + h * ncell) + ql * 8 + (valid ? 128 * pcq : 0);
         cq[h] = v4i{c0, c0, c0, c0};
@@ -1246,9 +1221,8 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
     uint32_t wcur[4][NMI], wnxt[4][NMI];
     const int ritem = 4 * (lane & 3) + ((lane & 15) >> 2);
     const int wi_c = rwi < a.W ? rwi : a.W - 1;
-    int wi_l[NML];
-#pragma unroll
-    for (int m = 0; m < NML; ++m) wi_l[m] = 2 * m + rwi < a.LW ? 2 * m + rwi : (a.LW > 0 ? a.LW - 1 : 0);
+    const int lwi = F4 ? slot : rwi;                                 // an FP4 label tile holds 32 classes per slot, an i8 tile 16
+    const int wi_l = lwi < a.LW ? lwi : (a.LW > 0 ? a.LW - 1 : 0);
     auto load_words = [&](int64_t batch, uint32_t (&w)[4][NMI]) {       // k_scan_hist_r2's: whole batches without clamps or masks
         const int64_t first = batch * 64;
         if (first + 64 <= (int64_t)a.R) {
@@ -1257,8 +1231,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 w[g][0] = pc[g * 16 * a.W];
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][1 + m] = pl[g * 16 * a.LW + wi_l[m]];
+                w[g][1] = pl[g * 16 * a.LW + wi_l];
             }
         } else {
 #pragma unroll
@@ -1267,8 +1240,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
                 const int64_t it = item < a.R ? item : (int64_t)a.R - 1;
                 const uint32_t ok = item < a.R ? 0xffffffffu : 0u;   // items past the end: all-zero codes, no labels -- they come after every real item
                 w[g][0] = a.rbits[it * a.W + wi_c] & ok;             // of their bucket and are never relevant, so they change no credit
-#pragma unroll
-                for (int m = 0; m < NML; ++m) w[g][1 + m] = a.rlab[it * a.LW + wi_l[m]] & ok;
+                w[g][1] = a.rlab[it * a.LW + wi_l] & ok;
             }
         }
     };
@@ -1281,11 +1253,12 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
         At[0][1] = (int)(xa & 0x04040404u);
         At[0][2] = (int)(xb & 0x02020202u);
         At[0][3] = (int)(xb & 0x04040404u);
+        if constexpr (F4) {
+            At[1] = label_item_f4(w[1]);
+        } else {
+            const uint32_t y = w[1] >> rsh;
 #pragma unroll
-        for (int m = 1; m < NMI; ++m) {
-            const uint32_t y = w[m] >> rsh;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) At[m][j] = (int)(y & (0x01010101u << j));
+            for (int j = 0; j < 4; ++j) At[1][j] = (int)(y & (0x01010101u << j));
         }
     };
     auto credit = [&](u64 old, uint32_t m, int h) {                  // k_scan_ap_c's, operation for operation
@@ -1309,39 +1282,39 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
         u64 oldA[4], oldB[4];
         v4i addr_p, lab_p;
         auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& lab) {      // first pair of a batch: nothing to consume; closed by 8 wait states
-            if constexpr (NML == 2)
-                asm volatile("s_nop 3\n\t" XMH_AP2_MFMA("lab", "a1", "q1", "0") XMH_AP2_MFMA("lab", "a2", "q2", "%[lab]") XMH_AP2_MFMA("addr", "a0", "q0", "%[c0]") "s_nop 7"
+            if constexpr (F4)
+                asm volatile("s_nop 3\n\t" XMH_AP2_MFMA_F4("lab", "a1", "q1", "0") XMH_AP2_MFMA("addr", "a0", "q0", "%[c0]") "s_nop 7"
                              : [lab] "=&v"(lab), [addr] "=&v"(addr)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a2] "v"(At[NMI - 1]), [q2] "v"(bl[h][NML - 1]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]));
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]));
             else
                 asm volatile("s_nop 3\n\t" XMH_AP2_MFMA("lab", "a1", "q1", "0") XMH_AP2_MFMA("addr", "a0", "q0", "%[c0]") "s_nop 7"
                              : [lab] "=&v"(lab), [addr] "=&v"(addr)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]));
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]));
         };
 #define XMH_AP2_OUTS(OLD) [lab] "=&v"(lab), [addr] "=&v"(addr), [o0] "=&v"(OLD[0]), [o1] "=&v"(OLD[1]), [o2] "=&v"(OLD[2]), [o3] "=&v"(OLD[3])
 #define XMH_AP2_PREV [p0] "v"(addr_p[0]), [p1] "v"(addr_p[1]), [p2] "v"(addr_p[2]), [p3] "v"(addr_p[3]), [l0] "v"(lab_p[0]), [l1] "v"(lab_p[1]), [l2] "v"(lab_p[2]), [l3] "v"(lab_p[3])
         auto fusedA = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& lab) {          // consumers into set A
-            if constexpr (NML == 2)
-                asm volatile(XMH_AP2_FUSED2(XMH_AP2_SETA)
+            if constexpr (F4)
+                asm volatile(XMH_AP2_FUSED(XMH_AP2_MFMA_F4, XMH_AP2_SETA)
                              : XMH_AP2_OUTS(oldA), "+{v[112:115]}"(incA01), "+{v[116:119]}"(incA23)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a2] "v"(At[NMI - 1]), [q2] "v"(bl[h][NML - 1]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
                              : "memory");
             else
-                asm volatile(XMH_AP2_FUSED1(XMH_AP2_SETA)
+                asm volatile(XMH_AP2_FUSED(XMH_AP2_MFMA, XMH_AP2_SETA)
                              : XMH_AP2_OUTS(oldA), "+{v[112:115]}"(incA01), "+{v[116:119]}"(incA23)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
                              : "memory");
         };
         auto fusedB = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& lab) {          // consumers into set B
-            if constexpr (NML == 2)
-                asm volatile(XMH_AP2_FUSED2(XMH_AP2_SETB)
+            if constexpr (F4)
+                asm volatile(XMH_AP2_FUSED(XMH_AP2_MFMA_F4, XMH_AP2_SETB)
                              : XMH_AP2_OUTS(oldB), "+{v[120:123]}"(incB01), "+{v[124:127]}"(incB23)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a2] "v"(At[NMI - 1]), [q2] "v"(bl[h][NML - 1]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
                              : "memory");
             else
-                asm volatile(XMH_AP2_FUSED1(XMH_AP2_SETB)
+                asm volatile(XMH_AP2_FUSED(XMH_AP2_MFMA, XMH_AP2_SETB)
                              : XMH_AP2_OUTS(oldB), "+{v[120:123]}"(incB01), "+{v[124:127]}"(incB23)
-                             : [a1] "v"(At[1]), [q1] "v"(bl[h][0]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
+                             : [a1] "v"(At[1]), [q1] "v"(bl[h]), [a0] "v"(At[0]), [q0] "v"(bq[h]), [c0] "v"(cq[h]), XMH_AP2_PREV
                              : "memory");
         };
         // the returns of set A / B are in (4 newer LDS operations in flight at most): credit them to query group h
@@ -1373,8 +1346,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
             else fusedA(A[G], H, addr, lab);
             addr_p = addr; lab_p = lab;
             if constexpr (G > 0 && H == 0) {                          // the previous group's tiles may be reused from here on, not earlier
-                if constexpr (NMI == 2) asm volatile("" ::"v"(A[G - 1][0]), "v"(A[G - 1][1]));
-                else asm volatile("" ::"v"(A[G - 1][0]), "v"(A[G - 1][1]), "v"(A[G - 1][NMI - 1]));
+                asm volatile("" ::"v"(A[G - 1][0]), "v"(A[G - 1][1]));
             }
             if constexpr (P >= 2) {
                 if constexpr ((P - 2) & 1) drainB((P - 2) % NQ, N4{});
