@@ -405,10 +405,11 @@ __global__ __launch_bounds__(256) void k_im2col_patch(const float* __restrict__ 
 }
 
 // ---- x[b][0] = cls + pos[0]; x[b][1+p] = patch[b*NP+p] + pos[1+p]; then LayerNorm (ln_pre) ----------------
+// pre (or NULL): the rows before the LayerNorm are kept as well
 __global__ __launch_bounds__(256) void k_vit_assemble(const float* __restrict__ patch, const float* __restrict__ cls,
                                                       const float* __restrict__ pos, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float eps, float* __restrict__ x,
-                                                      int64_t B, int NP, int D) {
+                                                      float* __restrict__ pre, int64_t B, int NP, int D) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int L = NP + 1;
@@ -423,6 +424,7 @@ __global__ __launch_bounds__(256) void k_vit_assemble(const float* __restrict__ 
         const int c = j * 64 + lane;
         v[j] = c < D ? src[c] + pos[(int64_t)t * D + c] : 0.0f;
         s += v[j];
+        if (pre && c < D) pre[row * D + c] = v[j];           // the stream in front of ln_pre, for its backward (xmh_vit_train_forward)
     }
     const float mean = wave_sum(s) / (float)D;
     float q = 0.0f;
@@ -801,6 +803,17 @@ int gather_packed_rows(const float* packed, int64_t ldp, const int32_t* offs, co
     return XMH_OK;
 }
 
+int vit_assemble_keep(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, float eps, float* x,
+                      float* pre, int64_t B, int n_patches, int D, hipStream_t st) {
+    if (B < 0 || n_patches <= 0 || D <= 0 || D > 64 * kLnMaxPerLane) return fail(XMH_EINVAL, "xmh_vit_assemble: bad shape");
+    if (B == 0) return XMH_OK;
+    if (!patch_out || !cls || !pos || !gamma || !beta || !x) return fail(XMH_EINVAL, "xmh_vit_assemble: null pointer");
+    hipLaunchKernelGGL(k_vit_assemble, dim3((unsigned)ceil_div(B * (n_patches + 1), 4)), dim3(256), 0, st, patch_out, cls, pos, gamma, beta, eps, x,
+                       pre, B, n_patches, D);
+    XMH_LAUNCH_CHECK("xmh_vit_assemble");
+    return XMH_OK;
+}
+
 int im2col_planes(const float* image, int64_t B, int channels, int resolution, int patch, float* cols, const Planes& p, hipStream_t st) {
     if (B < 0 || channels <= 0 || patch <= 0 || resolution % patch || patch % 4) return fail(XMH_EINVAL, "xmh_im2col_patch: bad geometry res=%d patch=%d", resolution, patch);
     if (B == 0) return XMH_OK;
@@ -839,13 +852,7 @@ extern "C" int xmh_im2col_patch(const float* image, int64_t B, int channels, int
 
 extern "C" int xmh_vit_assemble(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta,
                                 float eps, float* x, int64_t B, int n_patches, int D, xmh_stream_t stream) {
-    if (B < 0 || n_patches <= 0 || D <= 0 || D > 64 * kLnMaxPerLane) return xmh::fail(XMH_EINVAL, "xmh_vit_assemble: bad shape");
-    if (B == 0) return XMH_OK;
-    if (!patch_out || !cls || !pos || !gamma || !beta || !x) return xmh::fail(XMH_EINVAL, "xmh_vit_assemble: null pointer");
-    hipLaunchKernelGGL(k_vit_assemble, dim3((unsigned)xmh::ceil_div(B * (n_patches + 1), 4)), dim3(256), 0, xmh::as_stream(stream), patch_out, cls, pos,
-                       gamma, beta, eps, x, B, n_patches, D);
-    XMH_LAUNCH_CHECK("xmh_vit_assemble");
-    return XMH_OK;
+    return xmh::vit_assemble_keep(patch_out, cls, pos, gamma, beta, eps, x, nullptr, B, n_patches, D, xmh::as_stream(stream));
 }
 
 extern "C" int xmh_text_embed(const int64_t* ids, const float* tok_emb, const float* pos, float* x, int32_t* eos_index, int64_t B,

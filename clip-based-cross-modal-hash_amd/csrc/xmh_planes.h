@@ -116,5 +116,8 @@ int gather_packed_rows(const float* packed, int64_t ldp, const int32_t* offs, co
 // pass of its own, for the saved-activation forward (xmh_gemm.hip)
 int quickgelu_planes(const float* u, int64_t rows, int64_t cols, float* f, const Planes& p, hipStream_t st);
 int im2col_planes(const float* image, int64_t B, int channels, int resolution, int patch, float* cols, const Planes& p, hipStream_t st);
+// xmh_vit_assemble that also keeps the rows in front of ln_pre (pre [B, n_patches + 1, D], may be null): what ln_pre's backward reads
+int vit_assemble_keep(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, float eps, float* x,
+                      float* pre, int64_t B, int n_patches, int D, hipStream_t st);
 
 }  // namespace xmh

@@ -91,6 +91,14 @@ class ClipBlockGrads(C.Structure):             # xmh_clip_block_grads
     _fields_ = [(n, vp) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")]
 
 
+class VitGrads(C.Structure):                   # xmh_vit_grads
+    _fields_ = [(n, vp) for n in ("proj", "ln_post_w", "ln_post_b", "ln_pre_w", "ln_pre_b", "pos", "cls", "conv1")] + [("blocks", C.POINTER(ClipBlockGrads))]
+
+
+class TextGrads(C.Structure):                  # xmh_text_grads
+    _fields_ = [(n, vp) for n in ("proj", "ln_final_w", "ln_final_b", "pos", "tok")] + [("blocks", C.POINTER(ClipBlockGrads))]
+
+
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
 PROTOTYPES = {
     "xmh_version": (i32, []),
@@ -150,6 +158,14 @@ PROTOTYPES = {
     "xmh_text_forward": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "xmh_text_forward_packed": (i32, [C.POINTER(TextWeights), vp, vp, i64, i64, i32, i32, vp, vp, sz, vp]),
     "xmh_text_forward_packed_dev": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, i32, vp, vp, vp, sz, vp]),
+    "xmh_vit_train_saved_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_vit_train_ws_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "xmh_vit_train_forward": (i32, [C.POINTER(VitWeights), vp, i64, vp, vp, sz, vp, sz, vp]),
+    "xmh_vit_backward": (i32, [C.POINTER(VitWeights), vp, i64, vp, sz, vp, C.POINTER(VitGrads), i32, vp, sz, vp]),
+    "xmh_text_train_saved_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_text_train_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_text_train_forward": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, vp, vp, vp, sz, vp, sz, vp]),
+    "xmh_text_backward": (i32, [C.POINTER(TextWeights), vp, vp, vp, i64, i32, vp, sz, vp, C.POINTER(TextGrads), i32, vp, sz, vp]),
     "xmh_head_workspace_bytes": (sz, [i64, i32, i32]),
     "xmh_head_dcmht": (i32, [C.POINTER(DcmhtHead), vp, i64, i32, vp, vp, vp, vp, sz, vp]),
     "xmh_head_dsph": (i32, [C.POINTER(Linear), vp, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -1,6 +1,7 @@
 """``BaseModel`` with the surface the reference's runner relies on (models/base.py:10-70): ``load_backbone``,
 ``encode_image`` / ``encode_text`` / ``object_function`` to override, ``forward``, ``freezen`` / ``unfreezen``,
-``from_config``.  Inference only: the forward pass runs in libxmh.so, so there is no autograd graph."""
+``from_config``.  ``forward`` is the inference pair (libxmh.so under no_grad, no autograd graph); ``forward_train`` is the
+differentiable one: both towers in exact fp32 behind torch.autograd (CLIP.encode_image_train / encode_text_train), then the heads."""
 from __future__ import annotations
 
 import os
@@ -57,6 +58,11 @@ class BaseModel(nn.Module):
         """both towers; with ``return_loss`` the method's objective instead of the pair (reference models/base.py:52-60)"""
         embeds = (self.encode_image(image), self.encode_text(text))
         return self.object_function(*embeds, labels=labels, indexs=indexs) if return_loss else embeds
+
+    def forward_train(self, image, text):
+        """the pair a training step differentiates (what the reference's ``model(image, text)`` is in train mode): gradients reach
+        every parameter of the heads and of both towers that has requires_grad"""
+        return (self.hash.encode_img(self.backbone.encode_image_train(image)), self.hash.encode_txt(self.backbone.encode_text_train(text)))
 
     @classmethod
     def from_config(cls, cfg, output_dim=None, train_num=None):

@@ -262,6 +262,165 @@ class _BlocksTrain(torch.autograd.Function):
         return (None, None, None, gx, *gp)
 
 
+# ---- the two towers behind torch.autograd --------------------------------------------------------------------------
+def _tower_params_ok(params, who):
+    for p in params:
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("%s needs contiguous fp32 CUDA/HIP parameters (got %s %s); there is no CPU fallback" % (who, p.dtype, p.device))
+
+
+def _block_params(tr):
+    return [p for blk in tr.resblocks for p in Transformer._train_params(blk)]
+
+
+def _grad_structs(layers, gp_blocks):
+    grads = (_lib.ClipBlockGrads * max(layers, 1))()
+    for i in range(layers):
+        grads[i] = _lib.ClipBlockGrads(*[_addr(t) for t in gp_blocks[12 * i:12 * i + 12]])
+    return grads
+
+
+def _upstream(g):
+    g = g.detach().to(torch.float32)
+    return g if g.is_contiguous() else g.contiguous()
+
+
+_VIT_OWN = 8       # conv1, class_embedding, positional_embedding, ln_pre w/b, ln_post w/b, proj; the blocks' parameters follow
+
+
+def _vit_params(vis):
+    return [vis.conv1.weight, vis.class_embedding, vis.positional_embedding, vis.ln_pre.weight, vis.ln_pre.bias, vis.ln_post.weight,
+            vis.ln_post.bias, vis.proj] + _block_params(vis.transformer)
+
+
+def _vit_exact_desc(vis, params, keep):
+    """xmh_vit_weights over the parameters IN PLACE; only `x @ proj` needs a copy (the descriptor holds proj transposed)"""
+    _tower_params_ok(params, "encode_image_train")
+    conv, cls, pos, lpw, lpb, low, lob, proj = (p.detach() for p in params[:_VIT_OWN])
+    tr = vis.transformer
+    blocks = _exact_desc(tr, params[_VIT_OWN:], keep)
+    proj_t = proj.t().contiguous()
+    keep.extend((proj_t, blocks))
+    keep.extend(params[:_VIT_OWN])
+    width = conv.shape[0]
+    heads = tr.resblocks[0].heads if len(tr.resblocks) else max(width // 64, 1)
+    return _lib.VitWeights(vis.input_resolution, vis.patch_size, width, heads, len(tr.resblocks), proj.shape[1],
+                           _lib.Linear(conv.data_ptr(), None, None, None, width, conv[0].numel()), cls.data_ptr(), pos.data_ptr(), lpw.data_ptr(),
+                           lpb.data_ptr(), low.data_ptr(), lob.data_ptr(), _lib.Linear(proj_t.data_ptr(), None, None, None, proj.shape[1], width), blocks)
+
+
+def _vit_sizes(vis, B):
+    L, width = vis.positional_embedding.shape
+    return L, width, 3 * vis.patch_size ** 2, vis.proj.shape[1], len(vis.transformer.resblocks)
+
+
+class _VitTrain(torch.autograd.Function):
+    """forward = xmh_vit_train_forward, backward = xmh_vit_backward"""
+
+    @staticmethod
+    def forward(ctx, vis, image, *params):
+        B = image.shape[0]
+        L, width, conv_k, out_dim, layers = _vit_sizes(vis, B)
+        keep = []
+        desc = _vit_exact_desc(vis, params, keep)
+        sbytes = lib.xmh_vit_train_saved_bytes(B, L, width, layers)
+        nbytes = lib.xmh_vit_train_ws_bytes(B, L, width, conv_k, out_dim)
+        buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=image.device)
+        ws = _workspace(nbytes, image.device)
+        out = torch.empty(B, out_dim, dtype=torch.float32, device=image.device)
+        check(lib.xmh_vit_train_forward(ctypes.byref(desc), ptr(image), B, ptr(out), ptr(buf), sbytes, ptr(ws), nbytes, current_stream()),
+              "xmh_vit_train_forward")
+        ctx.vis = vis
+        ctx.save_for_backward(image, buf, *params)      # saved parameters: autograd notices an in-place change before backward
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        image, buf, *params = ctx.saved_tensors
+        vis = ctx.vis
+        B = image.shape[0]
+        L, width, conv_k, out_dim, layers = _vit_sizes(vis, B)
+        need = ctx.needs_input_grad[2:]
+        gp = [torch.empty_like(p) if need[i] else None for i, p in enumerate(params)]
+        blocks = _grad_structs(layers, gp[_VIT_OWN:])
+        conv, cls, pos, lpw, lpb, low, lob, proj = gp[:_VIT_OWN]
+        grads = _lib.VitGrads(_addr(proj), _addr(low), _addr(lob), _addr(lpw), _addr(lpb), _addr(pos), _addr(cls), _addr(conv), blocks)
+        keep = []
+        desc = _vit_exact_desc(vis, params, keep)
+        gg = _upstream(g)
+        nbytes = lib.xmh_vit_train_ws_bytes(B, L, width, conv_k, out_dim)
+        ws = _workspace(nbytes, gg.device)
+        check(lib.xmh_vit_backward(ctypes.byref(desc), ptr(image), B, ptr(buf), buf.numel() * 4, ptr(gg), ctypes.byref(grads), 0, ptr(ws), nbytes,
+                                   current_stream()), "xmh_vit_backward")
+        return (None, None, *gp)
+
+
+_TEXT_OWN = 5      # token_embedding.weight, positional_embedding, ln_final w/b, text_projection; the blocks' parameters follow
+
+
+def _text_train_params(clip):
+    return [clip.token_embedding.weight, clip.positional_embedding, clip.ln_final.weight, clip.ln_final.bias, clip.text_projection] + \
+        _block_params(clip.transformer)
+
+
+def _text_exact_desc(clip, params, keep):
+    _tower_params_ok(params, "encode_text_train")
+    tok, pos, lfw, lfb, proj = (p.detach() for p in params[:_TEXT_OWN])
+    tr = clip.transformer
+    blocks = _exact_desc(tr, params[_TEXT_OWN:], keep)
+    proj_t = proj.t().contiguous()
+    keep.extend((proj_t, blocks))
+    keep.extend(params[:_TEXT_OWN])
+    width = tok.shape[1]
+    heads = tr.resblocks[0].heads if len(tr.resblocks) else max(width // 64, 1)
+    return _lib.TextWeights(tok.shape[0], pos.shape[0], width, heads, len(tr.resblocks), proj.shape[1], tok.data_ptr(), pos.data_ptr(),
+                            lfw.data_ptr(), lfb.data_ptr(), _lib.Linear(proj_t.data_ptr(), None, None, None, proj.shape[1], width), blocks)
+
+
+class _TextTrain(torch.autograd.Function):
+    """forward = xmh_text_train_forward, backward = xmh_text_backward"""
+
+    @staticmethod
+    def forward(ctx, clip, ids, kpm, *params):
+        B, L = ids.shape
+        width, out_dim, layers = params[0].shape[1], params[4].shape[1], len(clip.transformer.resblocks)
+        keep = []
+        desc = _text_exact_desc(clip, params, keep)
+        sbytes = lib.xmh_text_train_saved_bytes(B, L, width, layers)
+        nbytes = lib.xmh_text_train_ws_bytes(B, L, width, out_dim)
+        buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=ids.device)
+        ws = _workspace(nbytes, ids.device)
+        out = torch.empty(B, out_dim, dtype=torch.float32, device=ids.device)
+        eos = torch.empty(B, dtype=torch.int32, device=ids.device)
+        check(lib.xmh_text_train_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, ptr(out), ptr(eos), ptr(buf), sbytes, ptr(ws), nbytes,
+                                         current_stream()), "xmh_text_train_forward")
+        ctx.clip, ctx.kpm = clip, kpm
+        ctx.save_for_backward(ids, eos, buf, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        ids, eos, buf, *params = ctx.saved_tensors
+        clip = ctx.clip
+        B, L = ids.shape
+        width, out_dim, layers = params[0].shape[1], params[4].shape[1], len(clip.transformer.resblocks)
+        need = ctx.needs_input_grad[3:]
+        gp = [torch.empty_like(p) if need[i] else None for i, p in enumerate(params)]
+        blocks = _grad_structs(layers, gp[_TEXT_OWN:])
+        tok, pos, lfw, lfb, proj = gp[:_TEXT_OWN]
+        grads = _lib.TextGrads(_addr(proj), _addr(lfw), _addr(lfb), _addr(pos), _addr(tok), blocks)
+        keep = []
+        desc = _text_exact_desc(clip, params, keep)
+        gg = _upstream(g)
+        nbytes = lib.xmh_text_train_ws_bytes(B, L, width, out_dim)
+        ws = _workspace(nbytes, gg.device)
+        check(lib.xmh_text_backward(ctypes.byref(desc), ptr(ids), ptr(ctx.kpm), ptr(eos), B, L, ptr(buf), buf.numel() * 4, ptr(gg),
+                                    ctypes.byref(grads), 0, ptr(ws), nbytes, current_stream()), "xmh_text_backward")
+        return (None, None, None, *gp)
+
+
 class VisionTransformer(nn.Module):
     def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim, return_patches=False):
         super().__init__()
@@ -345,6 +504,57 @@ class CLIP(nn.Module):
     @torch.no_grad()
     def encode_image(self, image):
         return self.visual.run(image)
+
+    def encode_image_train(self, image):
+        """encode_image in exact fp32 behind torch.autograd: the result carries a graph whose backward is ONE call of
+        xmh_vit_backward.  Gradients go to exactly the parameters of the image tower with requires_grad (none to the image).  Under
+        no_grad, or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
+        vis = self.visual
+        if self.return_patches or vis.return_patches:
+            raise NotImplementedError("encode_image_train returns the cls feature only: the patch tokens (return_patches=True) feed MITH's "
+                                      "head, whose backward is not built")
+        image = ops._f32c(image).contiguous()
+        if image.dim() != 4 or image.shape[1:] != (3, vis.input_resolution, vis.input_resolution):
+            raise ValueError("image batch is %s, the tower takes [B, 3, %d, %d]" % (tuple(image.shape), vis.input_resolution, vis.input_resolution))
+        params = _vit_params(vis)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _VitTrain.apply(vis, image, *params)
+        B, (L, width), out_dim = image.shape[0], vis.positional_embedding.shape, vis.proj.shape[1]
+        keep = []
+        desc = _vit_exact_desc(vis, params, keep)
+        nbytes = lib.xmh_clip_workspace_bytes(B, L, width, 3 * vis.patch_size ** 2, 0, ops.PREC_F32X)
+        ws = _workspace(nbytes, image.device)
+        out = torch.empty(B, out_dim, dtype=torch.float32, device=image.device)
+        check(lib.xmh_vit_b32_forward(ctypes.byref(desc), ptr(image), B, ops.PREC_F32X, ptr(out), None, ptr(ws), nbytes, current_stream()),
+              "xmh_vit_b32_forward")
+        return out
+
+    def encode_text_train(self, text, key_padding_mask=None):
+        """encode_text in exact fp32 behind torch.autograd, on the padded rows: gradients go to exactly the parameters of the text
+        tower with requires_grad (logit_scale is no input: its .grad stays None, as in the reference, where nothing reads it).  Under
+        no_grad, or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
+        if self.return_patches:
+            raise NotImplementedError("encode_text_train returns the EOS feature only: the token outputs (return_patches=True) feed MITH's "
+                                      "head, whose backward is not built")
+        if not text.is_cuda:
+            raise RuntimeError("xmh ops need CUDA/HIP tensors (got %s); there is no CPU fallback" % text.device)
+        ids = text.to(torch.int64).contiguous()
+        if ids.dim() != 2 or ids.shape[1] > self.context_length:
+            raise ValueError("token batch is %s, the tower takes [B, L] with L <= %d" % (tuple(ids.shape), self.context_length))
+        kpm = None if key_padding_mask is None else key_padding_mask.to(device=ids.device, dtype=torch.uint8).contiguous()
+        params = _text_train_params(self)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _TextTrain.apply(self, ids, kpm, *params)
+        B, L = ids.shape
+        width, out_dim = params[0].shape[1], params[4].shape[1]
+        keep = []
+        desc = _text_exact_desc(self, params, keep)
+        nbytes = lib.xmh_clip_workspace_bytes(B, L, width, 0, 0, ops.PREC_F32X)
+        ws = _workspace(nbytes, ids.device)
+        out = torch.empty(B, out_dim, dtype=torch.float32, device=ids.device)
+        check(lib.xmh_text_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, ops.PREC_F32X, ptr(out), None, None, ptr(ws), nbytes,
+                                   current_stream()), "xmh_text_forward")
+        return out
 
     def _text_desc(self, precision: int, keep: list):
         blocks = _blocks_desc(list(self.transformer.resblocks), precision, keep)

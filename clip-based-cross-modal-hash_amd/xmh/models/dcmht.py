@@ -2,8 +2,10 @@
 (:72-155: similarity_loss / soft_argmax_hash_loss / our_loss / object_function) through xmh_loss.hip.  `our_loss` /
 `object_function` are differentiable with respect to the two code matrices (`_Objective`: the gradient kernels of xmh_loss.hip
 behind torch.autograd, i.e. what `loss.backward()` of runners/DCMHT/runner.py:124 hands to the hash heads).  In `.train()` mode the
-heads carry that gradient on to every one of their parameters and to the embeddings (heads.py, xmh_head_grad.hip); the backward
-of the CLIP towers is not built, so the backbone is trained frozen: embeddings under no_grad, `model.hash(...)`."""
+heads carry that gradient on to every one of their parameters and to the embeddings (heads.py, xmh_head_grad.hip), and
+`forward_train` (base.py) hands it on to both CLIP towers (clip.py: encode_image_train / encode_text_train, xmh_tower_grad.hip),
+so a step fine-tunes the backbone as the reference's does.  `forward` / `encode_image` / `encode_text` stay the inference pair:
+embeddings under no_grad."""
 import torch
 
 from .. import retrieval as R

@@ -9,7 +9,8 @@ that workbook, read by codetable.hyp_threshold); otherwise unset -- the model co
 call raises ValueError.
 
 In `.train()` mode the two heads (heads.py::DSPHLinearHash) run dropout with a keep mask drawn on the device and carry the loss
-gradient on to `fc.weight`, `fc.bias` and the embeddings (xmh_head_grad.hip); the backward of the CLIP towers is not built."""
+gradient on to `fc.weight`, `fc.bias` and the embeddings (xmh_head_grad.hip); `forward_train` (base.py) hands it on to both CLIP
+towers (xmh_tower_grad.hip)."""
 import torch
 import torch.nn as nn
 

@@ -238,6 +238,10 @@ class MITH(BaseModel):
         txt_eos, txt_tokens, _, new_mask = self.backbone.encode_text(text, key_padding_mask=key_padding_mask, masked_rows="zero")
         return self.hash.encode_txt(txt_eos, txt_tokens, new_mask)
 
+    def forward_train(self, image, text):
+        raise NotImplementedError("MITH's head has no backward (localized token aggregation, bitwise hashing), and it reads the towers' "
+                                  "token outputs (return_patches=True), which the differentiable towers do not return")
+
     def forward(self, image, text, key_padding_mask=None, labels=None, indexs=None, return_loss=False):
         img, txt = towers.run_both(lambda: self.encode_image(image), lambda: self.encode_text(text, key_padding_mask=key_padding_mask))
         if return_loss:                                   # reference :71-74: no label_sim is passed, so its assertion fires

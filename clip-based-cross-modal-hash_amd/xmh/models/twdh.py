@@ -52,6 +52,9 @@ class TwDH(BaseModel):
             out[k] = ops.pair_softmax(ops.gemm_nt(long_hash, w))  # quantization(long_hash.matmul(v)), TwDH.py:73,83
         return out
 
+    def forward_train(self, image, text):
+        raise NotImplementedError("TwDH's head has no backward (the long code and its short-code transforms)")
+
     def encode_image(self, image):
         long_hash = self.hash.encode_img(self.backbone.encode_image(image))
         return long_hash, self._short(long_hash)

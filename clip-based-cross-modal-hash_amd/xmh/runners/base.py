@@ -211,9 +211,9 @@ class BaseTrainer:
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t}, mAP: {self.max_mapt2i}")
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("train_epoch is not built: the losses and the DCMHT / DSPH hash heads have their backward and "
-                                  "build_optimizer gives the reference's BertAdam (a frozen backbone trains the heads), but the "
-                                  "backward of the CLIP towers and of MITH's / TwDH's heads is still missing")
+        raise NotImplementedError("train_epoch is built for DCMHT and DSPH only (their losses, hash heads and both CLIP towers have a "
+                                  "backward, and build_optimizer gives the reference's BertAdam): the backward of MITH's and TwDH's "
+                                  "heads is still missing, and MITH needs the token outputs of the towers differentiable too")
 
     def compute_loss(self, *a, **k):
         raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")

@@ -42,6 +42,41 @@ class _MethodTrainer(BaseTrainer):
                    world_size=world_size, distributed=distributed, **extra)
 
 
+def _train_epoch(trainer, epoch: int):
+    """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser).  The
+    optimiser is built on the first call, when the instance has none yet."""
+    if trainer.distributed:
+        raise NotImplementedError("train_epoch with distributed=True: there is no all-reduce of the gradients")
+    if getattr(trainer, "optimizer", None) is None:
+        built = trainer.build_optimizer(trainer.cfg.get("optimizer"))
+        trainer.optimizer, trainer.lr_schedu = built[0], built[-1]
+        trainer.optimizer_loss = built[1] if len(built) == 3 else None
+    optimizer_loss = getattr(trainer, "optimizer_loss", None)      # DSPH: the proxies' own optimiser
+    trainer.change_state(mode="train")
+    trainer.logger.info(">>>>>> epochs: %d/%d" % (epoch, trainer.epochs))
+    all_loss = 0
+    times = 0
+    for image, text, key_padding_mask, label, index in trainer.train_loader:
+        trainer.global_step += 1
+        times += 1
+        image = image.to(trainer.device, non_blocking=True)
+        text = text.to(trainer.device, non_blocking=True)
+        index = index.numpy()
+        hash_img, hash_text = trainer.model.forward_train(image, text)
+        loss = trainer.compute_loss(img_hash=hash_img, txt_hash=hash_text, label=label, index=index, epoch=epoch, times=times,
+                                    global_step=trainer.global_step)
+        all_loss += loss.detach()
+        trainer.optimizer.zero_grad()
+        if optimizer_loss is not None:
+            optimizer_loss.zero_grad()
+        loss.backward()
+        trainer.optimizer.step()
+        if optimizer_loss is not None:
+            optimizer_loss.step()
+    rates = "-".join("%.9f" % r for r in sorted(set(trainer.optimizer.get_lr())))
+    trainer.logger.info(f">>>>>> [{epoch}/{trainer.epochs}] loss: {all_loss / len(trainer.train_loader)}, lr: {rates}")
+
+
 @registry.register_runner("DCMHTTrainer")
 class DCMHTTrainer(_MethodTrainer):
     """runners/DCMHT/runner.py: the model emits 2K pair probabilities; bit j = +1 iff p[j,1] > p[j,0] (:82-95)."""
@@ -62,6 +97,10 @@ class DCMHTTrainer(_MethodTrainer):
     @classmethod
     def pack_hash_code(cls, code, out, row_index, flags):
         R.pack_pair_argmax(code.reshape(code.shape[0], -1), out=out, row_index=row_index)
+
+    def train_epoch(self, epoch: int):
+        """runners/DCMHT/runner.py:107-128"""
+        _train_epoch(self, epoch)
 
     def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
         """runners/DCMHT/runner.py:97-105: the objective of one batch.  The returned loss is differentiable with respect to
@@ -90,6 +129,10 @@ class DSPHTrainer(_MethodTrainer):
                                          weight_decay=hyp.get("weight_decay", 0.0005))
         self.logger.info("Building optimizer!")
         return optimizer, optimizer_loss, lr_schedu
+
+    def train_epoch(self, epoch: int):
+        """runners/DSPH/runner.py:104-127: as DCMHT's, and the proxies' SGD steps beside BertAdam"""
+        _train_epoch(self, epoch)
 
     def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
         """runners/DSPH/runner.py:93-101: the HyP objective of one batch (xmh_hyp.hip behind torch.autograd), differentiable with
@@ -128,6 +171,10 @@ class MITHTrainer(_MethodTrainer):
             self.print_loss_dict(loss_dict, bits=img_cls_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
         return all_loss
 
+    def train_epoch(self, epoch: int):
+        raise NotImplementedError("MITHTrainer.train_epoch: MITH's head (localized token aggregation, bitwise hashing) has no backward, "
+                                  "and the differentiable towers do not return the token outputs it reads")
+
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)
         return img_cls_hash + tokens_hash_i, txt_cls_hash + tokens_hash_t
@@ -143,6 +190,9 @@ class TwDHTrainer(DCMHTTrainer):
         self.long_dim = cfg.model.get("long_dim", 512)
         self.max_short, self.best_epoch_short = {}, {}
         super().__init__(cfg, *a, **k)
+
+    def train_epoch(self, epoch: int):
+        raise NotImplementedError("TwDHTrainer.train_epoch: TwDH's head (the long code and its short-code transforms) has no backward")
 
     def build_model(self, cfg_model, output_dim=16):
         super().build_model(cfg_model, output_dim=output_dim)

@@ -465,6 +465,49 @@ int xmh_text_forward_packed_dev(const xmh_text_weights* w, const int64_t* ids, c
                                 int precision, float* out_eos, float* out_tokens, void* workspace, size_t workspace_bytes,
                                 xmh_stream_t stream);
 
+/* The two towers in TRAINING mode: a forward that keeps what backward reads, and the backward to every parameter of
+ * the tower.  Exact fp32 throughout: the descriptors' w_f32 members point at the parameters in place (proj is still the TRANSPOSED
+ * projection, [out_dim, width]), the other members are not read.  The forwards are the calls of xmh_vit_b32_forward /
+ * xmh_text_forward in precision 2 with the block stack run through xmh_clip_blocks_forward_saved: same bits.  There is no
+ * return_patches mode and no gradient to the image.
+ * saved (xmh_*_train_saved_bytes, 256-byte aligned device memory): the block record of xmh_clip_blocks_forward_saved, the rows in
+ * front of ln_pre [B, L, width] (image only), and the B rows entering ln_post / ln_final.  workspace: xmh_*_train_ws_bytes, one
+ * size for the forward and the backward.  L of the image tower is (resolution / patch)^2 + 1, conv_k = 3 * patch * patch.
+ * Gradients have the PARAMETERS' own shapes: proj [width, out_dim] (not the descriptor's), pos [L, width] (text: [context, width],
+ * the rows at or beyond L zero), cls [width], conv1 [width, conv_k], tok [vocab, width] (dense; a row whose id does not occur is
+ * zero; ids outside the table count for the row the forward reads, 0 or vocab - 1).  NULL = a frozen parameter, and a product that
+ * nothing asked-for depends on is not launched.  `blocks`: host array [layers], as for xmh_clip_blocks_backward.  accumulate != 0:
+ * every gradient is added to what its buffer holds, else overwritten.
+ * Limits as the block stack's: width % 4 == 0, width <= 1024, width / heads == 64, L <= 128, B * L <= 2^21, patch % 4 == 0
+ * (XMH_ENOTSUP beyond); -12 for a short saved buffer or workspace, -22 for null or misfitting arguments.  No host synchronisation,
+ * no allocation, no float atomics: every reduction is summed in one fixed order, two calls on equal inputs agree to the bit. */
+typedef struct xmh_vit_grads {
+    float *proj, *ln_post_w, *ln_post_b, *ln_pre_w, *ln_pre_b, *pos, *cls, *conv1;
+    const xmh_clip_block_grads* blocks;
+} xmh_vit_grads;
+typedef struct xmh_text_grads {
+    float *proj, *ln_final_w, *ln_final_b, *pos, *tok;
+    const xmh_clip_block_grads* blocks;
+} xmh_text_grads;
+size_t xmh_vit_train_saved_bytes(int64_t B, int L, int width, int layers);
+size_t xmh_vit_train_ws_bytes(int64_t B, int L, int width, int conv_k, int out_dim);
+/* image [B, 3, r, r] -> out_cls [B, out_dim] */
+int xmh_vit_train_forward(const xmh_vit_weights* w, const float* image, int64_t B, float* out_cls, void* saved, size_t saved_bytes,
+                          void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* g [B, out_dim] -> the gradients named in grads; image and saved are the forward's */
+int xmh_vit_backward(const xmh_vit_weights* w, const float* image, int64_t B, const void* saved, size_t saved_bytes, const float* g,
+                     const xmh_vit_grads* grads, int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+size_t xmh_text_train_saved_bytes(int64_t B, int L, int width, int layers);
+size_t xmh_text_train_ws_bytes(int64_t B, int L, int width, int out_dim);
+/* ids [B, L] i64 (+ key_padding_mask [B, L] bytes or NULL) -> out_eos [B, out_dim] and eos_index [B] i32 (both required) */
+int xmh_text_train_forward(const xmh_text_weights* w, const int64_t* ids, const uint8_t* key_padding_mask, int64_t B, int L,
+                           float* out_eos, int32_t* eos_index, void* saved, size_t saved_bytes, void* workspace,
+                           size_t workspace_bytes, xmh_stream_t stream);
+/* g [B, out_dim] -> the gradients named in grads; ids, key_padding_mask, eos_index and saved are the forward's */
+int xmh_text_backward(const xmh_text_weights* w, const int64_t* ids, const uint8_t* key_padding_mask, const int32_t* eos_index,
+                      int64_t B, int L, const void* saved, size_t saved_bytes, const float* g, const xmh_text_grads* grads,
+                      int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
 /* One modality of the DCMHT head in eval mode (models/DCMHT/hash/hash.py:15-82): MultiheadAttention over a length-1
  * sequence == out_proj(v_proj(x)) (softmax over one key is 1), BatchNorm1d with running statistics (image) or LayerNorm
  * (text), fc2 + relu, softmax over each (off, on) pair. */
