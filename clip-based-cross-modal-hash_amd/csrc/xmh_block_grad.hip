@@ -167,8 +167,7 @@ int launch_attn_bwd(hipStream_t st, const float* qkv, const float* dO, float* dq
     constexpr int LP = 4 * NJ;
     const size_t lds = ((size_t)2 * LP * kKp + (size_t)2 * kTq * kKp + (size_t)2 * kTq * (LP + 1)) * sizeof(float);
     auto kern = k_attn_bwd<NJ>;
-    if (lds > 64 * 1024)
-        if (const int rl = xmh::raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "xmh_clip_blocks_backward")) return rl;
+    if (lds > 64 * 1024) XMH_TRY(xmh::raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "xmh_clip_blocks_backward"));
     hipLaunchKernelGGL(kern, dim3((unsigned)(B * H)), dim3(kThreads), lds, st, qkv, dO, dqkv, L, H, causal, kpm);
     return XMH_OK;
 }
@@ -189,31 +188,16 @@ size_t work_layout(int64_t M, int D, void* base, Work* w) {
     Work v;
     v.t1 = ar.take<float>((size_t)M * D);
     v.t4 = ar.take<float>((size_t)M * D * 4);
-    v.stats = ar.take<double>((size_t)M * 2);
-    v.lnpart = ar.take<double>((size_t)kLnChunks * 2 * D);
-    size_t most = 0;
-    const int shapes[4][2] = {{D, 4 * D}, {4 * D, D}, {D, D}, {3 * D, D}};
-    for (const auto& s : shapes) {
-        int splits, chunk;
-        tn_split(M, s[0], s[1], &splits, &chunk);
-        if (splits > 1 && (size_t)splits * s[0] * s[1] > most) most = (size_t)splits * s[0] * s[1];
-    }
-    v.part = ar.take<float>(most);
-    v.bpart = ar.take<double>((size_t)kMaxSplits * 4 * D);
+    const TnShape tn[] = {{M, D, 4 * D}, {M, 4 * D, D}, {M, D, D}, {M, 3 * D, D}};
+    take_scratch(ar, M, D, 4 * D, tn, &v);
     if (w) *w = v;
     return ar.used;
 }
 
-bool any_grad(const xmh_clip_block_grads& g) {
-    return g.ln1_w || g.ln1_b || g.qkv_w || g.qkv_b || g.out_w || g.out_b || g.ln2_w || g.ln2_b || g.fc_w || g.fc_b || g.proj_w || g.proj_b;
-}
-
-bool limits_ok(int64_t B, int L, int width) { return B > 0 && L > 0 && width > 0 && width % 4 == 0 && L <= 128 && B * L <= kMaxRows; }
-
 }  // namespace
 
 extern "C" size_t xmh_clip_blocks_backward_ws_bytes(int64_t B, int L, int width) {
-    if (!limits_ok(B, L, width)) return 0;
+    if (!stack_limits_ok(B, L, width)) return 0;
     return work_layout(B * L, width, nullptr, nullptr);
 }
 
@@ -224,34 +208,32 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
     XMH_RANGE("xmh_clip_blocks_backward");
     const char* who = "xmh_clip_blocks_backward";
     if (B == 0 || layers == 0) return XMH_OK;
-    if (B < 0 || L <= 0 || layers < 0 || width <= 0 || heads <= 0 || width % heads) return xmh::fail(-22, "%s: bad arguments", who);
-    if (!blocks || !grads) return xmh::fail(-22, "%s: null blocks / grads", who);
-    if (!dy) return xmh::fail(-22, "%s: null dy", who);
-    if (!saved) return xmh::fail(-22, "%s: null saved buffer", who);
-    if (!workspace) return xmh::fail(-22, "%s: null workspace", who);
+    if (B < 0 || L <= 0 || layers < 0 || width <= 0 || heads <= 0 || width % heads) return xmh::fail(XMH_EINVAL, "%s: bad arguments", who);
+    if (!blocks || !grads) return xmh::fail(XMH_EINVAL, "%s: null blocks / grads", who);
+    if (!dy) return xmh::fail(XMH_EINVAL, "%s: null dy", who);
+    if (!saved) return xmh::fail(XMH_EINVAL, "%s: null saved buffer", who);
+    if (!workspace) return xmh::fail(XMH_EINVAL, "%s: null workspace", who);
     if (width % 4) return xmh::fail(XMH_ENOTSUP, "%s: width %d is not a multiple of 4", who, width);
-    if (width / heads != kDh) return xmh::fail(XMH_ENOTSUP, "%s: head dim %d (only 64, CLIP's width/heads)", who, width / heads);
-    if (L > 128) return xmh::fail(XMH_ENOTSUP, "%s: L=%d > 128", who, L);
-    if (B * L > kMaxRows) return xmh::fail(XMH_ENOTSUP, "%s: %lld x %d tokens (at most 2^21)", who, (long long)B, L);
+    XMH_TRY(check_stack_limits(who, B, L, width, heads));
     const int64_t M = B * L;
     const int D = width;
     const size_t need = xmh::saved_record_bytes(layers, M, D);
-    if (saved_bytes < need) return xmh::fail(-12, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, need);
+    if (saved_bytes < need) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, need);
     Work wk;
     const size_t ws_need = work_layout(M, D, workspace, &wk);
-    if (workspace_bytes < ws_need) return xmh::fail(-12, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws_need);
+    if (workspace_bytes < ws_need) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws_need);
 
     // the walk stops at the lowest layer anything is asked of: below it nothing is read, neither its record nor its weights
     int lowest = 0;
     if (!need_dx) {
-        while (lowest < layers && !any_grad(grads[lowest])) ++lowest;
+        while (lowest < layers && !block_asked(grads[lowest])) ++lowest;
         if (lowest == layers) return XMH_OK;
     }
     for (int i = lowest; i < layers; ++i) {
         const xmh_clip_block& b = blocks[i];
-        if (!xmh::block_fits(b, D)) return xmh::fail(-22, "%s: block %d has layer shapes that do not fit width %d", who, i, D);
+        if (!xmh::block_fits(b, D)) return xmh::fail(XMH_EINVAL, "%s: block %d has layer shapes that do not fit width %d", who, i, D);
         if (!b.qkv.w_f32 || !b.out.w_f32 || !b.fc.w_f32 || !b.proj.w_f32 || !b.ln1_w || !b.ln2_w)
-            return xmh::fail(-22, "%s: block %d lacks fp32 weights", who, i);
+            return xmh::fail(XMH_EINVAL, "%s: block %d lacks fp32 weights", who, i);
     }
     hipStream_t st = xmh::as_stream(stream);
     for (int i = layers - 1; i >= lowest; --i) {
@@ -276,7 +258,7 @@ extern "C" int xmh_clip_blocks_backward(const xmh_clip_block* blocks, int layers
         weight_grads(st, wk, dy, r.attn, M, D, D, g.out_w, g.out_b, accumulate);
         if (!need_dqkv) continue;
         launch_nn(st, dy, b.out.w_f32, M, D, D, wk.t1, nullptr);                               // dattn
-        if (int rc = attn_bwd(st, r.qkv, wk.t1, wk.t4, B, L, heads, causal, key_padding_mask)) return rc;      // dqkv [M, 3D]
+        XMH_TRY(attn_bwd(st, r.qkv, wk.t1, wk.t4, B, L, heads, causal, key_padding_mask));                     // dqkv [M, 3D]
         weight_grads(st, wk, wk.t4, r.ln1, M, 3 * D, D, g.qkv_w, g.qkv_b, accumulate);
         if (!need_dln1) continue;
         launch_nn(st, wk.t4, b.qkv.w_f32, M, 3 * D, D, wk.t1, nullptr);                        // dln1

@@ -248,6 +248,45 @@ struct GradScratch {
     double* bpart;    // [kMaxSplits][N] bias partials
 };
 
+// a product dW [N, K] = dY^T X over M rows that weight_grads will be asked for
+struct TnShape {
+    int64_t M;
+    int N, K;
+};
+
+// GradScratch's four buffers from a workspace: `rows` LayerNorm rows of width D, bias gradients up to `bias_width` wide, and the
+// partials of the largest split product among `tn` (one with no rows or no columns is never launched)
+template <size_t n>
+void take_scratch(xmh::Arena& ar, int64_t rows, int D, int bias_width, const TnShape (&tn)[n], GradScratch* gs) {
+    gs->stats = ar.take<double>((size_t)rows * 2);
+    gs->lnpart = ar.take<double>((size_t)kLnChunks * 2 * D);
+    size_t most = 0;
+    for (const TnShape& s : tn) {
+        if (s.M <= 0 || s.K <= 0) continue;
+        int splits, chunk;
+        tn_split(s.M, s.N, s.K, &splits, &chunk);
+        if (splits > 1 && (size_t)splits * s.N * s.K > most) most = (size_t)splits * s.N * s.K;
+    }
+    gs->part = ar.take<float>(most);
+    gs->bpart = ar.take<double>((size_t)kMaxSplits * bias_width);
+}
+
+// is any gradient of this block asked for
+bool block_asked(const xmh_clip_block_grads& g) {
+    return g.ln1_w || g.ln1_b || g.qkv_w || g.qkv_b || g.out_w || g.out_b || g.ln2_w || g.ln2_b || g.fc_w || g.fc_b || g.proj_w || g.proj_b;
+}
+
+// the shapes the size functions of both files answer for (the towers add their own bound on the width) ...
+bool stack_limits_ok(int64_t B, int L, int width) { return B > 0 && L > 0 && width > 0 && width % 4 == 0 && L <= 128 && B * L <= kMaxRows; }
+
+// ... and what the entry points say beyond them, after their own check of the width
+int check_stack_limits(const char* who, int64_t B, int L, int width, int heads) {
+    if (width / heads != 64) return xmh::fail(XMH_ENOTSUP, "%s: head dim %d (only 64, CLIP's width/heads)", who, width / heads);
+    if (L > 128) return xmh::fail(XMH_ENOTSUP, "%s: L=%d > 128", who, L);
+    if (B * L > kMaxRows) return xmh::fail(XMH_ENOTSUP, "%s: %lld x %d tokens (at most 2^21)", who, (long long)B, L);
+    return XMH_OK;
+}
+
 // dx [M, K] = dy [M, N] w [N, K] (. QuickGELU'(gelu_pre))
 void launch_nn(hipStream_t st, const float* dy, const float* w, int64_t M, int N, int K, float* dx, const float* gelu_pre) {
     MmArgs g = {};

@@ -158,18 +158,8 @@ size_t work_layout(int64_t B, int L, int D, int conv_k, int out_dim, void* base,
     v.dln = ar.take<float>((size_t)B * D);
     v.drow = ar.take<float>((size_t)B * D);
     v.bsum = ar.take<double>((size_t)xmh::ceil_div(B, kBatchChunk) * L * D);
-    v.gs.stats = ar.take<double>((size_t)M * 2);
-    v.gs.lnpart = ar.take<double>((size_t)kLnChunks * 2 * D);
-    size_t most = 0;
-    const int64_t shapes[2][3] = {{B, D, out_dim}, {BP, D, conv_k}};
-    for (const auto& s : shapes) {
-        if (s[0] <= 0 || s[2] <= 0) continue;
-        int splits, chunk;
-        tn_split(s[0], (int)s[1], (int)s[2], &splits, &chunk);
-        if (splits > 1 && (size_t)splits * s[1] * s[2] > most) most = (size_t)splits * s[1] * s[2];
-    }
-    v.gs.part = ar.take<float>(most);
-    v.gs.bpart = ar.take<double>((size_t)kMaxSplits * D);
+    const TnShape tn[] = {{B, D, out_dim}, {BP, D, conv_k}};
+    take_scratch(ar, M, D, D, tn, &v.gs);
     const size_t fwd = xmh_clip_workspace_bytes(B, L, D, 0, 0, 2), bwd = xmh_clip_blocks_backward_ws_bytes(B, L, D);
     v.blocks_bytes = fwd > bwd ? fwd : bwd;
     v.blocks = ar.take<char>(v.blocks_bytes);
@@ -177,18 +167,21 @@ size_t work_layout(int64_t B, int L, int D, int conv_k, int out_dim, void* base,
     return ar.used;
 }
 
-bool limits_ok(int64_t B, int L, int D) { return B > 0 && L > 0 && L <= 128 && D > 0 && D % 4 == 0 && D <= kMaxWidth && B * L <= kMaxRows; }
-
-int check_limits(const char* who, int64_t B, int L, int D, int heads) {
-    if (D % 4 || D > kMaxWidth) return xmh::fail(XMH_ENOTSUP, "%s: width %d (a multiple of 4, at most %d)", who, D, kMaxWidth);
-    if (D / heads != 64) return xmh::fail(XMH_ENOTSUP, "%s: head dim %d (only 64, CLIP's width/heads)", who, D / heads);
-    if (L > 128) return xmh::fail(XMH_ENOTSUP, "%s: L=%d > 128", who, L);
-    if (B * L > kMaxRows) return xmh::fail(XMH_ENOTSUP, "%s: %lld x %d tokens (at most 2^21)", who, (long long)B, L);
+// the two buffers of a call, laid out and measured against what the caller handed in
+int lay_out(const char* who, int64_t B, int L, int D, int layers, int conv_k, int out_dim, const void* saved, size_t saved_bytes, void* workspace,
+            size_t workspace_bytes, Kept* kp, TowerWork* wk) {
+    const size_t kneed = kept_layout(B, L, D, layers, conv_k > 0, const_cast<void*>(saved), kp);
+    if (saved_bytes < kneed) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, kneed);
+    const size_t wneed = work_layout(B, L, D, conv_k, out_dim, workspace, wk);
+    if (workspace_bytes < wneed) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, wneed);
     return XMH_OK;
 }
 
-bool block_asked(const xmh_clip_block_grads& g) {
-    return g.ln1_w || g.ln1_b || g.qkv_w || g.qkv_b || g.out_w || g.out_b || g.ln2_w || g.ln2_b || g.fc_w || g.fc_b || g.proj_w || g.proj_b;
+bool limits_ok(int64_t B, int L, int D) { return stack_limits_ok(B, L, D) && D <= kMaxWidth; }
+
+int check_limits(const char* who, int64_t B, int L, int D, int heads) {
+    if (D % 4 || D > kMaxWidth) return xmh::fail(XMH_ENOTSUP, "%s: width %d (a multiple of 4, at most %d)", who, D, kMaxWidth);
+    return check_stack_limits(who, B, L, D, heads);
 }
 
 bool any_block_asked(const xmh_clip_block_grads* g, int layers) {
@@ -289,11 +282,8 @@ extern "C" int xmh_vit_train_forward(const xmh_vit_weights* w, const float* imag
     VitShape s;
     XMH_TRY(vit_shape(who, w, B, &s));
     Kept kp;
-    const size_t kneed = kept_layout(B, s.L, s.D, w->layers, true, saved, &kp);
-    if (saved_bytes < kneed) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, kneed);
     TowerWork wk;
-    const size_t wneed = work_layout(B, s.L, s.D, s.conv_k, w->out_dim, workspace, &wk);
-    if (workspace_bytes < wneed) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, wneed);
+    XMH_TRY(lay_out(who, B, s.L, s.D, w->layers, s.conv_k, w->out_dim, saved, saved_bytes, workspace, workspace_bytes, &kp, &wk));
     XMH_TRY(xmh_im2col_patch(image, B, 3, w->resolution, w->patch, wk.cols, stream));
     XMH_TRY(xmh_gemm_nt_f32(wk.cols, s.conv_k, w->conv1.w_f32, s.conv_k, w->conv1.bias, nullptr, 0, wk.patches, s.D, B * s.P, s.D, s.conv_k, 0, 0, stream));
     XMH_TRY(xmh::vit_assemble_keep(wk.patches, w->cls, w->pos, w->ln_pre_w, w->ln_pre_b, kLnEps, wk.x, kp.pre, B, s.P, s.D, xmh::as_stream(stream)));
@@ -314,11 +304,8 @@ extern "C" int xmh_vit_backward(const xmh_vit_weights* w, const float* image, in
     XMH_TRY(vit_shape(who, w, B, &s));
     if (w->layers > 0 && !grads->blocks) return xmh::fail(XMH_EINVAL, "%s: null block gradients", who);
     Kept kp;
-    const size_t kneed = kept_layout(B, s.L, s.D, w->layers, true, const_cast<void*>(saved), &kp);
-    if (saved_bytes < kneed) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, kneed);
     TowerWork wk;
-    const size_t wneed = work_layout(B, s.L, s.D, s.conv_k, w->out_dim, workspace, &wk);
-    if (workspace_bytes < wneed) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, wneed);
+    XMH_TRY(lay_out(who, B, s.L, s.D, w->layers, s.conv_k, w->out_dim, saved, saved_bytes, workspace, workspace_bytes, &kp, &wk));
     const xmh_vit_grads& gr = *grads;
     const int64_t M = B * s.L;
     const int D = s.D;
@@ -360,11 +347,8 @@ extern "C" int xmh_text_train_forward(const xmh_text_weights* w, const int64_t* 
     XMH_TRY(text_shape(who, w, B, L));
     const int D = w->width;
     Kept kp;
-    const size_t kneed = kept_layout(B, L, D, w->layers, false, saved, &kp);
-    if (saved_bytes < kneed) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, kneed);
     TowerWork wk;
-    const size_t wneed = work_layout(B, L, D, 0, w->out_dim, workspace, &wk);
-    if (workspace_bytes < wneed) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, wneed);
+    XMH_TRY(lay_out(who, B, L, D, w->layers, 0, w->out_dim, saved, saved_bytes, workspace, workspace_bytes, &kp, &wk));
     XMH_TRY(xmh_text_embed(ids, w->tok_emb, w->pos, wk.x, eos_index, B, L, D, w->vocab, stream));
     if (w->layers > 0)
         XMH_TRY(xmh_clip_blocks_forward_saved(w->blocks, w->layers, D, w->heads, wk.x, B, L, 1, key_padding_mask, 2, wk.blocks, wk.blocks_bytes,
@@ -384,11 +368,8 @@ extern "C" int xmh_text_backward(const xmh_text_weights* w, const int64_t* ids, 
     if (w->layers > 0 && !grads->blocks) return xmh::fail(XMH_EINVAL, "%s: null block gradients", who);
     const int D = w->width;
     Kept kp;
-    const size_t kneed = kept_layout(B, L, D, w->layers, false, const_cast<void*>(saved), &kp);
-    if (saved_bytes < kneed) return xmh::fail(XMH_ENOMEM, "%s: saved buffer of %zu bytes, %zu needed", who, saved_bytes, kneed);
     TowerWork wk;
-    const size_t wneed = work_layout(B, L, D, 0, w->out_dim, workspace, &wk);
-    if (workspace_bytes < wneed) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, wneed);
+    XMH_TRY(lay_out(who, B, L, D, w->layers, 0, w->out_dim, saved, saved_bytes, workspace, workspace_bytes, &kp, &wk));
     const xmh_text_grads& gr = *grads;
     hipStream_t st = xmh::as_stream(stream);
     const bool front = gr.pos || gr.tok;

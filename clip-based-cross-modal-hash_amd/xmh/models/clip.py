@@ -52,6 +52,11 @@ def _addr(t):
     return None if t is None else t.data_ptr()
 
 
+def _kpm_u8(mask, device):
+    """key padding mask as the kernels read it: contiguous uint8 on `device`, or None"""
+    return None if mask is None else mask.to(device=device, dtype=torch.uint8).contiguous()
+
+
 def _linear_desc(W: torch.Tensor, bias, precision: int, keep: list) -> "_lib.Linear":
     """xmh_linear of a [N, K] weight; `keep` collects every tensor whose address goes into the descriptor."""
     W2 = ops._f32c(W.detach())
@@ -120,7 +125,7 @@ class _Block(nn.Module):
 class Transformer(nn.Module):
     def __init__(self, width: int, layers: int, heads: int):
         super().__init__()
-        self.width, self.layers = width, layers
+        self.width, self.layers, self.heads = width, layers, heads
         self.resblocks = nn.Sequential(*[_Block(width, heads) for _ in range(layers)])
 
     def run(self, x: torch.Tensor, causal: bool = False, key_padding_mask=None) -> torch.Tensor:
@@ -131,14 +136,12 @@ class Transformer(nn.Module):
             return x
         B, L, D = x.shape
         blocks, precision = _cached_desc(self, lambda prec, keep: _blocks_desc(list(self.resblocks), prec, keep))
-        kpm = None if key_padding_mask is None else key_padding_mask.to(device=x.device, dtype=torch.uint8).contiguous()
+        kpm = _kpm_u8(key_padding_mask, x.device)
         nbytes = lib.xmh_clip_workspace_bytes(B, L, D, 0, 0, precision)
         ws = _workspace(nbytes, x.device)
-        check(lib.xmh_clip_blocks_forward(blocks, len(self.resblocks), D, self.resblocks[0].heads if len(self.resblocks) else 1,
-                                          ptr(x), B, L, int(causal), ptr(kpm), precision, ptr(ws), nbytes, current_stream()),
-              "xmh_clip_blocks_forward")
+        check(lib.xmh_clip_blocks_forward(blocks, len(self.resblocks), D, self.heads, ptr(x), B, L, int(causal), ptr(kpm), precision, ptr(ws), nbytes,
+                                          current_stream()), "xmh_clip_blocks_forward")
         return x
-
 
     # per-layer record of xmh_clip_blocks_forward_saved (include/xmh.h): field -> width in units of D
     # (the C side states the same layout once, in csrc/xmh_clip_record.h: saved_record)
@@ -153,15 +156,15 @@ class Transformer(nn.Module):
         B, L, D = x.shape
         layers = len(self.resblocks)
         blocks, precision = _cached_desc(self, lambda prec, keep: _blocks_desc(list(self.resblocks), prec, keep))
-        kpm = None if key_padding_mask is None else key_padding_mask.to(device=x.device, dtype=torch.uint8).contiguous()
+        kpm = _kpm_u8(key_padding_mask, x.device)
         nbytes = lib.xmh_clip_workspace_bytes(B, L, D, 0, 0, precision)
         ws = _workspace(nbytes, x.device)
         sbytes = lib.xmh_clip_saved_bytes(B, L, D, layers)
         buf = torch.empty(sbytes // 4, dtype=torch.float32, device=x.device)
-        check(lib.xmh_clip_blocks_forward_saved(blocks, layers, D, self.resblocks[0].heads if layers else 1, ptr(x), B, L, int(causal),
-                                                ptr(kpm), precision, ptr(ws), nbytes, ptr(buf), sbytes, current_stream()),
-              "xmh_clip_blocks_forward_saved")
-        saved, per_layer, md = [], 16 * B * L * D, B * L * D
+        check(lib.xmh_clip_blocks_forward_saved(blocks, layers, D, self.heads, ptr(x), B, L, int(causal), ptr(kpm), precision, ptr(ws), nbytes,
+                                                ptr(buf), sbytes, current_stream()), "xmh_clip_blocks_forward_saved")
+        md = B * L * D
+        saved, per_layer = [], sum(n for _, n in self.SAVED_FIELDS) * md
         for i in range(layers):
             rec, off = {}, i * per_layer
             for name, n in self.SAVED_FIELDS:
@@ -170,12 +173,11 @@ class Transformer(nn.Module):
             saved.append(rec)
         return x, saved
 
-    # the twelve parameters of a block in the member order of xmh_clip_block_grads (include/xmh.h)
     @staticmethod
     def _train_params(blk):
-        return (blk.ln_1.weight, blk.ln_1.bias, blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj.weight,
-                blk.attn.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, blk.mlp.c_proj.weight,
-                blk.mlp.c_proj.bias)
+        """the twelve parameters of a block in the field order of xmh_clip_block_grads: a view of clip_train.BLOCK"""
+        from .clip_train import BLOCK, _get
+        return tuple(_get[path](blk) for _, path in BLOCK)
 
     def run_train(self, x: torch.Tensor, causal: bool = False, key_padding_mask=None) -> torch.Tensor:
         """The block stack in exact fp32 behind torch.autograd: x [B, L, D] is copied, never written; the result carries
@@ -184,241 +186,30 @@ class Transformer(nn.Module):
         no_grad, or nothing requires grad -- this is `run` in exact mode on a copy, and no record is kept."""
         if not x.is_cuda or x.dim() != 3:
             raise ValueError("run_train takes a [B, L, D] tensor on the GPU; there is no CPU fallback")
-        params = [p for blk in self.resblocks for p in self._train_params(blk)]
-        kpm = None if key_padding_mask is None else key_padding_mask.to(device=x.device, dtype=torch.uint8).contiguous()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            return _BlocksTrain.apply(self, bool(causal), kpm, x, *params)
-        return _train_forward(self, x, bool(causal), kpm, params, keep_record=False)[0]
+        from . import clip_train
+        return clip_train.run_blocks(self, x, bool(causal), _kpm_u8(key_padding_mask, x.device))
 
 
-def _exact_desc(tr, params, keep: list):
-    """xmh_clip_block array over the parameters IN PLACE (fp32 weights only: no operand planes, nothing cached across steps)"""
-    for p in params:
-        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError("run_train needs contiguous fp32 CUDA/HIP parameters (got %s %s); there is no CPU fallback" % (p.dtype, p.device))
-    arr = (_lib.ClipBlock * len(tr.resblocks))()
-    for i in range(len(tr.resblocks)):
-        l1w, l1b, qw, qb, ow, ob, l2w, l2b, fw, fb, pw, pb = (p.detach() for p in params[12 * i:12 * i + 12])
-        lin = lambda w, b: _lib.Linear(w.data_ptr(), None, None, b.data_ptr(), w.shape[0], w.shape[1])      # noqa: E731
-        arr[i] = _lib.ClipBlock(l1w.data_ptr(), l1b.data_ptr(), l2w.data_ptr(), l2b.data_ptr(), lin(qw, qb), lin(ow, ob), lin(fw, fb), lin(pw, pb))
-    keep.extend(params)
-    return arr
+def _vit_forward_cls(desc, precision: int, image: torch.Tensor) -> torch.Tensor:
+    """xmh_vit_b32_forward of a checked [B, 3, R, R] batch, the cls feature only"""
+    B, L = image.shape[0], (desc.resolution // desc.patch) ** 2 + 1
+    nbytes = lib.xmh_clip_workspace_bytes(B, L, desc.width, desc.conv1.k, 0, precision)
+    ws = _workspace(nbytes, image.device)
+    out = torch.empty(B, desc.out_dim, dtype=torch.float32, device=image.device)
+    check(lib.xmh_vit_b32_forward(ctypes.byref(desc), ptr(image), B, precision, ptr(out), None, ptr(ws), nbytes, current_stream()),
+          "xmh_vit_b32_forward")
+    return out
 
 
-def _train_forward(tr, x, causal, kpm, params, keep_record=True):
-    """-> (y, record buffer or None): exact-mode forward on a copy of x"""
-    y = x.detach().to(torch.float32).contiguous()
-    y = y.clone() if y.data_ptr() == x.data_ptr() else y
-    B, L, D = y.shape
-    layers = len(tr.resblocks)
-    heads = tr.resblocks[0].heads if layers else 1
-    keep = []
-    blocks = _exact_desc(tr, params, keep)
-    nbytes = lib.xmh_clip_workspace_bytes(B, L, D, 0, 0, ops.PREC_F32X)
-    ws = _workspace(nbytes, y.device)
-    if not keep_record:
-        check(lib.xmh_clip_blocks_forward(blocks, layers, D, heads, ptr(y), B, L, int(causal), ptr(kpm), ops.PREC_F32X, ptr(ws), nbytes,
-                                          current_stream()), "xmh_clip_blocks_forward")
-        return y, None
-    sbytes = lib.xmh_clip_saved_bytes(B, L, D, layers)
-    buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=y.device)
-    check(lib.xmh_clip_blocks_forward_saved(blocks, layers, D, heads, ptr(y), B, L, int(causal), ptr(kpm), ops.PREC_F32X, ptr(ws), nbytes,
-                                            ptr(buf), sbytes, current_stream()), "xmh_clip_blocks_forward_saved")
-    return y, buf
-
-
-class _BlocksTrain(torch.autograd.Function):
-    """forward = xmh_clip_blocks_forward_saved (exact mode), backward = xmh_clip_blocks_backward"""
-
-    @staticmethod
-    def forward(ctx, tr, causal, kpm, x, *params):
-        y, buf = _train_forward(tr, x, causal, kpm, params)
-        ctx.tr, ctx.causal, ctx.kpm, ctx.meta = tr, causal, kpm, (x.shape, x.dtype)
-        ctx.save_for_backward(buf, *params)             # saved parameters: autograd notices an in-place change before backward
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable      # the gradient kernels are not themselves differentiable
-    def backward(ctx, g):
-        buf, *params = ctx.saved_tensors
-        tr = ctx.tr
-        B, L, D = ctx.meta[0]
-        layers = len(tr.resblocks)
-        need = ctx.needs_input_grad
-        gp = [torch.empty_like(p) if need[4 + i] else None for i, p in enumerate(params)]
-        grads = (_lib.ClipBlockGrads * max(layers, 1))()
-        for i in range(layers):
-            grads[i] = _lib.ClipBlockGrads(*[_addr(t) for t in gp[12 * i:12 * i + 12]])
-        dy = g.detach().to(torch.float32).contiguous()
-        dy = dy.clone() if dy.data_ptr() == g.data_ptr() else dy      # updated in place: never the caller's tensor
-        keep = []
-        blocks = _exact_desc(tr, params, keep)
-        nbytes = lib.xmh_clip_blocks_backward_ws_bytes(B, L, D)
-        ws = _workspace(nbytes, dy.device)
-        check(lib.xmh_clip_blocks_backward(blocks, layers, D, tr.resblocks[0].heads if layers else 1, B, L, int(ctx.causal), ptr(ctx.kpm),
-                                           ptr(buf), buf.numel() * 4 if layers else 0, ptr(dy), int(need[3]), grads, 0, ptr(ws), nbytes,
-                                           current_stream()), "xmh_clip_blocks_backward")
-        gx = dy.reshape(ctx.meta[0]).to(ctx.meta[1]) if need[3] else None
-        return (None, None, None, gx, *gp)
-
-
-# ---- the two towers behind torch.autograd (DESIGN 3.13) --------------------------------------------------------------------------
-def _tower_params_ok(params, who):
-    for p in params:
-        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError("%s needs contiguous fp32 CUDA/HIP parameters (got %s %s); there is no CPU fallback" % (who, p.dtype, p.device))
-
-
-def _block_params(tr):
-    return [p for blk in tr.resblocks for p in Transformer._train_params(blk)]
-
-
-def _grad_structs(layers, gp_blocks):
-    grads = (_lib.ClipBlockGrads * max(layers, 1))()
-    for i in range(layers):
-        grads[i] = _lib.ClipBlockGrads(*[_addr(t) for t in gp_blocks[12 * i:12 * i + 12]])
-    return grads
-
-
-def _upstream(g):
-    g = g.detach().to(torch.float32)
-    return g if g.is_contiguous() else g.contiguous()
-
-
-_VIT_OWN = 8       # conv1, class_embedding, positional_embedding, ln_pre w/b, ln_post w/b, proj; the blocks' parameters follow
-
-
-def _vit_params(vis):
-    return [vis.conv1.weight, vis.class_embedding, vis.positional_embedding, vis.ln_pre.weight, vis.ln_pre.bias, vis.ln_post.weight,
-            vis.ln_post.bias, vis.proj] + _block_params(vis.transformer)
-
-
-def _vit_exact_desc(vis, params, keep):
-    """xmh_vit_weights over the parameters IN PLACE; only `x @ proj` needs a copy (the descriptor holds proj transposed)"""
-    _tower_params_ok(params, "encode_image_train")
-    conv, cls, pos, lpw, lpb, low, lob, proj = (p.detach() for p in params[:_VIT_OWN])
-    tr = vis.transformer
-    blocks = _exact_desc(tr, params[_VIT_OWN:], keep)
-    proj_t = proj.t().contiguous()
-    keep.extend((proj_t, blocks))
-    keep.extend(params[:_VIT_OWN])
-    width = conv.shape[0]
-    heads = tr.resblocks[0].heads if len(tr.resblocks) else max(width // 64, 1)
-    return _lib.VitWeights(vis.input_resolution, vis.patch_size, width, heads, len(tr.resblocks), proj.shape[1],
-                           _lib.Linear(conv.data_ptr(), None, None, None, width, conv[0].numel()), cls.data_ptr(), pos.data_ptr(), lpw.data_ptr(),
-                           lpb.data_ptr(), low.data_ptr(), lob.data_ptr(), _lib.Linear(proj_t.data_ptr(), None, None, None, proj.shape[1], width), blocks)
-
-
-def _vit_sizes(vis, B):
-    L, width = vis.positional_embedding.shape
-    return L, width, 3 * vis.patch_size ** 2, vis.proj.shape[1], len(vis.transformer.resblocks)
-
-
-class _VitTrain(torch.autograd.Function):
-    """forward = xmh_vit_train_forward, backward = xmh_vit_backward"""
-
-    @staticmethod
-    def forward(ctx, vis, image, *params):
-        B = image.shape[0]
-        L, width, conv_k, out_dim, layers = _vit_sizes(vis, B)
-        keep = []
-        desc = _vit_exact_desc(vis, params, keep)
-        sbytes = lib.xmh_vit_train_saved_bytes(B, L, width, layers)
-        nbytes = lib.xmh_vit_train_ws_bytes(B, L, width, conv_k, out_dim)
-        buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=image.device)
-        ws = _workspace(nbytes, image.device)
-        out = torch.empty(B, out_dim, dtype=torch.float32, device=image.device)
-        check(lib.xmh_vit_train_forward(ctypes.byref(desc), ptr(image), B, ptr(out), ptr(buf), sbytes, ptr(ws), nbytes, current_stream()),
-              "xmh_vit_train_forward")
-        ctx.vis = vis
-        ctx.save_for_backward(image, buf, *params)      # saved parameters: autograd notices an in-place change before backward
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        image, buf, *params = ctx.saved_tensors
-        vis = ctx.vis
-        B = image.shape[0]
-        L, width, conv_k, out_dim, layers = _vit_sizes(vis, B)
-        need = ctx.needs_input_grad[2:]
-        gp = [torch.empty_like(p) if need[i] else None for i, p in enumerate(params)]
-        blocks = _grad_structs(layers, gp[_VIT_OWN:])
-        conv, cls, pos, lpw, lpb, low, lob, proj = gp[:_VIT_OWN]
-        grads = _lib.VitGrads(_addr(proj), _addr(low), _addr(lob), _addr(lpw), _addr(lpb), _addr(pos), _addr(cls), _addr(conv), blocks)
-        keep = []
-        desc = _vit_exact_desc(vis, params, keep)
-        gg = _upstream(g)
-        nbytes = lib.xmh_vit_train_ws_bytes(B, L, width, conv_k, out_dim)
-        ws = _workspace(nbytes, gg.device)
-        check(lib.xmh_vit_backward(ctypes.byref(desc), ptr(image), B, ptr(buf), buf.numel() * 4, ptr(gg), ctypes.byref(grads), 0, ptr(ws), nbytes,
-                                   current_stream()), "xmh_vit_backward")
-        return (None, None, *gp)
-
-
-_TEXT_OWN = 5      # token_embedding.weight, positional_embedding, ln_final w/b, text_projection; the blocks' parameters follow
-
-
-def _text_train_params(clip):
-    return [clip.token_embedding.weight, clip.positional_embedding, clip.ln_final.weight, clip.ln_final.bias, clip.text_projection] + \
-        _block_params(clip.transformer)
-
-
-def _text_exact_desc(clip, params, keep):
-    _tower_params_ok(params, "encode_text_train")
-    tok, pos, lfw, lfb, proj = (p.detach() for p in params[:_TEXT_OWN])
-    tr = clip.transformer
-    blocks = _exact_desc(tr, params[_TEXT_OWN:], keep)
-    proj_t = proj.t().contiguous()
-    keep.extend((proj_t, blocks))
-    keep.extend(params[:_TEXT_OWN])
-    width = tok.shape[1]
-    heads = tr.resblocks[0].heads if len(tr.resblocks) else max(width // 64, 1)
-    return _lib.TextWeights(tok.shape[0], pos.shape[0], width, heads, len(tr.resblocks), proj.shape[1], tok.data_ptr(), pos.data_ptr(),
-                            lfw.data_ptr(), lfb.data_ptr(), _lib.Linear(proj_t.data_ptr(), None, None, None, proj.shape[1], width), blocks)
-
-
-class _TextTrain(torch.autograd.Function):
-    """forward = xmh_text_train_forward, backward = xmh_text_backward"""
-
-    @staticmethod
-    def forward(ctx, clip, ids, kpm, *params):
-        B, L = ids.shape
-        width, out_dim, layers = params[0].shape[1], params[4].shape[1], len(clip.transformer.resblocks)
-        keep = []
-        desc = _text_exact_desc(clip, params, keep)
-        sbytes = lib.xmh_text_train_saved_bytes(B, L, width, layers)
-        nbytes = lib.xmh_text_train_ws_bytes(B, L, width, out_dim)
-        buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=ids.device)
-        ws = _workspace(nbytes, ids.device)
-        out = torch.empty(B, out_dim, dtype=torch.float32, device=ids.device)
-        eos = torch.empty(B, dtype=torch.int32, device=ids.device)
-        check(lib.xmh_text_train_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, ptr(out), ptr(eos), ptr(buf), sbytes, ptr(ws), nbytes,
-                                         current_stream()), "xmh_text_train_forward")
-        ctx.clip, ctx.kpm = clip, kpm
-        ctx.save_for_backward(ids, eos, buf, *params)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        ids, eos, buf, *params = ctx.saved_tensors
-        clip = ctx.clip
-        B, L = ids.shape
-        width, out_dim, layers = params[0].shape[1], params[4].shape[1], len(clip.transformer.resblocks)
-        need = ctx.needs_input_grad[3:]
-        gp = [torch.empty_like(p) if need[i] else None for i, p in enumerate(params)]
-        blocks = _grad_structs(layers, gp[_TEXT_OWN:])
-        tok, pos, lfw, lfb, proj = gp[:_TEXT_OWN]
-        grads = _lib.TextGrads(_addr(proj), _addr(lfw), _addr(lfb), _addr(pos), _addr(tok), blocks)
-        keep = []
-        desc = _text_exact_desc(clip, params, keep)
-        gg = _upstream(g)
-        nbytes = lib.xmh_text_train_ws_bytes(B, L, width, out_dim)
-        ws = _workspace(nbytes, gg.device)
-        check(lib.xmh_text_backward(ctypes.byref(desc), ptr(ids), ptr(ctx.kpm), ptr(eos), B, L, ptr(buf), buf.numel() * 4, ptr(gg),
-                                    ctypes.byref(grads), 0, ptr(ws), nbytes, current_stream()), "xmh_text_backward")
-        return (None, None, None, *gp)
+def _text_forward_eos(desc, precision: int, ids: torch.Tensor, kpm) -> torch.Tensor:
+    """xmh_text_forward on the padded rows of [B, L] int64 ids, the EOS feature only"""
+    B, L = ids.shape
+    nbytes = lib.xmh_clip_workspace_bytes(B, L, desc.width, 0, 0, precision)
+    ws = _workspace(nbytes, ids.device)
+    out = torch.empty(B, desc.out_dim, dtype=torch.float32, device=ids.device)
+    check(lib.xmh_text_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, precision, ptr(out), None, None, ptr(ws), nbytes, current_stream()),
+          "xmh_text_forward")
+    return out
 
 
 class VisionTransformer(nn.Module):
@@ -441,8 +232,7 @@ class VisionTransformer(nn.Module):
                                                               self.ln_pre.bias, self.ln_post.weight, self.ln_post.bias)]
         keep.extend(small)
         keep.append(blocks)
-        heads = self.transformer.resblocks[0].heads if len(self.transformer.resblocks) else 1
-        return _lib.VitWeights(self.input_resolution, self.patch_size, width, heads, len(self.transformer.resblocks), self.proj.shape[1],
+        return _lib.VitWeights(self.input_resolution, self.patch_size, width, self.transformer.heads, len(self.transformer.resblocks), self.proj.shape[1],
                                _linear_desc(self.conv1.weight.reshape(width, -1), None, precision, keep),
                                *[_addr(t) for t in small],
                                _linear_desc(_transposed(self, "proj"), None, precision, keep), blocks)
@@ -455,13 +245,10 @@ class VisionTransformer(nn.Module):
                 raise ValueError("image batch is %s, the tower takes [B, 3, %d, %d]" % (tuple(image.shape), self.input_resolution, self.input_resolution))
             L = self.positional_embedding.shape[0]
             desc, precision = _cached_desc(self, self._desc)
-            nbytes = lib.xmh_clip_workspace_bytes(B, L, desc.width, 3 * self.patch_size ** 2, out_dim if self.return_patches else 0, precision)
-            ws = _workspace(nbytes, image.device)
             if not self.return_patches:
-                out = torch.empty(B, out_dim, dtype=torch.float32, device=image.device)
-                check(lib.xmh_vit_b32_forward(ctypes.byref(desc), ptr(image), B, precision, ptr(out), None, ptr(ws), nbytes, current_stream()),
-                      "xmh_vit_b32_forward")
-                return out
+                return _vit_forward_cls(desc, precision, image)
+            nbytes = lib.xmh_clip_workspace_bytes(B, L, desc.width, 3 * self.patch_size ** 2, out_dim, precision)
+            ws = _workspace(nbytes, image.device)
             y = torch.empty(B, L, out_dim, dtype=torch.float32, device=image.device)
             check(lib.xmh_vit_b32_forward(ctypes.byref(desc), ptr(image), B, precision, None, ptr(y), ptr(ws), nbytes, current_stream()),
                   "xmh_vit_b32_forward")
@@ -516,18 +303,8 @@ class CLIP(nn.Module):
         image = ops._f32c(image).contiguous()
         if image.dim() != 4 or image.shape[1:] != (3, vis.input_resolution, vis.input_resolution):
             raise ValueError("image batch is %s, the tower takes [B, 3, %d, %d]" % (tuple(image.shape), vis.input_resolution, vis.input_resolution))
-        params = _vit_params(vis)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _VitTrain.apply(vis, image, *params)
-        B, (L, width), out_dim = image.shape[0], vis.positional_embedding.shape, vis.proj.shape[1]
-        keep = []
-        desc = _vit_exact_desc(vis, params, keep)
-        nbytes = lib.xmh_clip_workspace_bytes(B, L, width, 3 * vis.patch_size ** 2, 0, ops.PREC_F32X)
-        ws = _workspace(nbytes, image.device)
-        out = torch.empty(B, out_dim, dtype=torch.float32, device=image.device)
-        check(lib.xmh_vit_b32_forward(ctypes.byref(desc), ptr(image), B, ops.PREC_F32X, ptr(out), None, ptr(ws), nbytes, current_stream()),
-              "xmh_vit_b32_forward")
-        return out
+        from . import clip_train
+        return clip_train.encode_image(vis, image)
 
     def encode_text_train(self, text, key_padding_mask=None):
         """encode_text in exact fp32 behind torch.autograd, on the padded rows: gradients go to exactly the parameters of the text
@@ -541,20 +318,8 @@ class CLIP(nn.Module):
         ids = text.to(torch.int64).contiguous()
         if ids.dim() != 2 or ids.shape[1] > self.context_length:
             raise ValueError("token batch is %s, the tower takes [B, L] with L <= %d" % (tuple(ids.shape), self.context_length))
-        kpm = None if key_padding_mask is None else key_padding_mask.to(device=ids.device, dtype=torch.uint8).contiguous()
-        params = _text_train_params(self)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _TextTrain.apply(self, ids, kpm, *params)
-        B, L = ids.shape
-        width, out_dim = params[0].shape[1], params[4].shape[1]
-        keep = []
-        desc = _text_exact_desc(self, params, keep)
-        nbytes = lib.xmh_clip_workspace_bytes(B, L, width, 0, 0, ops.PREC_F32X)
-        ws = _workspace(nbytes, ids.device)
-        out = torch.empty(B, out_dim, dtype=torch.float32, device=ids.device)
-        check(lib.xmh_text_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, ops.PREC_F32X, ptr(out), None, None, ptr(ws), nbytes,
-                                   current_stream()), "xmh_text_forward")
-        return out
+        from . import clip_train
+        return clip_train.encode_text(self, ids, _kpm_u8(key_padding_mask, ids.device))
 
     def _text_desc(self, precision: int, keep: list):
         blocks = _blocks_desc(list(self.transformer.resblocks), precision, keep)
@@ -563,8 +328,7 @@ class CLIP(nn.Module):
         keep.extend(small)
         keep.append(blocks)
         width = self.token_embedding.weight.shape[1]
-        heads = self.transformer.resblocks[0].heads if len(self.transformer.resblocks) else 1
-        return _lib.TextWeights(self.token_embedding.weight.shape[0], self.positional_embedding.shape[0], width, heads,
+        return _lib.TextWeights(self.token_embedding.weight.shape[0], self.positional_embedding.shape[0], width, self.transformer.heads,
                                 len(self.transformer.resblocks), self.text_projection.shape[1], *[_addr(t) for t in small],
                                 _linear_desc(_transposed(self, "text_projection"), None, precision, keep), blocks)
 
@@ -579,11 +343,20 @@ class CLIP(nn.Module):
         B, L = ids.shape
         desc, precision = _cached_desc(self, self._text_desc, params=self._text_params(), slot="text")
         out_dim = self.text_projection.shape[1]
-        kpm = None if key_padding_mask is None else key_padding_mask.to(device=ids.device, dtype=torch.uint8).contiguous()
+        kpm = _kpm_u8(key_padding_mask, ids.device)
+        packable = L <= 64 and TEXT_PACKING and precision != 2 and out_dim <= desc.width
+        offs = None
+        if not self.return_patches and kpm is None and L <= 64 and TEXT_PACKING and precision == 2:
+            # exact mode (fp32 MFMA; diagnostics): round 4's form of the packing below, the row count read back by the host
+            offs = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
+            offs[1:] = torch.cumsum(ids.argmax(dim=1) + 1, 0)
+            total = int(offs[B].item())
+            offs = offs if total < 0.9 * B * L else None
+        if not self.return_patches and not packable and offs is None:
+            return _text_forward_eos(desc, precision, ids, kpm)
         nbytes = lib.xmh_clip_workspace_bytes(B, L, desc.width, 0, out_dim if self.return_patches else 0, precision)
         ws = _workspace(nbytes, ids.device)
         eos_tok = torch.empty(B, out_dim, dtype=torch.float32, device=ids.device)
-        packable = L <= 64 and TEXT_PACKING and precision != 2 and out_dim <= desc.width
         if packable and not self.return_patches:
             # only the EOS embedding is wanted and the attention is causal: the tokens behind a caption's EOS cannot reach it, so the
             # tower runs on the rows up to EOS only (bit-identical output, sum(lengths) / (B L) of the work).  Round 5: the lengths are
@@ -592,18 +365,9 @@ class CLIP(nn.Module):
             check(lib.xmh_text_forward_packed_dev(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, precision, ptr(eos_tok), None, ptr(ws), nbytes,
                                                   current_stream()), "xmh_text_forward_packed_dev")
             return eos_tok
-        if not self.return_patches and kpm is None and L <= 64 and TEXT_PACKING and precision == 2:
-            # exact mode (fp32 MFMA; diagnostics): round 4's form of the same packing, the row count read back by the host
-            offs = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
-            offs[1:] = torch.cumsum(ids.argmax(dim=1) + 1, 0)
-            total = int(offs[B].item())
-            if total < 0.9 * B * L:
-                check(lib.xmh_text_forward_packed(ctypes.byref(desc), ptr(ids), ptr(offs), total, B, L, precision, ptr(eos_tok), ptr(ws), nbytes,
-                                                  current_stream()), "xmh_text_forward_packed")
-                return eos_tok
-        if not self.return_patches:
-            check(lib.xmh_text_forward(ctypes.byref(desc), ptr(ids), ptr(kpm), B, L, precision, ptr(eos_tok), None, None, ptr(ws), nbytes,
-                                       current_stream()), "xmh_text_forward")
+        if offs is not None:
+            check(lib.xmh_text_forward_packed(ctypes.byref(desc), ptr(ids), ptr(offs), total, B, L, precision, ptr(eos_tok), ptr(ws), nbytes,
+                                              current_stream()), "xmh_text_forward_packed")
             return eos_tok
         y = torch.empty(B, L, out_dim, dtype=torch.float32, device=ids.device)
         new_mask = None if kpm is None else (kpm.bool() | (ids == self.vocab_size - 1))

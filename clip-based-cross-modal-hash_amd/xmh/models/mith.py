@@ -124,8 +124,7 @@ class MITHHashLayer(nn.Module):
         w, b = lct.hashing.stacked()
         w, b, pe = ops._f32c(w.detach()).contiguous(), ops._f32c(b.detach()).contiguous(), ops._f32c(lct.position.pe.detach()).contiguous()
         keep.extend((mlps, blocks, w, b, pe))
-        heads = lct.transformer.resblocks[0].heads if len(lct.transformer.resblocks) else 1
-        return _lib.MithHead(D, self.k_bits, lct.lta.top_k, len(layers), len(lct.transformer.resblocks), heads, mlps,
+        return _lib.MithHead(D, self.k_bits, lct.lta.top_k, len(layers), len(lct.transformer.resblocks), lct.transformer.heads, mlps,
                              _clip._linear_desc(gcl.common_concept_embedding.weight, None, precision, keep), pe.data_ptr(), blocks,
                              w.data_ptr(), b.data_ptr())
 
@@ -135,7 +134,7 @@ class MITHHashLayer(nn.Module):
         B, L, D = tokens.shape
         params = list(gcl.parameters()) + list(lct.parameters()) + list(lct.buffers())
         desc, precision = _clip._cached_desc(lct, lambda prec, keep: self._desc(gcl, lct, prec, keep), params=params, slot="mith")
-        m = None if mask is None else mask.to(device=tokens.device, dtype=torch.uint8).contiguous()
+        m = _clip._kpm_u8(mask, tokens.device)
         nbytes = lib.xmh_head_mith_workspace_bytes(B, L, D, self.k_bits, precision)
         ws = _clip._workspace(nbytes, tokens.device)
         cls_hash = torch.empty(B, self.k_bits, dtype=torch.float32, device=tokens.device)

@@ -163,32 +163,29 @@ class _CEntry:
     """forward kept once; backward through the C ABI with chosen pointers"""
 
     def __init__(self, case):
-        from xmh.models import clip
+        from xmh.models import clip_train as CT
+        self.CT = CT
         self.D, self.heads, self.layers, self.L, self.B, self.causal, _ = BC.CASES[case]
         sd, x, up, kpm = BC.case_inputs(case)
         self.tr = _stack(sd, self.D, self.heads, self.layers)
-        self.params = [p for blk in self.tr.resblocks for p in self.tr._train_params(blk)]
+        self.params = CT.block_params(self.tr)
         self.kpm = None if kpm is None else torch.tensor(kpm).cuda().to(torch.uint8)
         self.up = torch.tensor(up).cuda()
-        self.y, self.buf = clip._train_forward(self.tr, torch.tensor(x).cuda(), self.causal, self.kpm, self.params)
-        self.keep = []
-        self.blocks = clip._exact_desc(self.tr, self.params, self.keep)
+        self.y, self.buf, self.blocks, self.keep = CT.blocks_forward(self.tr, torch.tensor(x).cuda(), self.causal, self.kpm, self.params)
 
     def backward(self, want, need_dx=1, accumulate=0, init=None, buf=None, saved_bytes=None, ws_bytes=None, dy="up", width=None, heads=None,
                  L=None):
         """want(layer, kind) -> bool; init: value the gradient buffers hold before the call -> ({name: tensor}, dy, rc)"""
-        from xmh import _lib
         from xmh._lib import current_stream, lib, ptr
-        bufs, grads = {}, (_lib.ClipBlockGrads * self.layers)()
-        for i in range(self.layers):
-            row = []
-            for (kind, _), p in zip(BC.PARAMS, self.params[12 * i:12 * i + 12]):
-                t = None
-                if want(i, kind):
-                    t = torch.full_like(p, float("nan")) if init is None else init["g_l%d_%s" % (i, kind)].clone()
-                    bufs["g_l%d_%s" % (i, kind)] = t
-                row.append(None if t is None else t.data_ptr())
-            grads[i] = _lib.ClipBlockGrads(*row)
+        bufs, gp = {}, []
+        kinds = [(i, kind) for i in range(self.layers) for kind, _ in self.CT.BLOCK]
+        for (i, kind), p in zip(kinds, self.params):
+            t = None
+            if want(i, kind):
+                t = torch.full_like(p, float("nan")) if init is None else init["g_l%d_%s" % (i, kind)].clone()
+                bufs["g_l%d_%s" % (i, kind)] = t
+            gp.append(t)
+        grads = self.CT.block_grads(gp)
         dyt = self.up.clone() if dy == "up" else None
         buf = self.buf if buf is None else buf
         n = lib.xmh_clip_blocks_backward_ws_bytes(self.B, self.L, self.D)

@@ -214,41 +214,40 @@ class _CEntry:
     def __init__(self, case):
         from xmh import _lib
         from xmh._lib import check, current_stream, lib, ptr
-        from xmh.models import clip
+        from xmh.models import clip_train as CT
         self.tower = TC.tower_of(case)
         sd, x, up, kpm = TC.case_inputs(case)
         self.m = _module(self.tower, sd)
         self.x, self.up = torch.tensor(x).cuda(), torch.tensor(up).cuda()
         self.kpm = None if kpm is None else torch.tensor(kpm).cuda().to(torch.uint8)
         self.keep = []
-        self.names = list(TC.tower_parameters(self.tower, self.m))
         named = TC.tower_parameters(self.tower, self.m)
+        self.order = list(named)                                                # the names of the test's cases, in the order of the struct's fields
         B = self.x.shape[0]
         if self.tower == "img":
             vis = self.m.visual
-            self.params = clip._vit_params(vis)
-            self.order = ["g_conv1", "g_cls", "g_pos", "g_ln_pre_w", "g_ln_pre_b", "g_ln_post_w", "g_ln_post_b", "g_proj"]
-            self.desc = clip._vit_exact_desc(vis, self.params, self.keep)
-            self.L, self.D, conv_k, out_dim, self.layers = clip._vit_sizes(vis, B)
-            self.sbytes = lib.xmh_vit_train_saved_bytes(B, self.L, self.D, self.layers)
-            self.nbytes = lib.xmh_vit_train_ws_bytes(B, self.L, self.D, conv_k, out_dim)
+            self.struct, self.table = _lib.VitGrads, CT.VIT
+            self.params = CT.tower_params(vis, CT.VIT)
+            self.desc = d = CT.vit_desc(vis, self.params, self.keep)
+            self.L = vis.positional_embedding.shape[0]
+            self.sbytes = lib.xmh_vit_train_saved_bytes(B, self.L, d.width, d.layers)
+            self.nbytes = lib.xmh_vit_train_ws_bytes(B, self.L, d.width, d.conv1.k, d.out_dim)
         else:
-            self.params = clip._text_train_params(self.m)
-            self.order = ["g_tok", "g_pos", "g_ln_final_w", "g_ln_final_b", "g_text_projection"]
-            self.desc = clip._text_exact_desc(self.m, self.params, self.keep)
-            self.L, self.D, out_dim = self.x.shape[1], self.params[0].shape[1], self.params[4].shape[1]
-            self.layers = len(self.m.transformer.resblocks)
-            self.sbytes = lib.xmh_text_train_saved_bytes(B, self.L, self.D, self.layers)
-            self.nbytes = lib.xmh_text_train_ws_bytes(B, self.L, self.D, out_dim)
-        self.order += [n for n in self.names if re.match(r"g_l\d+_", n)]
-        assert [named[n].data_ptr() for n in self.order] == [p.data_ptr() for p in self.params]
+            self.struct, self.table = _lib.TextGrads, CT.TEXT
+            self.params = CT.tower_params(self.m, CT.TEXT)
+            self.desc = d = CT.text_desc(self.m, self.params, self.keep)
+            self.L = self.x.shape[1]
+            self.sbytes = lib.xmh_text_train_saved_bytes(B, self.L, d.width, d.layers)
+            self.nbytes = lib.xmh_text_train_ws_bytes(B, self.L, d.width, d.out_dim)
+        self.D, self.layers, out_dim = d.width, d.layers, d.out_dim
+        assert [named[n].data_ptr() for n in self.order] == [p.data_ptr() for p in self.params]     # the package's tables agree with them
         assert self.sbytes > 0 and self.nbytes > 0
         self.B = B
         self.buf = torch.empty(self.sbytes // 4, dtype=torch.float32, device="cuda")
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
         self.y = torch.empty(B, out_dim, dtype=torch.float32, device="cuda")
         self.eos = torch.empty(B, dtype=torch.int32, device="cuda")
-        self._lib, self.lib, self.ptr, self.stream = _lib, lib, ptr, current_stream
+        self.CT, self.lib, self.ptr, self.stream = CT, lib, ptr, current_stream
         check(self.forward(), "train forward")
 
     def forward(self, saved_bytes=None, ws_bytes=None, y="y"):
@@ -262,25 +261,18 @@ class _CEntry:
 
     def backward(self, want=lambda n: True, accumulate=0, init=None, saved_bytes=None, ws_bytes=None, g="up", L=None):
         """-> ({name: gradient buffer}, rc); init: what the buffers hold before the call (NaN when not given)"""
-        _lib, lib, ptr = self._lib, self.lib, self.ptr
+        lib, ptr = self.lib, self.ptr
         bufs = {}
         for n, p in zip(self.order, self.params):
             if want(n):
                 bufs[n] = torch.full_like(p, float("nan")) if init is None else init[n].clone()
-        a = lambda n: None if n not in bufs else bufs[n].data_ptr()                # noqa: E731
-        own = len(self.order) - 12 * self.layers
-        blocks = (_lib.ClipBlockGrads * max(self.layers, 1))()
-        for i in range(self.layers):
-            blocks[i] = _lib.ClipBlockGrads(*[a(n) for n in self.order[own + 12 * i:own + 12 * i + 12]])
+        grads = self.CT.tower_grads(self.struct, self.table, [bufs.get(n) for n in self.order])
         sb, nb = self.sbytes if saved_bytes is None else saved_bytes, self.nbytes if ws_bytes is None else ws_bytes
         gp = ptr(self.up) if g == "up" else None
         if self.tower == "img":
-            grads = _lib.VitGrads(a("g_proj"), a("g_ln_post_w"), a("g_ln_post_b"), a("g_ln_pre_w"), a("g_ln_pre_b"), a("g_pos"), a("g_cls"),
-                                  a("g_conv1"), blocks)
             rc = lib.xmh_vit_backward(ctypes.byref(self.desc), ptr(self.x), self.B, ptr(self.buf), sb, gp, ctypes.byref(grads), accumulate,
                                       ptr(self.ws), nb, self.stream())
         else:
-            grads = _lib.TextGrads(a("g_text_projection"), a("g_ln_final_w"), a("g_ln_final_b"), a("g_pos"), a("g_tok"), blocks)
             rc = lib.xmh_text_backward(ctypes.byref(self.desc), ptr(self.x), ptr(self.kpm), ptr(self.eos), self.B, L or self.L, ptr(self.buf), sb, gp,
                                        ctypes.byref(grads), accumulate, ptr(self.ws), nb, self.stream())
         return bufs, rc
@@ -305,6 +297,34 @@ def test_c_entry_reproduces_autograd_and_accumulate_adds(case):
         assert torch.equal(acc[n], g0[n] + a[n]), n
     none, rc = c.backward(want=lambda n: False)                                  # nothing asked for: nothing launched, nothing written
     assert rc == 0 and not none
+
+
+# 5b a parameter changed in place between forward and backward: the backward reuses the forward's descriptor, so autograd must refuse
+@pytest.mark.parametrize("case,name", [("img_r8_p4_d64_b1", "visual.proj"), ("txt_v64_c16_d64_b3", "text_projection")])
+def test_an_inplace_change_of_a_parameter_before_backward_is_noticed(case, name):
+    tower = TC.tower_of(case)
+    sd, x, up, kpm = TC.case_inputs(case)
+    m = _module(tower, sd)
+    y = _forward(tower, m, x, kpm)
+    with torch.no_grad():
+        m.get_parameter(name).add_(1)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        (y * torch.tensor(up).cuda()).sum().backward()
+
+
+def test_an_inplace_change_of_a_block_parameter_before_backward_is_noticed():
+    import block_grad_cases as BC
+    from xmh.models.clip import Transformer
+    D, heads, layers, L, B, causal, _ = BC.CASES["d64_l1_b1"]
+    sd, x, up, kpm = BC.case_inputs("d64_l1_b1")
+    tr = Transformer(D, layers, heads)
+    tr.load_state_dict({k: torch.tensor(v) for k, v in sd.items()}, strict=True)
+    tr = tr.cuda()
+    y = tr.run_train(torch.tensor(x).cuda(), causal=causal)
+    with torch.no_grad():
+        tr.resblocks[0].mlp.c_fc.weight.add_(1)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        (y * torch.tensor(up).cuda()).sum().backward()
 
 
 # 6 no host synchronisation -----------------------------------------------------------------------------------------------------

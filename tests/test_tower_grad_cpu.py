@@ -95,6 +95,64 @@ def test_sizes():
     assert vs(2, 5, 64, 0) > 0                                       # a tower without blocks keeps its rows all the same
 
 
+# (B, L, D) -> what the six size functions returned before the scratch sizing, the limit checks and the entry points' prologue were
+# shared (recorded from that library): saved bytes for layers 0, 1, 12; workspaces for conv_k in (48, 3072) x out_dim in (16, 512)
+RECORDED_SIZES = {
+    (1, 5, 64): dict(vit_saved=(1536, 22016, 247296), text_saved=(256, 20736, 246016), clip_saved=(0, 20480, 245760),
+                     vit_ws=(186624, 186624, 235008, 235008), text_ws=(183552, 183552), blocks_ws=104960),
+    (2, 17, 128): dict(vit_saved=(18432, 296960, 3360768), text_saved=(1024, 279552, 3343360), clip_saved=(0, 278528, 3342336),
+                       vit_ws=(510464, 510464, 897536, 897536), text_ws=(470528, 470528), blocks_ws=284416),
+    (41, 50, 64): dict(vit_saved=(535296, 8932096, 101296896), text_saved=(10496, 8407296, 100772096), clip_saved=(0, 8396800, 100761600),
+                       vit_ws=(7630848, 7630848, 40385792, 40385792), text_ws=(6009344, 6009344), blocks_ws=3607296),
+    (128, 50, 768): dict(vit_saved=(20054016, 334626816, 3794927616), text_saved=(393216, 314966016, 3775266816),
+                         clip_saved=(0, 314572800, 3774873600), vit_ws=(264172800, 264959232, 337777920, 340825344),
+                         text_ws=(221779200, 224826624), blocks_ws=113741824),
+    (128, 77, 512): dict(vit_saved=(20447232, 343408640, 3895984128), text_saved=(262144, 323223552, 3875799040),
+                         clip_saved=(0, 322961408, 3875536896), vit_ws=(270167296, 270691584, 398847232, 398847232),
+                         text_ws=(226684160, 228715776), blocks_ws=111306752),
+}
+
+
+def test_sizes_are_the_recorded_ones():
+    from xmh._lib import lib
+    for s, want in RECORDED_SIZES.items():
+        got = dict(vit_saved=tuple(lib.xmh_vit_train_saved_bytes(*s, n) for n in (0, 1, 12)),
+                   text_saved=tuple(lib.xmh_text_train_saved_bytes(*s, n) for n in (0, 1, 12)),
+                   clip_saved=tuple(lib.xmh_clip_saved_bytes(*s, n) for n in (0, 1, 12)),
+                   vit_ws=tuple(lib.xmh_vit_train_ws_bytes(*s, k, o) for k in (48, 3072) for o in (16, 512)),
+                   text_ws=tuple(lib.xmh_text_train_ws_bytes(*s, o) for o in (16, 512)),
+                   blocks_ws=lib.xmh_clip_blocks_backward_ws_bytes(*s))
+        assert got == want, s
+    vs, vw, ts, tw = lib.xmh_vit_train_saved_bytes, lib.xmh_vit_train_ws_bytes, lib.xmh_text_train_saved_bytes, lib.xmh_text_train_ws_bytes
+    zeros = [vs(0, 50, 768, 12), vw(4, 50, 768, 0, 512), ts(4, 0, 512, 12), tw(4, 32, 512, 0), vs(4, 129, 768, 1), tw(4, 129, 512, 512),
+             vs(4, 50, 1028, 1), ts(4, 32, 510, 1), vw(2, 129, 64, 48, 16), ts(2, 8, 66, 1), lib.xmh_clip_blocks_backward_ws_bytes(4, 129, 512),
+             lib.xmh_clip_blocks_backward_ws_bytes(0, 32, 512), lib.xmh_clip_blocks_backward_ws_bytes(4, 32, 510)]
+    assert zeros == [0] * len(zeros)
+
+
+def test_tables_state_the_parameter_order_once():
+    import block_grad_cases as BC
+    from xmh import _lib
+    from xmh.models import clip_train as CT
+    from xmh.models.clip import CLIP
+    fields = lambda struct: [n for n, _ in struct._fields_ if n != "blocks"]      # noqa: E731
+    for table, struct in ((CT.BLOCK, _lib.ClipBlockGrads), (CT.VIT, _lib.VitGrads), (CT.TEXT, _lib.TextGrads)):
+        assert [name for name, _ in table] == fields(struct)
+    assert CT.BLOCK == BC.PARAMS                                    # the cases' names are the table's
+    m = CLIP(16, 8, 1, 64, 4, 8, 16, 64, 1, 1)
+    blk = m.transformer.resblocks[0]
+    for module, table in ((blk, CT.BLOCK), (m.visual, CT.VIT), (m, CT.TEXT)):
+        assert all(isinstance(module.get_parameter(path), torch.nn.Parameter) for _, path in table)
+    img = CT.tower_params(m.visual, CT.VIT)
+    txt = CT.tower_params(m, CT.TEXT)
+    assert len(img) == len(CT.VIT) + len(CT.BLOCK) and len(txt) == len(CT.TEXT) + len(CT.BLOCK)
+    assert [id(p) for p in CT.block_params(m.transformer)] == [id(blk.get_parameter(path)) for _, path in CT.BLOCK]
+    assert [id(p) for p in m.transformer._train_params(blk)] == [id(p) for p in CT.block_params(m.transformer)]
+    assert sorted(map(id, img)) == sorted(id(p) for p in m.visual.parameters())                   # each exactly once
+    mine = set(map(id, img))
+    assert sorted(map(id, txt)) == sorted(id(p) for p in m.parameters() if id(p) not in mine and p is not m.logit_scale)
+
+
 def test_argument_errors_without_a_gpu():
     from xmh import _lib
     L = _lib.lib
