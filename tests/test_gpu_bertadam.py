@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import bertadam_cases as BC
+from train_step_cases import dcmht_head as _dcmht64
 
 pytestmark = pytest.mark.gpu
 
@@ -328,19 +329,6 @@ def _labels(B, C):
     return L
 
 
-def _dcmht64(x, t, bn, eps):
-    e = x.shape[1]
-    F = torch.nn.functional
-    o = F.linear(F.linear(x, t["atten.in_proj_weight"][2 * e:], t["atten.in_proj_bias"][2 * e:]), t["atten.out_proj.weight"],
-                 t["atten.out_proj.bias"])
-    if bn:
-        n = (o - o.mean(0)) / torch.sqrt(o.var(0, unbiased=False) + eps) * t["norm.weight"] + t["norm.bias"]
-    else:
-        n = F.layer_norm(o, (e,), t["norm.weight"], t["norm.bias"], eps)
-    f = torch.relu(F.linear(n, t["fc2.weight"], t["fc2.bias"]))
-    return torch.softmax(f.view(f.shape[0], -1, 2), -1).view(f.shape[0], -1)
-
-
 class _Restated:
     """the BertAdam step on float64 torch leaves, through step_f64; one hyper-parameter set"""
 
@@ -402,8 +390,8 @@ def test_dcmht_heads_follow_the_restatement_behind_build_optimizer(tmp_path):
         loss, loss_dict = model.object_function(hi, ht, labels.cuda())
         loss.backward()
         assert all(p.grad is not None for p in model.hash.parameters()) and all(p.grad is None for p in model.backbone.parameters())
-        pi = _dcmht64(xi, {k[len("img_hash."):]: v for k, v in d.items() if k.startswith("img_hash.")}, True, 1e-5)
-        pt = _dcmht64(xt, {k[len("txt_hash."):]: v for k, v in d.items() if k.startswith("txt_hash.")}, False, 1e-5)
+        pi = _dcmht64(xi, {k[len("img_hash."):]: v for k, v in d.items() if k.startswith("img_hash.")}, True, 1e-5)[0]
+        pt = _dcmht64(xt, {k[len("txt_hash."):]: v for k, v in d.items() if k.startswith("txt_hash.")}, False, 1e-5)[0]
         want = OL.our_loss(pi, pt, labels, K, vartheta=model.vartheta, threshold=model.threshold, quan_alpha=model.quan_alpha)["loss"]
         want.backward()
         print("dcmht step loss %.8f want %.8f" % (float(loss), float(want)))
