@@ -15,6 +15,15 @@
 // with the host.  There are no float atomics: every sum has one fixed order, so two calls on the same inputs agree to the bit.
 // The dot products that decide a relu' mask ([cos > thr]) are formed in the same lane order by every kernel that needs them, so the
 // forward, the row gradient and the proxy gradient see the same mask.
+// Non-finite inputs pass through as they do through the reference's expression, they are not masked: a NaN similarity gives a NaN
+// hinge (F.relu keeps it, fmaxf would drop it) and a NaN weight in the gradient ([NaN > thr] would drop it), a NaN norm gives a NaN
+// 1 / norm (clamp_min keeps it), and a column is skipped for its zero weights only when the norm behind them is finite (1 / Inf = 0
+// makes the weight of a label -0, and the reference multiplies that column in: 0 * Inf = NaN).
+// So a NaN or Inf in a proxy makes neg, neg_t (pos, pos_t where a row carries its class) and the loss NaN, every row of grad_x and
+// grad_y NaN and that proxy's row of grad_P NaN; a NaN or Inf in a code row makes the terms that row enters NaN, its own gradient
+// row NaN and every row of grad_P NaN.
+// The reference's backward multiplies every row of M into its pair products, the pairs that share a class with weight 0: a row of M
+// whose norm is not finite therefore turns the x and y gradients of every row of M NaN (0 * NaN), here as there.
 // Bound: B = 100, K = 16..128, C = 80 (COCO, configs[4]) is a few tens of KB of L2-resident operands: launch-latency bound.
 #include "xmh_common.h"
 #include "xmh_device.h"
@@ -50,16 +59,26 @@ __host__ __device__ inline size_t ws_layout(int64_t B, int C, void* base, WsView
 
 using xmh::wave_sum;
 
-__device__ __forceinline__ float inv_norm(float n) { return 1.0f / fmaxf(n, kEps); }
+__device__ __forceinline__ float inv_norm(float n) { return 1.0f / (n < kEps ? kEps : n); }   // a NaN norm stays NaN (fmaxf drops it)
+
+// relu(v) as F.relu forms it: NaN stays NaN
+__device__ __forceinline__ float hinge(float v) { return isnan(v) ? v : fmaxf(v, 0.0f); }
+
+// relu'(sim - thr) * w, with a NaN similarity handed on as the weight: the reference's backward ends in NaN wherever it enters
+__device__ __forceinline__ float hinge_weight(float sim, float thr, float w) { return sim > thr ? w : (isnan(sim) ? sim : 0.0f); }
 
 __device__ __forceinline__ bool has_label(const uint32_t* lab, int Lw, int row, int c) {
     return (lab[(int64_t)row * Lw + (c >> 5)] >> (c & 31)) & 1u;
 }
 
-// Is row j (lanes < Lw hold its label words in w) a regulariser partner of the row whose words are `mine` (itself in M)?
-// j must be in M as well (>= 2 labels) and share no class with it.  Wave-uniform.
-__device__ __forceinline__ bool disjoint_partner(uint32_t mine, uint32_t w) {
-    return wave_sum((int)__popc(w)) >= 2 && __ballot((mine & w) != 0u) == 0ull;
+// Row j (lanes < Lw hold its label words in w) against the row whose words are `mine` (itself in M).  in_m: j is in M as well (>= 2
+// labels).  disjoint: it is then a regulariser partner, sharing no class.  Wave-uniform.
+struct Partner {
+    bool in_m, disjoint;
+};
+__device__ __forceinline__ Partner partner_of(uint32_t mine, uint32_t w) {
+    const bool in_m = wave_sum((int)__popc(w)) >= 2;
+    return {in_m, in_m && __ballot((mine & w) != 0u) == 0ull};
 }
 
 // Blocks [0, B): row i of the codes.  Blocks [B, B + C): the norm of proxy c.
@@ -119,8 +138,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
                 acc[0] += (double)(1.0f - cs);
                 acc[2] += (double)(1.0f - ct);
             } else {
-                acc[1] += (double)fmaxf(cs - thr, 0.0f);
-                acc[3] += (double)fmaxf(ct - thr, 0.0f);
+                acc[1] += (double)hinge(cs - thr);
+                acc[3] += (double)hinge(ct - thr);
             }
         }
     }
@@ -128,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
     if (alpha > 0.0f && npos >= 2) {
         for (int j = wave; j < B; j += kWaves) {
             const uint32_t w = lane < Lw ? lab[(int64_t)j * Lw + lane] : 0u;
-            if (!disjoint_partner(mine, w)) continue;
+            if (!partner_of(mine, w).disjoint) continue;
             ++z;
             if (kLoss) {
                 const float* xj = x + (int64_t)j * K;
@@ -143,9 +162,9 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
                     ny2 = fmaf(b, b, ny2);
                 }
                 const float ixj = inv_norm(sqrtf(wave_sum(nx2))), iyj = inv_norm(sqrtf(wave_sum(ny2)));
-                acc[4] += (double)fmaxf(wave_sum(dxx) * ix * ixj - thr, 0.0f);
-                acc[5] += (double)fmaxf(wave_sum(dyy) * iy * iyj - thr, 0.0f);
-                acc[6] += (double)fmaxf(wave_sum(dxy) * ix * iyj - thr, 0.0f);
+                acc[4] += (double)hinge(wave_sum(dxx) * ix * ixj - thr);
+                acc[5] += (double)hinge(wave_sum(dyy) * iy * iyj - thr);
+                acc[6] += (double)hinge(wave_sum(dxy) * ix * iyj - thr);
             }
         }
     }
@@ -207,7 +226,7 @@ __device__ __forceinline__ void normalize_backward_store(const float* v, float n
         if (k < K) vd = fmaf(v[k], du[r], vd);
     }
     vd = xmh::block_sum<kWaves>(vd, sh);
-    const float s = nv >= kEps ? vd * iv : 0.0f;                 // u . du; a clamped row passes du / eps only
+    const float s = nv < kEps ? 0.0f : vd * iv;                  // u . du; a clamped row passes du / eps only, a NaN norm stays NaN
 #pragma unroll
     for (int r = 0; r < kSlots; ++r) {
         const int k = threadIdx.x + r * kThreads;
@@ -267,8 +286,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                     d = fmaf(xs[k], p, d);
                     dt = fmaf(ys[k], p, dt);
                 }
-                a = wave_sum(d) * ix * ip > thr ? wneg * ip : 0.0f;
-                b = wave_sum(dt) * iy * ip > thr ? wneg * ip : 0.0f;
+                a = hinge_weight(wave_sum(d) * ix * ip, thr, wneg * ip);
+                b = hinge_weight(wave_sum(dt) * iy * ip, thr, wneg * ip);
             }
             if (lane == 0) {
                 cw[c] = a;
@@ -278,7 +297,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
         __syncthreads();
         for (int c = 0; c < C; ++c) {
             const float a = cw[c], b = ctw[c];
-            if (a == 0.0f && b == 0.0f) continue;
+            // nothing to add; a NaN weight is not skipped, nor the +-0 weights of a proxy with an Inf norm (0 * Inf = NaN)
+            if (a == 0.0f && b == 0.0f && !isinf(ws.np[c])) continue;
             const float* pc = P + (int64_t)c * K;
 #pragma unroll
             for (int r = 0; r < kSlots; ++r) {
@@ -294,11 +314,21 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
             const uint32_t mine = lane < Lw ? lab[(int64_t)i * Lw + lane] : 0u;
             for (int j0 = 0; j0 < B; j0 += kChunk) {
                 const int n = min(kChunk, B - j0);
+                // The first chunk goes on from the proxies' sums; every later chunk is summed from zero and then added.  The partners of
+                // a row point much the same way, so a running fp32 sum loses bits with its length: at B = 513 one chain over all
+                // partners was 3.9 times the reference's own fp32 error in d/dx, against 2.5 - 3.7 at B <= 300.
+                float tx[kSlots], ty[kSlots];
+#pragma unroll
+                for (int r = 0; r < kSlots; ++r) {
+                    tx[r] = j0 == 0 ? ax[r] : 0.0f;
+                    ty[r] = j0 == 0 ? ay[r] : 0.0f;
+                }
                 for (int jj = wave; jj < n; jj += kWaves) {
                     const int j = j0 + jj;
                     const uint32_t w = lane < Lw ? lab[(int64_t)j * Lw + lane] : 0u;
                     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
-                    if (disjoint_partner(mine, w)) {
+                    const Partner pj = partner_of(mine, w);
+                    if (pj.disjoint) {
                         const float* xj = x + (int64_t)j * K;
                         const float* yj = y + (int64_t)j * K;
                         float dxx = 0.0f, dyy = 0.0f, dxy = 0.0f, dyx = 0.0f;
@@ -311,10 +341,15 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                         }
                         const float ixj = inv_norm(ws.nx[j]), iyj = inv_norm(ws.ny[j]);
                         // x-x and y-y: the pair masks are symmetric, so row i collects both (i, j) and (j, i)
-                        c0 = wave_sum(dxx) * ix * ixj > thr ? 2.0f * wreg * ixj : 0.0f;   // x_j into d/dx_i
-                        c1 = wave_sum(dxy) * ix * iyj > thr ? wreg * iyj : 0.0f;          // y_j into d/dx_i (x-y term, i first)
-                        c2 = wave_sum(dyy) * iy * iyj > thr ? 2.0f * wreg * iyj : 0.0f;   // y_j into d/dy_i
-                        c3 = wave_sum(dyx) * ixj * iy > thr ? wreg * ixj : 0.0f;          // x_j into d/dy_i (x-y term, i second)
+                        c0 = hinge_weight(wave_sum(dxx) * ix * ixj, thr, 2.0f * wreg * ixj);   // x_j into d/dx_i
+                        c1 = hinge_weight(wave_sum(dxy) * ix * iyj, thr, wreg * iyj);          // y_j into d/dx_i (x-y term, i first)
+                        c2 = hinge_weight(wave_sum(dyy) * iy * iyj, thr, 2.0f * wreg * iyj);   // y_j into d/dy_i
+                        c3 = hinge_weight(wave_sum(dyx) * ixj * iy, thr, wreg * ixj);          // x_j into d/dy_i (x-y term, i second)
+                    } else if (pj.in_m) {
+                        // a masked pair of M x M (i itself among them): weight 0 in the reference's products n(x_M) n(x_M)^T ..., which still
+                        // multiply row j in.  0 * norm is 0 for a finite norm (skipped below) and NaN for a NaN or Inf one.
+                        c0 = c3 = 0.0f * ws.nx[j];
+                        c1 = c2 = 0.0f * ws.ny[j];
                     }
                     if (lane == 0) {
                         pw[jj] = c0;
@@ -334,10 +369,15 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                         const int k = threadIdx.x + r * kThreads;
                         if (k < K) {
                             const float a = xj[k], b = yj[k];
-                            ax[r] = fmaf(c1, b, fmaf(c0, a, ax[r]));
-                            ay[r] = fmaf(c3, a, fmaf(c2, b, ay[r]));
+                            tx[r] = fmaf(c1, b, fmaf(c0, a, tx[r]));
+                            ty[r] = fmaf(c3, a, fmaf(c2, b, ty[r]));
                         }
                     }
+                }
+#pragma unroll
+                for (int r = 0; r < kSlots; ++r) {
+                    ax[r] = j0 == 0 ? tx[r] : ax[r] + tx[r];
+                    ay[r] = j0 == 0 ? ty[r] : ay[r] + ty[r];
                 }
                 __syncthreads();
             }
@@ -367,8 +407,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                         d = fmaf(xi[k], p, d);
                         dt = fmaf(yi[k], p, dt);
                     }
-                    a = wave_sum(d) * ixi * ip > thr ? wneg * ixi : 0.0f;
-                    b = wave_sum(dt) * iyi * ip > thr ? wneg * iyi : 0.0f;
+                    a = hinge_weight(wave_sum(d) * ixi * ip, thr, wneg * ixi);
+                    b = hinge_weight(wave_sum(dt) * iyi * ip, thr, wneg * iyi);
                 }
                 if (lane == 0) {
                     wx[ii] = a;
@@ -378,7 +418,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
             __syncthreads();
             for (int ii = 0; ii < n; ++ii) {
                 const float a = wx[ii], b = wy[ii];
-                if (a == 0.0f && b == 0.0f) continue;
+                if (a == 0.0f && b == 0.0f && !isinf(ws.nx[i0 + ii]) && !isinf(ws.ny[i0 + ii])) continue;   // as in the row blocks
                 const float* xi = x + (int64_t)(i0 + ii) * K;
                 const float* yi = y + (int64_t)(i0 + ii) * K;
 #pragma unroll

@@ -619,12 +619,18 @@ int xmh_quant_loss_grad(const float* code, int64_t n, float scale, const float* 
  * ------------------------------------------------------------------------------------------- */
 size_t xmh_hyp_loss_ws_bytes(int64_t B, int K, int C);
 /* out8 (device, 8 doubles) = (loss, pos, neg, pos_t, neg_t, reg, reg_t, reg_xt); loss is their sum.  P_num == 0 or N_num == 0
- * gives NaN terms (0 / 0) as the reference does; alpha <= 0, or no pair of multi-label rows with disjoint labels, gives reg = 0. */
+ * gives NaN terms (0 / 0) as the reference does; alpha <= 0, or no pair of multi-label rows with disjoint labels, gives reg = 0.
+ * Non-finite inputs are not masked: a NaN or Inf in a proxy or a code row makes every term NaN that one of its cosines enters (the
+ * hinge keeps a NaN as F.relu does), and with it the loss; the other terms stay finite. */
 int xmh_hyp_loss(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab,
                  float threshold, float alpha, void* ws, size_t ws_bytes, double* out8, xmh_stream_t stream);
 /* d loss / d x, d y, d P as autograd derives them from the reference's expression (relu'(0) = 0; F.normalize's backward, a row
  * clamped by its eps receiving du / 1e-12).  grad_x [B, K], grad_y [B, K] and grad_P [C, K] (device, all required) are written,
- * or added to when accumulate != 0, with upstream[0] (device float, NULL = 1) folded in. */
+ * or added to when accumulate != 0, with upstream[0] (device float, NULL = 1) folded in.
+ * Non-finite inputs give the NaN rows of the reference's backward, not a finite gradient: a NaN or Inf in proxy c makes every row of
+ * grad_x and grad_y and row c of grad_P NaN; one in a code row makes that row of its gradient and every row of grad_P NaN, and,
+ * when the row has two or more labels and the regulariser is live, the grad_x and grad_y rows of every such row (the reference's pair
+ * products multiply every multi-label row in, masked pairs with weight 0). */
 int xmh_hyp_loss_grad(const float* x, const float* y, const float* P, int64_t B, int K, int C, const uint32_t* lab,
                       float threshold, float alpha, const float* upstream, float* grad_x, float* grad_y, float* grad_P,
                       int accumulate, void* ws, size_t ws_bytes, xmh_stream_t stream);
