@@ -10,7 +10,8 @@
 //   xmh_mith_loss       k_mith_lik<false>  (4B stacked code columns x N-row chunks: 64 x 64 dot tiles, per-block partials of the
 //                                           four likelihood sums)
 //                       k_mith_nce_logits  (64 x 64 logit tiles of the cls problem and of every sample's token problem -> ws)
-//                       k_mith_nce_lse     (one wave per logit row and column: log-sum-exp, its cross-entropy term -> ws)
+//                       k_mith_nce_lse     (one wave per logit row and column: log-sum-exp as (max, log sum), its cross-entropy
+//                                           term -> ws)
 //                       k_mith_finalize    (one block: ordered sums of the partials, quantisation, distillation -> out10)
 //   xmh_mith_loss_grad  k_mith_lik<true>   (the same dot tiles -> the weights (S - sigma(s)) m in LDS -> per-chunk partials of
 //                                           sum_n w[n, b] Y[n] for each code column)
@@ -24,6 +25,11 @@
 // per-block partials summed in index order: no float atomics, two calls on the same inputs agree to the bit.  The forward and the
 // gradient form the likelihood dot products with the same routine, so both see the same clamp mask.  No call allocates or
 // synchronises with the host.
+//
+// Non-finite inputs pass through as they do through the reference's expression.  A NaN dot product (a NaN in a buffer or code row,
+// or Inf entries of both signs) stays NaN through the clamp, so the likelihoods it enters and the loss are NaN: the buffer keeps such a
+// row for the rest of the epoch, and every step that reads it must say so.  In the gradient the clamp's mask is a select, 0 for a NaN
+// product as torch's clamp backward selects it, so only 0 * Y[n] of the non-finite entries of that buffer row turns NaN.
 #include "xmh_common.h"
 #include "xmh_device.h"
 
@@ -57,7 +63,9 @@ __host__ __device__ inline LikGrid lik_grid(int64_t N, int B) {
 struct WsView {
     double* lik;      // [P * ctiles][4] per-block likelihood sums of S s - log(1 + exp(s))
     double* ce;       // [2B + 2BK] cross-entropy term of each logit line (cls rows, cls cols, token rows, token cols)
-    float* lse;       // [2B + 2BK] log-sum-exp of each line
+    float2* lse;      // [2B + 2BK] log-sum-exp of each line in two parts: x = its largest logit m, y = log sum exp(logit - m).  One
+                      // float for m + log(...) would carry the rounding of a number the size of the logits (up to 1 / tau = 14) into
+                      // every softmax; log_softmax as torch forms it, (logit - m) - log(...), does not
     float* logits;    // [B * B] cls, then [B][K][K] tokens (already divided by tau)
     float* gpart;     // [P][4B][K] per-chunk likelihood gradient sums (gradient only)
 };
@@ -69,7 +77,7 @@ __host__ __device__ inline size_t ws_layout(int64_t N, int B, int K, void* base,
     WsView w;
     w.lik = ar.take<double>((size_t)g.P * g.ctiles * 4);
     w.ce = ar.take<double>(lines);
-    w.lse = ar.take<float>(lines);
+    w.lse = ar.take<float2>(lines);
     w.logits = ar.take<float>((size_t)B * B + (size_t)B * K * K);
     w.gpart = ar.take<float>((size_t)g.P * 4 * B * K);
     if (v) *v = w;
@@ -115,20 +123,20 @@ struct Stacked {
     }
 };
 
-// InfoNCE gradient G[i][j] = coef (softmax_row[i][j] + softmax_col[i][j] - 2 [i == j]) from the stored logits; kT: element (m, k) is
-// G[k][m] (for G^T products)
+// InfoNCE gradient G[i][j] = coef (softmax_row[i][j] + softmax_col[i][j] - 2 [i == j]) from the stored logits and the two parts of
+// each line's log-sum-exp (lr of the rows, lc of the columns); kT: element (m, k) is G[k][m] (for G^T products)
 template <bool kT>
 struct NceG {
     const float* L;
-    const float* lr;
-    const float* lc;
+    const float2 *lr, *lc;
     int R;
     float coef;
     __device__ __forceinline__ float operator()(int m, int k) const {
         const int i = kT ? k : m, j = kT ? m : k;
         if (i >= R || j >= R) return 0.0f;
         const float x = L[(int64_t)i * R + j];
-        const float p = expf(x - lr[i]) + expf(x - lc[j]) - (i == j ? 2.0f : 0.0f);
+        const float2 r = lr[i], c = lc[j];
+        const float p = expf((x - r.x) - r.y) + expf((x - c.x) - c.y) - (i == j ? 2.0f : 0.0f);
         return coef * p;
     }
 };
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_mith_lik(Args a, WsView ws, LikGri
                 const bool live = nl < nrem && c < C4;
                 const int code = live ? c / B : 0;
                 const float d = acc[i][j];
-                const float s = 0.5f * fminf(fmaxf(d, -64.0f), 64.0f);
+                const float s = 0.5f * (isnan(d) ? d : fminf(fmaxf(d, -64.0f), 64.0f));   // torch's clamp keeps a NaN, fmaxf drops it
                 const float Sv = live ? a.S[n * B + (c - code * B)] : 0.0f;
                 const float e = expf(s);
                 if (!kGrad) {
@@ -221,8 +229,8 @@ __global__ __launch_bounds__(kThreads) void k_mith_lik(Args a, WsView ws, LikGri
 #pragma unroll
                     for (int q = 0; q < 4; ++q) part[q] += code == q ? v : 0.0;
                 } else {
-                    const float m = (d >= -64.0f && d <= 64.0f) ? 1.0f : 0.0f;   // clamp' on the closed interval, as torch's
-                    Ws[nl][tn * 4 + j] = live ? wcoef * (Sv - e / (1.0f + e)) * m : 0.0f;
+                    const bool pass = d >= -64.0f && d <= 64.0f;                 // clamp' on the closed interval, as torch's; a
+                    Ws[nl][tn * 4 + j] = live && pass ? wcoef * (Sv - e / (1.0f + e)) : 0.0f;   // select: 0 for a NaN d, not NaN * 0
                 }
             }
         }
@@ -360,8 +368,7 @@ __global__ __launch_bounds__(kThreads) void k_mith_nce_lse(Args a, WsView ws) {
     for (int j = lane; j < R; j += 64) se += expf(L[s0 + j * st] - mx);
     se = wave_sum(se);
     if (lane == 0) {
-        const float lse = mx + logf(se);
-        ws.lse[line] = lse;
+        ws.lse[line] = make_float2(mx, logf(se));
         ws.ce[line] = (double)mx + log((double)se) - (double)L[(int64_t)idx * R + idx];
     }
 }
@@ -460,8 +467,8 @@ __global__ __launch_bounds__(kThreads) void k_mith_grad(Args a, WsView ws, LikGr
         const int m0 = (blk / td) * kTile, n0 = (blk % td) * kTile;
         const int64_t lines = (int64_t)(p == 0 ? B : B * K);
         const float coef = (float)(0.5 / (double)lines);
-        const float* lr = ws.lse + q.line;
-        const float* lc = ws.lse + q.line + q.cstride;
+        const float2* lr = ws.lse + q.line;
+        const float2* lc = ws.lse + q.line + q.cstride;
         float acc[4][4];
         zero(acc);
         if (!second) {

@@ -665,12 +665,18 @@ typedef struct xmh_mith_loss_args {
 } xmh_mith_loss_args;
 size_t xmh_mith_loss_ws_bytes(int64_t N, int B, int K, int D);
 /* out10 (device, 10 doubles) = (loss, intra_i, intra_t, i2t, t2i, quan_i, quan_t, nce_cls, nce_tokens, distillation): the
- * unweighted terms of the reference's loss_dict except distillation, which is weighted as there; loss is the weighted total. */
+ * unweighted terms of the reference's loss_dict except distillation, which is weighted as there; loss is the weighted total.
+ * Non-finite inputs are not masked: a NaN in a buffer row or a code row (or Inf entries that cancel to NaN in a dot product) stays NaN
+ * through the clamp, as through torch's, and makes the likelihoods that product enters and the loss NaN; a NaN code or feature entry
+ * makes the quantisation, distillation or InfoNCE terms it enters NaN; the other terms stay finite.  The buffer keeps a poisoned row
+ * until that row is written again, so every step that reads it reports a NaN loss, as the reference does. */
 int xmh_mith_loss(const xmh_mith_loss_args* args, void* ws, size_t ws_bytes, double* out10, xmh_stream_t stream);
 /* grads: 8 device pointers in the input order (res_img_cls, res_txt_cls, img_cls_hash, txt_cls_hash, tokens_hash_i, tokens_hash_t,
  * trans_tokens_i, trans_tokens_t), each with its input's shape, or NULL when that gradient is not needed.  They are written, or
  * added to when accumulate != 0, with upstream[0] (device float, NULL = 1) folded in.  The clamp's gradient passes on the closed
- * interval [-64, 64], as torch's does. */
+ * interval [-64, 64], as torch's does, and is 0 for a NaN dot product (a select, as in torch's clamp backward): a non-finite entry
+ * k of a buffer row turns entry k of every row of the four code gradients NaN (0 * NaN) and nothing else; a NaN code entry turns
+ * that entry of the gradients it enters elementwise NaN; a NaN feature entry turns both gradients of its InfoNCE problem NaN. */
 int xmh_mith_loss_grad(const xmh_mith_loss_args* args, const float* upstream, float* const* grads, int accumulate, void* ws,
                        size_t ws_bytes, xmh_stream_t stream);
 
