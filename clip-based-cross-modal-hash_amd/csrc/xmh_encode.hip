@@ -16,6 +16,7 @@
 // Every one of these is HBM-bound elementwise / row-reduction work; the GEMMs around them dominate the time.
 #include "xmh_common.h"
 #include "xmh_device.h"
+#include "xmh_lta.h"
 #include "xmh_planes.h"
 
 #include <stdlib.h>
@@ -613,82 +614,12 @@ __global__ __launch_bounds__(256) void k_pair_softmax(const float* __restrict__ 
 
 
 // ---- MITH LocalizedTokenAggregation (models/MITH/hash/hash.py:109-169) + positional encoding (:41-65) ----------
-// One block per sample.  S [B, L, K] concept scores (tanh outputs), X [B, L, D] raw CLIP tokens.
-//   sim = S (+ -inf on masked tokens); sim = sim > 0 ? sim : -inf                                   (:142-153)
-//   per token keep the concepts >= its 8th-largest score (ties kept), others -inf                     (:114-124)
-//   softmax over the TOKEN axis per (sample, concept); a concept with no token gives NaN -> 0         (:159-160)
-//   M[b,k,:] = sum_l A[b,k,l] X[b,l,:]   (+ pe[k,:], the sin/cos table already divided by sqrt(D))    (:164-168, :63)
+// The body is xmh::lta_aggregate_block (xmh_lta.h), which the training forward shares; this instance stores no attention.
 __global__ __launch_bounds__(256) void k_lta_aggregate(const float* __restrict__ S, const float* __restrict__ X,
                                                        const uint8_t* __restrict__ mask, const float* __restrict__ pe,
                                                        float* __restrict__ M, int L, int K, int D, int topk) {
-    // grid (B, ceil(D / 64)): every block rebuilds the [L][K] attention of its sample (cheap, all 256 threads) and aggregates
-    // 64 feature columns -- one block per sample left 60 % of the CUs idle and ran 0.46 ms
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [L][K+1] scores -> attention, then thr[L]
-    const int b = blockIdx.x;
-    const int ld = K + 1;
-    float* thr_s = sm + L * ld;
-    for (int e = threadIdx.x; e < L * K; e += 256) {
-        const int l = e / K, k = e % K;
-        float v = S[((int64_t)b * L + l) * K + k];
-        if (mask && mask[(int64_t)b * L + l]) v = -INFINITY;
-        sm[l * ld + k] = v > 0.0f ? v : -INFINITY;
-    }
-    for (int l = threadIdx.x; l < L; l += 256) thr_s[l] = -INFINITY;
-    __syncthreads();
-    // per-token top-k threshold: the value v with #(> v) < topk <= #(>= v); one (token, candidate) pair per thread step.
-    // Several candidates of a row can qualify only if they are equal, so the racing stores write the same value.
-    for (int e = threadIdx.x; e < L * K; e += 256) {
-        const int l = e / K, i = e % K;
-        const float* row = sm + l * ld;
-        const float v = row[i];
-        int gt = 0, ge = 0;
-        for (int j = 0; j < K; ++j) {
-            gt += row[j] > v;
-            ge += row[j] >= v;
-        }
-        if (gt < topk && topk <= ge) thr_s[l] = v;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < L * K; e += 256) {
-        const int l = e / K, i = e % K;
-        if (!(sm[l * ld + i] >= thr_s[l])) sm[l * ld + i] = -INFINITY;
-    }
-    __syncthreads();
-    // softmax over tokens per concept
-    for (int k = threadIdx.x; k < K; k += 256) {
-        float mx = -INFINITY;
-        for (int l = 0; l < L; ++l) mx = fmaxf(mx, sm[l * ld + k]);
-        if (mx == -INFINITY) {
-            for (int l = 0; l < L; ++l) sm[l * ld + k] = 0.0f;                       // NaN -> 0 in the reference
-        } else {
-            float sum = 0.0f;
-            for (int l = 0; l < L; ++l) {
-                const float p = expf(sm[l * ld + k] - mx);
-                sm[l * ld + k] = p;
-                sum += p;
-            }
-            for (int l = 0; l < L; ++l) sm[l * ld + k] = sm[l * ld + k] / sum;
-        }
-    }
-    __syncthreads();
-    // aggregate 64 feature columns: thread = (column, quarter of the concepts), 16 concepts at a time in registers
-    const int d = blockIdx.y * 64 + (threadIdx.x & 63);
-    const int kq = threadIdx.x >> 6;                                 // 0..3
-    if (d >= D) return;
-    for (int k0 = kq * 16; k0 < K; k0 += 64) {
-        float acc[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc[u] = 0.0f;
-        for (int l = 0; l < L; ++l) {
-            const float x = X[((int64_t)b * L + l) * D + d];
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-                if (k0 + u < K) acc[u] = fmaf(sm[l * ld + k0 + u], x, acc[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-            if (k0 + u < K) M[((int64_t)b * K + k0 + u) * D + d] = acc[u] + (pe ? pe[(int64_t)(k0 + u) * D + d] : 0.0f);
-    }
+    xmh::lta_aggregate_block<false>(sm, S, X, mask, pe, M, nullptr, L, K, D, topk);
 }
 
 // ---- MITH BitwiseHashing (models/MITH/hash/hash.py:68-85): out[b,k] = tanh(w_k . z[b,k,:] + bias_k) (+ addend) ----
@@ -899,8 +830,8 @@ extern "C" int xmh_lta_aggregate(const float* scores, const float* tokens, const
     if (B < 0 || L <= 0 || K <= 0 || D <= 0 || top_k <= 0 || top_k > K) return xmh::fail(XMH_EINVAL, "xmh_lta_aggregate: bad shape L=%d K=%d top_k=%d", L, K, top_k);
     if (B == 0) return XMH_OK;
     if (!scores || !tokens || !out) return xmh::fail(XMH_EINVAL, "xmh_lta_aggregate: null pointer");
-    const size_t lds = ((size_t)L * (K + 1) + L) * 4;
-    if (lds > 160 * 1024) return xmh::fail(XMH_ENOTSUP, "xmh_lta_aggregate: L*K too large for LDS");
+    const size_t lds = xmh::lta_lds_bytes(L, K);
+    if (lds > xmh::kLtaMaxLds) return xmh::fail(XMH_ENOTSUP, "xmh_lta_aggregate: L*K too large for LDS");
     if (const int rl = xmh::raise_dynamic_lds(reinterpret_cast<const void*>(k_lta_aggregate), lds, "xmh_lta_aggregate")) return rl;
     hipLaunchKernelGGL(k_lta_aggregate, dim3((unsigned)B, (unsigned)xmh::ceil_div(D, 64)), dim3(256), lds, xmh::as_stream(stream), scores, tokens, token_mask, pos_enc, out, L, K, D, top_k);
     XMH_LAUNCH_CHECK("xmh_lta_aggregate");

@@ -77,6 +77,14 @@ class MithLossArgs(C.Structure):               # xmh_mith_loss_args
                 ("hyper_lambda", C.c_double), ("temperature", C.c_double)]
 
 
+class MithTrain(C.Structure):                  # xmh_mith_train
+    _fields_ = [("head", MithHead), ("proj", Linear)]
+
+
+class MithMlpGrads(C.Structure):               # xmh_mith_mlp_grads
+    _fields_ = [(n, vp) for n in ("ln_w", "ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
 class DcmhtTrain(C.Structure):                 # xmh_dcmht_train
     _fields_ = [("wv", vp), ("bv", vp), ("wo", vp), ("bo", vp), ("norm_w", vp), ("norm_b", vp), ("running_mean", vp),
                 ("running_var", vp), ("w2", vp), ("b2", vp), ("norm_is_batchnorm", i32), ("eps", C.c_float), ("momentum", C.c_float)]
@@ -97,6 +105,11 @@ class VitGrads(C.Structure):                   # xmh_vit_grads
 
 class TextGrads(C.Structure):                  # xmh_text_grads
     _fields_ = [(n, vp) for n in ("proj", "ln_final_w", "ln_final_b", "pos", "tok")] + [("blocks", C.POINTER(ClipBlockGrads))]
+
+
+class MithGrads(C.Structure):                  # xmh_mith_grads
+    _fields_ = [("mlps", C.POINTER(MithMlpGrads)), ("concept", vp), ("blocks", C.POINTER(ClipBlockGrads))] + \
+               [(n, vp) for n in ("hash_w", "hash_b", "proj_w", "proj_b", "d_cls", "d_tokens")]
 
 
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
@@ -192,6 +205,10 @@ PROTOTYPES = {
     "xmh_head_dcmht_backward": (i32, [C.POINTER(DcmhtTrain), vp, vp, i64, i32, i32, vp, sz, C.POINTER(DcmhtGrads), i32, vp, sz, vp]),
     "xmh_head_dsph_train_forward": (i32, [vp, vp, vp, vp, C.c_float, i64, i32, i32, vp, vp]),
     "xmh_head_dsph_backward": (i32, [vp, vp, vp, vp, C.c_float, vp, i64, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
+    "xmh_mith_train_saved_bytes": (sz, [i64, i32, i32, i32, i32, i32]),
+    "xmh_mith_train_ws_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "xmh_mith_train_forward": (i32, [C.POINTER(MithTrain), vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "xmh_mith_train_backward": (i32, [C.POINTER(MithTrain), vp, i64, i32, vp, vp, vp, vp, vp, sz, C.POINTER(MithGrads), i32, vp, sz, vp]),
     "xmh_bertadam_chunk": (i64, []),
     "xmh_bertadam_ws_bytes": (sz, [i64, i64]),
     "xmh_bertadam_step": (i32, [vp, i64, vp, i64, vp, sz, vp]),

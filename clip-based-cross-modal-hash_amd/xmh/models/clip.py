@@ -299,7 +299,8 @@ class CLIP(nn.Module):
         vis = self.visual
         if self.return_patches or vis.return_patches:
             raise NotImplementedError("encode_image_train returns the cls feature only: the patch tokens (return_patches=True) feed MITH's "
-                                      "head, whose backward is not built")
+                                      "head, whose backward (MITHHashLayer.encode_img_train) returns their gradient, but the tower's "
+                                      "training forward does not return them")
         image = ops._f32c(image).contiguous()
         if image.dim() != 4 or image.shape[1:] != (3, vis.input_resolution, vis.input_resolution):
             raise ValueError("image batch is %s, the tower takes [B, 3, %d, %d]" % (tuple(image.shape), vis.input_resolution, vis.input_resolution))
@@ -312,7 +313,8 @@ class CLIP(nn.Module):
         no_grad, or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
         if self.return_patches:
             raise NotImplementedError("encode_text_train returns the EOS feature only: the token outputs (return_patches=True) feed MITH's "
-                                      "head, whose backward is not built")
+                                      "head, whose backward (MITHHashLayer.encode_txt_train) returns their gradient, but the tower's "
+                                      "training forward does not return them")
         if not text.is_cuda:
             raise RuntimeError("xmh ops need CUDA/HIP tensors (got %s); there is no CPU fallback" % text.device)
         ids = text.to(torch.int64).contiguous()

@@ -1,7 +1,12 @@
 """MITH: CLIP in return_patches mode + the concept/token hash head (reference models/MITH/MITH.py:11-76,
 models/MITH/hash/hash.py:9-254), registered as "MITH".  Parameters sit under the reference's key names
 (``hash.gcl_i.mlp.mlps.0.0.weight`` ..., ``gcl_t`` aliasing ``gcl_i`` like in the reference, :218); the eval-path
-dataflow is SURVEY 2.4.  ``res_*_cls`` / ``trans_tokens_*`` only feed the training losses and are returned as None.
+dataflow is SURVEY 2.4.  ``res_*_cls`` / ``trans_tokens_*`` only feed the training losses; the eval path returns them as None.
+
+Training: ``MITHHashLayer.encode_img_train`` / ``encode_txt_train`` run one modality of the head behind one
+torch.autograd.Function whose forward and backward are one C call each (xmh_mith_grad.hip), exact fp32 over the parameters in place.
+Which parameter is which is stated once, in the table ``MLP`` and in ``head_params`` below, in the style of clip_train.py.
+``MITH.forward_train_heads`` puts them behind the frozen towers.
 
 The training objective (reference :116-232) runs through xmh_mith_loss.hip behind ``_MITHLoss`` (a torch.autograd.Function).
 Its rolling code buffer is one [train_num, K] tensor bound to the reference's four names (img_buffer_cls, txt_buffer_cls,
@@ -22,6 +27,7 @@ from .. import _lib, ops, towers
 from .._lib import check, current_stream, lib, ptr
 from ..common.register import registry
 from . import clip as _clip
+from . import clip_train as _ct
 from .base import BaseModel
 from .clip import Transformer
 
@@ -104,6 +110,7 @@ class MITHHashLayer(nn.Module):
                  res_mlp_layers=2):
         super().__init__()
         self.k_bits = k_bits
+        self.dropout = float(dropout)
         self.gcl_i = self.gcl_t = GlobalConceptLearning(k_bits, clip_embed_dim, dropout, activation, res_mlp_layers)
         self.lct_i = LocalConceptTransforming(clip_embed_dim, k_bits, transformer_layers, dropout, top_k_label)
         self.lct_t = LocalConceptTransforming(clip_embed_dim, k_bits, transformer_layers, dropout, top_k_label)
@@ -156,8 +163,144 @@ class MITHHashLayer(nn.Module):
     def encode_img(self, img_cls, img_tokens):
         return self._encode(self.gcl_i, self.lct_i, img_cls, img_tokens, None)
 
+    def _encode_train(self, gcl, lct, proj, cls, tokens_lnd, mask, who):
+        if self.dropout > 0:
+            raise NotImplementedError("%s: dropout = %g; the training head is built for dropout 0 (configs/MITH/config.yaml), there is "
+                                      "no mask replay" % (who, self.dropout))
+        if not (cls.is_cuda and tokens_lnd.is_cuda):
+            raise RuntimeError("%s needs CUDA/HIP tensors (got %s, %s); there is no CPU fallback" % (who, cls.device, tokens_lnd.device))
+        if cls.dim() != 2 or tokens_lnd.dim() != 3 or tokens_lnd.shape[1:] != cls.shape:
+            raise ValueError("%s: cls %s and tokens %s (LND) do not fit" % (who, tuple(cls.shape), tuple(tokens_lnd.shape)))
+        tokens = tokens_lnd.permute(1, 0, 2)                       # LND view of a [B,L,D] buffer -> back to [B,L,D]
+        params = head_params(gcl, lct, proj)
+        m = _clip._kpm_u8(mask, tokens.device)
+        if torch.is_grad_enabled() and (cls.requires_grad or tokens.requires_grad or any(p.requires_grad for p in params)):
+            return _MITHHeadTrain.apply(gcl, lct, m, cls, tokens, *params)
+        return _head_forward(gcl, lct, m, cls, tokens, params, keep_record=False)[0]
+
+    def encode_img_train(self, img_cls, img_tokens):
+        """encode_img of the reference in training mode (models/MITH/hash/hash.py:231-238) behind torch.autograd: img_cls [B, D],
+        img_tokens [L, B, D] (the LND view the towers return) -> (res_img_cls [B, D], img_cls_hash [B, K], tokens_hash_i [B, K],
+        trans_tokens_i [K, B, D]), fp32 CUDA tensors with a graph.  Gradients go to exactly the parameters with requires_grad (gcl_i
+        is gcl_t: its .grad is autograd's sum over both modalities) and to the two inputs if they require grad.  Under no_grad, or
+        with nothing to differentiate, it is the same forward and no record is kept.  B == 1 returns [1, K]: the reference's
+        torch.squeeze (:84) collapses that shape to [K], which is not imitated."""
+        return self._encode_train(self.gcl_i, self.lct_i, self.img_concept_proj, img_cls, img_tokens, None, "encode_img_train")
+
+    def encode_txt_train(self, txt_eos, txt_tokens, key_padding_mask):
+        """encode_txt in training mode (:240-247), as encode_img_train; key_padding_mask [B, L] (True = the token is ignored) or None"""
+        return self._encode_train(self.gcl_t, self.lct_t, self.txt_concept_proj, txt_eos, txt_tokens, key_padding_mask, "encode_txt_train")
+
     def encode_txt(self, txt_eos, txt_tokens, key_padding_mask):
         return self._encode(self.gcl_t, self.lct_t, txt_eos, txt_tokens, key_padding_mask)
+
+
+# ---- the head behind torch.autograd (DESIGN 3.14) ------------------------------------------------------------------------------------
+# (field of xmh_mith_mlp_grads in include/xmh.h, attribute path on a ResidualMLPs with the layer index), in the struct's field order
+MLP = (("ln_w", "lns.%d.weight"), ("ln_b", "lns.%d.bias"), ("fc1_w", "mlps.%d.0.weight"), ("fc1_b", "mlps.%d.0.bias"),
+       ("fc2_w", "mlps.%d.3.weight"), ("fc2_b", "mlps.%d.3.bias"))
+
+
+def head_params(gcl, lct, proj):
+    """parameter list of one modality: six per residual MLP (MLP's order), the concept embedding, twelve per transformer block
+    (clip_train.BLOCK), the K hash weights [1, D], the K hash biases [1], the concept projection's weight and bias"""
+    layers = gcl.mlp.num_layers if isinstance(gcl.mlp, ResidualMLPs) else 0
+    mlps = [gcl.mlp.get_parameter(path % i) for i in range(layers) for _, path in MLP]
+    fcs = list(lct.hashing.fc_list)
+    return mlps + [gcl.common_concept_embedding.weight] + _ct.block_params(lct.transformer) + [fc.weight for fc in fcs] + [fc.bias for fc in fcs] + \
+        [proj.weight, proj.bias]
+
+
+def _split(params, R, layers, K):
+    """head_params' list -> (mlps, concept, blocks, hash weights, hash biases, proj weight, proj bias)"""
+    a, b = len(MLP) * R, len(MLP) * R + 1 + len(_ct.BLOCK) * layers
+    return params[:a], params[a], params[a + 1:b], params[b:b + K], params[b + K:b + 2 * K], params[b + 2 * K], params[b + 2 * K + 1]
+
+
+def _head_forward(gcl, lct, mask, cls, tokens, params, keep_record=True):
+    """xmh_mith_train_forward on fp32 copies of cls [B, D] and tokens [B, L, D] -> ((res_cls, cls_hash, tokens_hash, trans_tokens),
+    what backward needs or None)"""
+    cls_c, tok = ops._f32c(cls.detach()).contiguous(), ops._f32c(tokens.detach()).contiguous()
+    B, L, D = tok.shape
+    K, tr = lct.hashing.k, lct.transformer
+    R, layers = (gcl.mlp.num_layers if isinstance(gcl.mlp, ResidualMLPs) else 0), len(tr.resblocks)
+    _ct._check_params(params, "MITH's training head")
+    pm, concept, pb, hw, hb, proj_w, proj_b = _split(params, R, layers, K)
+    lin = lambda w, b: _lib.Linear(w.data_ptr(), None, None, _clip._addr(b), w.shape[0], w.shape[1])      # noqa: E731
+    mlps = (_lib.MithMlp * max(R, 1))()
+    for i in range(R):
+        p = dict(zip((name for name, _ in MLP), pm[len(MLP) * i:len(MLP) * (i + 1)]))
+        mlps[i] = _lib.MithMlp(p["ln_w"].data_ptr(), p["ln_b"].data_ptr(), float(gcl.mlp.lns[i].eps), lin(p["fc1_w"], p["fc1_b"]), lin(p["fc2_w"], p["fc2_b"]))
+    blocks = _ct._exact_blocks(pb)
+    w, b = torch.cat([t.detach() for t in hw], 0), torch.cat([t.detach() for t in hb], 0)      # the K one-row layers stacked
+    pe = ops._f32c(lct.position.pe.detach()).reshape(-1, D)[:K].contiguous()
+    desc = _lib.MithTrain(_lib.MithHead(D, K, lct.lta.top_k, R, layers, tr.heads, mlps, lin(concept, None), pe.data_ptr(), blocks, w.data_ptr(),
+                                        b.data_ptr()), lin(proj_w, proj_b))
+    dev = tok.device
+    nbytes = lib.xmh_mith_train_ws_bytes(B, L, D, K, R)
+    sbytes = lib.xmh_mith_train_saved_bytes(B, L, D, K, R, layers) if keep_record else 0
+    ws = _clip._workspace(nbytes, dev)
+    buf = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=dev) if keep_record else None
+    outs = (torch.empty(B, D, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.float32, device=dev),
+            torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(K, B, D, dtype=torch.float32, device=dev))
+    check(lib.xmh_mith_train_forward(ctypes.byref(desc), ptr(cls_c), ptr(tok), ptr(mask), B, L, *(ptr(t) for t in outs), ptr(buf), sbytes, ptr(ws),
+                                     nbytes, current_stream()), "xmh_mith_train_forward")
+    if not keep_record:
+        return outs, None
+    return outs, (desc, [mlps, blocks, w, b, pe], cls_c, buf, (B, L, D, K, R, layers), nbytes)
+
+
+def saved_attention(buf, geom):
+    """the LTA attention A [B, K, L] inside the record xmh_mith_train_forward keeps, for tests and diagnostics.  C++ states the layout
+    (kept_layout, csrc/xmh_mith_grad.hip; Python cannot include it): the block record, per residual MLP x | ln | fc_pre | fc_act,
+    cls_hash, tokens_hash, A, z, p -- every piece rounded up to 256 bytes."""
+    B, L, D, K, R, layers = geom
+    al = lambda n: (4 * n + 255) // 256 * 256      # noqa: E731
+    off = al(layers * 16 * B * K * D) + R * (2 * al(B * D) + 2 * al(4 * B * D)) + 2 * al(B * K)
+    return buf[off // 4:off // 4 + B * K * L].view(B, K, L)
+
+
+class _MITHHeadTrain(torch.autograd.Function):
+    """forward = xmh_mith_train_forward, backward = xmh_mith_train_backward over the forward's descriptor: one modality of the head"""
+
+    @staticmethod
+    def forward(ctx, gcl, lct, mask, cls, tokens, *params):
+        outs, (ctx.desc, ctx.keep, cls_c, buf, ctx.geom, ctx.nbytes) = _head_forward(gcl, lct, mask, cls, tokens, params)
+        ctx.meta = ((cls.shape, cls.dtype), (tokens.shape, tokens.dtype))
+        ctx.set_materialize_grads(False)                # an output the loss does not use hands backward None, not a tensor of zeros
+        ctx.save_for_backward(cls_c, buf, *params)      # saved parameters: autograd notices an in-place change before backward
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernels are not themselves differentiable
+    def backward(ctx, *ups):
+        cls_c, buf, *params = ctx.saved_tensors         # first: this is where that in-place change raises
+        B, L, D, K, R, layers = ctx.geom
+        need = ctx.needs_input_grad
+        pneed = need[5:]
+        pm, _, pb, hw, hb, _, _ = _split(list(range(len(params))), R, layers, K)      # index ranges of the groups
+        stacked = set(hw) | set(hb)
+        gp = [torch.empty_like(p) if n and i not in stacked else None for i, (p, n) in enumerate(zip(params, pneed))]
+        dev = cls_c.device
+        d_hw = torch.empty(K, D, dtype=torch.float32, device=dev) if any(pneed[i] for i in hw) else None
+        d_hb = torch.empty(K, dtype=torch.float32, device=dev) if any(pneed[i] for i in hb) else None
+        d_cls = torch.empty(B, D, dtype=torch.float32, device=dev) if need[3] else None
+        d_tok = torch.empty(B, L, D, dtype=torch.float32, device=dev) if need[4] else None
+        mg = (_lib.MithMlpGrads * max(R, 1))()
+        for i in range(R):
+            mg[i] = _lib.MithMlpGrads(*[_clip._addr(gp[j]) for j in pm[len(MLP) * i:len(MLP) * (i + 1)]])
+        bg = _ct.block_grads([gp[j] for j in pb])
+        grads = _lib.MithGrads(mg, _clip._addr(gp[len(pm)]), bg, _clip._addr(d_hw), _clip._addr(d_hb), _clip._addr(gp[-2]), _clip._addr(gp[-1]),
+                               _clip._addr(d_cls), _clip._addr(d_tok))
+        gg = [None if g is None else _ct._upstream(g) for g in ups]
+        ws = _clip._workspace(ctx.nbytes, dev)
+        check(lib.xmh_mith_train_backward(ctypes.byref(ctx.desc), ptr(cls_c), B, L, *(ptr(g) for g in gg), ptr(buf), buf.numel() * 4,
+                                          ctypes.byref(grads), 0, ptr(ws), ctx.nbytes, current_stream()), "xmh_mith_train_backward")
+        for k, (i, j) in enumerate(zip(hw, hb)):          # the stacked rows back to the K one-row layers
+            gp[i] = d_hw[k:k + 1] if pneed[i] else None
+            gp[j] = d_hb[k:k + 1] if pneed[j] else None
+        (cs, cd), (ts, td) = ctx.meta
+        return (None, None, None, None if d_cls is None else d_cls.to(cd).reshape(cs), None if d_tok is None else d_tok.to(td).reshape(ts), *gp)
 
 
 class _MITHLoss(torch.autograd.Function):
@@ -238,8 +381,19 @@ class MITH(BaseModel):
         return self.hash.encode_txt(txt_eos, txt_tokens, new_mask)
 
     def forward_train(self, image, text):
-        raise NotImplementedError("MITH's head has no backward (localized token aggregation, bitwise hashing), and it reads the towers' "
-                                  "token outputs (return_patches=True), which the differentiable towers do not return")
+        raise NotImplementedError("MITH's head has its backward (forward_train_heads trains it over a frozen backbone), but it reads the "
+                                  "towers' token outputs (return_patches=True), which the differentiable towers do not return")
+
+    def forward_train_heads(self, image, text, key_padding_mask=None):
+        """The eight tensors of ``forward``, in its order, with a graph through the hash head only: the towers run as in
+        encode_image / encode_text under no_grad (a frozen backbone), the head through encode_img_train / encode_txt_train.  With
+        MITHTrainer.compute_loss and build_optimizer this trains MITH's heads."""
+        if key_padding_mask is not None and key_padding_mask.device != text.device:
+            key_padding_mask = key_padding_mask.to(text.device)
+        with torch.no_grad():
+            cls_token, seq_tokens, _ = self.backbone.encode_image(image)
+            txt_eos, txt_tokens, _, new_mask = self.backbone.encode_text(text, key_padding_mask=key_padding_mask, masked_rows="zero")
+        return (*self.hash.encode_img_train(cls_token, seq_tokens), *self.hash.encode_txt_train(txt_eos, txt_tokens, new_mask))
 
     def forward(self, image, text, key_padding_mask=None, labels=None, indexs=None, return_loss=False):
         img, txt = towers.run_both(lambda: self.encode_image(image), lambda: self.encode_text(text, key_padding_mask=key_padding_mask))

@@ -172,8 +172,9 @@ class MITHTrainer(_MethodTrainer):
         return all_loss
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("MITHTrainer.train_epoch: MITH's head (localized token aggregation, bitwise hashing) has no backward, "
-                                  "and the differentiable towers do not return the token outputs it reads")
+        raise NotImplementedError("MITHTrainer.train_epoch: MITH's head trains over a frozen backbone (MITH.forward_train_heads with "
+                                  "compute_loss and build_optimizer); an epoch that also trains the towers needs their token outputs "
+                                  "(return_patches=True) to be differentiable, which they are not")
 
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)

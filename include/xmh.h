@@ -727,6 +727,56 @@ int xmh_head_dsph_backward(const float* w, const float* x, const float* y, const
                            size_t workspace_bytes, xmh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MITH hash head in TRAINING mode: one modality of HashLayer.encode_img / encode_txt (models/MITH/hash/hash.py:231-247) as a
+ * forward that keeps what backward reads and a backward to every head parameter of that modality and to the two inputs
+ * (DESIGN 3.14).  Exact fp32 over the parameters in place: only the w_f32 / bias members of the descriptors are read.
+ *   cls path (carries gradient): y = ResidualMLPs(cls), cls_hash = tanh(y Wc^T), res_cls = y / max(|y|, 1e-12);
+ *   token scores: the same GlobalConceptLearning on the B L token rows -> scores [B, L, K], detached as in the reference (:235);
+ *   LTA: xmh_lta_aggregate's selection and softmax, M = A X + pe, the attention A [B, K, L] kept;
+ *   z = the transformer blocks over M [B, K, D] (sequence length K, no mask), through xmh_clip_blocks_forward_saved;
+ *   tokens_hash[b,k] = tanh(w_k . z[b,k,:] + b_k); trans_tokens = normalize(z Wp^T + bp), written [K, B, D].
+ * cls_hash and tokens_hash carry the bits of xmh_head_mith in precision 2.  B = 1 returns [1, K] (the reference's torch.squeeze
+ * collapses that shape).  saved == NULL (forward): no record is kept, same outputs.
+ * Gradients have the parameters' shapes; the K one-row hash layers are stacked, hash_w [K, D], hash_b [K].  NULL = frozen, and a
+ * product nothing asked-for depends on is not launched.  Each of the four upstream gradients may be NULL (that output was not used):
+ * what only that path feeds is then written as exact zeros.  accumulate != 0: parameter gradients are added to what their buffers
+ * hold; d_cls [B, D] and d_tokens [B, L, D] are always written.  d_tokens flows through A X only (the scores carry no gradient,
+ * pos_enc is a buffer): rows of masked tokens, and the contribution of a concept no token of the sample scores positively for, are
+ * exactly zero.
+ * Limits: K <= 128, D % 4 == 0, D <= 1024, D / heads == 64, res_layers <= 4, LayerNorm eps 1e-5, B L and B K <= 2^21, L (K + 2) <=
+ * 40960 (XMH_ENOTSUP beyond); -12 for a short saved buffer or workspace, -22 for null or misfitting arguments, all reported
+ * without a GPU.  No host synchronisation, no allocation, no float atomics; every sum has one fixed order (two calls on equal
+ * inputs agree to the bit).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_mith_train {
+    xmh_mith_head head;                                /* as for xmh_head_mith */
+    xmh_linear proj;                                   /* img_concept_proj / txt_concept_proj [D, D] with bias */
+} xmh_mith_train;
+typedef struct xmh_mith_mlp_grads {
+    float *ln_w, *ln_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+} xmh_mith_mlp_grads;
+typedef struct xmh_mith_grads {
+    const xmh_mith_mlp_grads* mlps;                    /* host array [res_layers] (may be NULL when res_layers == 0) */
+    float* concept;                                    /* [K, D] */
+    const xmh_clip_block_grads* blocks;                /* host array [layers] (may be NULL when layers == 0) */
+    float *hash_w, *hash_b;                            /* [K, D], [K] */
+    float *proj_w, *proj_b;                            /* [D, D], [D] */
+    float *d_cls, *d_tokens;                           /* [B, D], [B, L, D] */
+} xmh_mith_grads;
+/* 256-byte aligned device memory; 0 for a shape outside the limits.  One workspace size serves the forward and the backward. */
+size_t xmh_mith_train_saved_bytes(int64_t B, int L, int width, int k_bits, int res_layers, int layers);
+size_t xmh_mith_train_ws_bytes(int64_t B, int L, int width, int k_bits, int res_layers);
+/* cls [B, D], tokens [B, L, D] (contiguous), token_mask [B, L] bytes (non-zero = ignore) or NULL
+ * -> res_cls [B, D], cls_hash [B, K], tokens_hash [B, K], trans_tokens [K, B, D] (all required) */
+int xmh_mith_train_forward(const xmh_mith_train* h, const float* cls, const float* tokens, const uint8_t* token_mask, int64_t B, int L,
+                           float* res_cls, float* cls_hash, float* tokens_hash, float* trans_tokens, void* saved, size_t saved_bytes,
+                           void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* upstream gradients g_* in the outputs' shapes (each may be NULL) -> the gradients named in grads; cls and saved are the forward's */
+int xmh_mith_train_backward(const xmh_mith_train* h, const float* cls, int64_t B, int L, const float* g_res_cls, const float* g_cls_hash,
+                            const float* g_tokens_hash, const float* g_trans_tokens, const void* saved, size_t saved_bytes,
+                            const xmh_mith_grads* grads, int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BertAdam (models/common/optimizer.py:50-167): one optimiser step over any number of fp32 tensors in two launches.
  * Per tensor: norm = |g|_2; coef = min(1, max_grad_norm / (norm + 1e-6)) when max_grad_norm > 0, else 1; g' = g coef;
  * m = m b1 + (1 - b1) g'; v = v b2 + (1 - b2) g' g'; u = m / (sqrt(v) + e), plus weight_decay p when weight_decay > 0; p -= lr u.
