@@ -152,6 +152,8 @@ PROTOTYPES = {
     "xmh_attention_f32": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp]),
     "xmh_attention_split16": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp]),
     "xmh_image_preprocess_u8": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "xmh_image_preprocess_train_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_image_preprocess_train_u8": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, sz, vp, vp, vp]),
     "xmh_im2col_patch": (i32, [vp, i64, i32, i32, i32, vp, vp]),
     "xmh_vit_assemble": (i32, [vp, vp, vp, vp, vp, C.c_float, vp, i64, i32, i32, vp]),
     "xmh_text_embed": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),

@@ -1,11 +1,14 @@
-"""The reference's evaluation input pipeline behind its own names: ``build_dataloader`` (dataset/builder.py:34-104:
+"""The reference's input pipeline behind its own names: ``build_dataloader`` (dataset/builder.py:34-104:
 .mat / .npy / .txt parsing and the query / train / retrieval split) and ``transformer_dataset``
 (dataset/transformer_dataset.py:11-107: the sample tuple ``(image, caption, key_padding_mask, label, index)``).
 
-What differs, deliberately: ``_load_image`` only DECODES (PIL -> RGB bytes ``[H, W, 3] uint8``); the resize + ToTensor +
-Normalize of the reference's eval transform runs on the GPU, Pillow-exact, in ``BaseTrainer.encode_streams`` through
-``xmh.dataset.preprocess.GpuEvalTransform``.  Photos of different sizes cannot be stacked, so ``collate`` keeps the images
-of a batch as a list.  The training transform (random crop / flip) belongs to training, which is out of scope."""
+What differs, deliberately: ``_load_image`` only DECODES (PIL -> RGB bytes ``[H, W, 3] uint8``), for the training split as
+for the other two.  The transforms of the reference run on the GPU, Pillow-exact, in the runner: the evaluation one (resize +
+ToTensor + Normalize) in ``BaseTrainer.encode_streams`` through ``xmh.dataset.preprocess.GpuEvalTransform``, the training one
+(RandomHorizontalFlip + RandomResizedCrop + ToTensor + Normalize, reference :34-40) in ``train_epoch`` through
+``GpuTrainTransform``, which draws the crop boxes on the host.  ``is_train`` is the flag the runner reads to tell the two
+apart; the dataset itself does nothing with it.  Photos of different sizes cannot be stacked, so ``collate`` keeps the images
+of a batch as a list."""
 from __future__ import annotations
 
 import random
@@ -23,8 +26,6 @@ SPECIAL_TOKEN = {"CLS_TOKEN": "<|startoftext|>", "SEP_TOKEN": "<|endoftext|>", "
 class TransformerDataset(Dataset):
     def __init__(self, captions, indexs, labels, is_train=True, imageResolution=224, tokenizer=None, maxWords=32, npy=False, **kwags):
         super().__init__()
-        if is_train:
-            raise NotImplementedError("the training transform (RandomResizedCrop / flip) is outside the encode-and-retrieve path")
         self.captions, self.indexs, self.labels = captions, indexs, labels
         self.is_train, self.npy = is_train, npy
         self.imageResolution, self.maxWords, self.tokenizer = imageResolution, maxWords, tokenizer
@@ -95,9 +96,10 @@ def _first_key(mat: dict, keys, what: str):
 
 
 def build_dataloader(captionFile: str, indexFile: str, labelFile: str, imageResolution=224, query_num=5000, train_num=10000,
-                     dataset_cls=None, **kwargs):
-    """reference dataset/builder.py:34-104 -> (train, query, retrieval) datasets; the training split is returned as None
-    (training is out of scope), the other two are evaluation datasets."""
+                     dataset_cls=None, train_split=False, **kwargs):
+    """reference dataset/builder.py:34-104 -> (train, query, retrieval) datasets.  ``train_split=True`` builds the training
+    dataset over ``split_data``'s train slice with ``is_train=True``, as the reference does (:97-98); the default returns None
+    in its place (an evaluation-only run never decodes it).  The other two are evaluation datasets."""
     import scipy.io as scio
     assert dataset_cls is not None, "'dataset_cls' must be provided!"
     dataset = registry.get_dataset_class(dataset_cls)
@@ -118,5 +120,6 @@ def build_dataloader(captionFile: str, indexFile: str, labelFile: str, imageReso
     labels = _first_key(scio.loadmat(labelFile), ("category", "LAll", "labels"), "label")
     s_idx, s_cap, s_lab = split_data(captions, indexs, labels, query_num=query_num, train_num=train_num)
     kwargs.pop("img_train_transform", None)
-    mk = lambda i: dataset(captions=s_cap[i], indexs=s_idx[i], labels=s_lab[i], imageResolution=imageResolution, is_train=False, npy=npy, **kwargs)   # noqa: E731
-    return None, mk(0), mk(2)
+    mk = lambda i, train=False: dataset(captions=s_cap[i], indexs=s_idx[i], labels=s_lab[i], imageResolution=imageResolution,   # noqa: E731
+                                        is_train=train, npy=npy, **kwargs)
+    return (mk(1, True) if train_split else None), mk(0), mk(2)

@@ -175,11 +175,11 @@ class BaseTrainer:
                     indexFile=os.path.join(path, dataname, cfg.get("img_file", "index.mat")),
                     labelFile=os.path.join(path, dataname, cfg.get("label_file", "caption.mat")),
                     imageResolution=cfg.get("image_resolution", 224), maxWords=cfg.get("max_word", 32), query_num=query_num,
-                    train_num=train_num, dataset_cls=arch, tokenizer=tok())
+                    train_num=train_num, dataset_cls=arch, tokenizer=tok(), train_split=bool(self.is_train))
         self.build_loader(train_data, query_data, retrieval_data, batch_size, num_workers, pin_memory, shuffle)
 
     def build_loader(self, train_data, query_data, retrieval_data, batch_size, num_workers, pin_memory, shuffle, drop_last=False):
-        self.train_labels = train_data.get_all_label() if train_data is not None else None     # no training split on this path
+        self.train_labels = train_data.get_all_label() if train_data is not None else None     # no training split when is_train is false
         self.query_labels = query_data.get_all_label()
         self.retrieval_labels = retrieval_data.get_all_label()
         self.retrieval_num = len(self.retrieval_labels)
@@ -263,6 +263,15 @@ class BaseTrainer:
             from ..dataset.preprocess import GpuEvalTransform
             t = GpuEvalTransform(int(getattr(self, "image_resolution", 224) or 224))
             self.__dict__["_gpu_eval_transform"] = t
+        return t
+
+    def _train_image_transform(self):
+        """the training transform of raw photos (dataset/transformer_dataset.py:34-40), its draws seeded by run.seed"""
+        t = self.__dict__.get("_gpu_train_transform")
+        if t is None:
+            from ..dataset.preprocess import GpuTrainTransform
+            t = GpuTrainTransform(int(getattr(self, "image_resolution", 224) or 224), seed=self.cfg.run.get("seed", 1814))
+            self.__dict__["_gpu_train_transform"] = t
         return t
 
     def generate_hashes(self, image, text, key_padding_mask=None) -> dict:

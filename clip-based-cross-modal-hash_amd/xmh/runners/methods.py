@@ -44,7 +44,8 @@ class _MethodTrainer(BaseTrainer):
 
 def _train_epoch(trainer, epoch: int):
     """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser).  The
-    optimiser is built on the first call, when the instance has none yet."""
+    optimiser is built on the first call, when the instance has none yet.  A batch of raw photos (uint8, stacked or a list of
+    different sizes: the file layout's training split) goes through the GPU training transform; a float batch goes on as it is."""
     if trainer.distributed:
         raise NotImplementedError("train_epoch with distributed=True: there is no all-reduce of the gradients")
     if getattr(trainer, "optimizer", None) is None:
@@ -59,7 +60,10 @@ def _train_epoch(trainer, epoch: int):
     for image, text, key_padding_mask, label, index in trainer.train_loader:
         trainer.global_step += 1
         times += 1
-        image = image.to(trainer.device, non_blocking=True)
+        if isinstance(image, (list, tuple)) or image.dtype == torch.uint8:      # raw RGB bytes: the training transform runs on the GPU
+            image = trainer._train_image_transform()(image)                     # (dataset/transformer_dataset.py:34-40, Pillow-exact)
+        else:
+            image = image.to(trainer.device, non_blocking=True)
         text = text.to(trainer.device, non_blocking=True)
         index = index.numpy()
         hash_img, hash_text = trainer.model.forward_train(image, text)

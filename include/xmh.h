@@ -329,6 +329,33 @@ int xmh_image_preprocess_u8(const uint8_t* images, int64_t B, int H, int W, int 
                             const int32_t* bounds_h, const int32_t* kk_h, int ksize_h,
                             const float* mean3_host, const float* std3_host, uint8_t* tmp, uint8_t* resized_u8,
                             float* out_chw, xmh_stream_t stream);
+/* Training image transform (reference dataset/transformer_dataset.py:34-40: torchvision RandomHorizontalFlip +
+ * RandomResizedCrop(r) + ToTensor + Normalize on a PIL image) for a RAGGED batch, every image with its own crop and flip:
+ *     Image.fromarray(a) [.transpose(FLIP_LEFT_RIGHT)] .crop((left, top, left + w, top + h)) .resize((r, r), Image.BILINEAR)
+ * to the bit (Pillow's two-pass 8-bit resample; its coefficient tables are computed on the device, per image and axis, in
+ * double), then ((u8 / 255) - mean) / std.  The random draw is the caller's.
+ * One descriptor per image, a DEVICE array: `offset` = byte offset of the image's first uploaded pixel in `pixels` (rows of
+ * W * 3 bytes, RGB); H, W = rows and columns uploaded; top, left, h, w = the crop box in the coordinates of the FLIPPED image
+ * (the reference flips, then crops): crop column x reads source column flip ? W - 1 - (left + x) : left + x. */
+typedef struct {
+    int64_t offset;
+    int32_t H, W;
+    int32_t top, left, h, w;
+    int32_t flip;
+    int32_t reserved;
+} xmh_crop_desc;
+/* bytes of workspace for a batch of B crops of at most max_h x max_w pixels resized to r x r (coefficient tables of
+ * 2 * ceil(max(max_x / r, 1)) + 1 taps per output pixel and the horizontal pass's uint8 rows); 0 for shapes the call refuses. */
+size_t xmh_image_preprocess_train_ws_bytes(int64_t B, int max_h, int max_w, int r);
+/* pixels: `pixel_bytes` bytes on the device; desc [B] on the device; max_h / max_w: upper bounds of desc[].h / desc[].w (they size
+ * the launches and the tables: three launches whatever B is, no host synchronisation, no allocation).  Outputs (either may be
+ * NULL): resized_u8 [B][r][r][3]; out_chw [B][3][r][r] f32 with mean3_host / std3_host three HOST floats each.  The host can only
+ * check what it sees (B, r, the bounds, null pointers, the workspace size: XMH_EINVAL / XMH_ENOMEM); the kernels clamp every
+ * source coordinate into its image and every byte index into `pixels`, so a bad descriptor never reads outside the buffer.
+ * B == 0 is XMH_OK. */
+int xmh_image_preprocess_train_u8(const uint8_t* pixels, int64_t pixel_bytes, const xmh_crop_desc* desc, int64_t B, int max_h,
+                                  int max_w, int r, const float* mean3_host, const float* std3_host, void* workspace,
+                                  size_t workspace_bytes, uint8_t* resized_u8, float* out_chw, xmh_stream_t stream);
 /* VisionTransformer.conv1 input gather (models/CLIP/model.py:219,235): image [B,C,res,res] -> cols [B*G*G, C*P*P] */
 int xmh_im2col_patch(const float* image, int64_t B, int channels, int resolution, int patch, float* cols,
                      xmh_stream_t stream);
