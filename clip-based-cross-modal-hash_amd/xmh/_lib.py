@@ -181,6 +181,14 @@ PROTOTYPES = {
     "xmh_text_train_ws_bytes": (sz, [i64, i32, i32, i32]),
     "xmh_text_train_forward": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, vp, vp, vp, sz, vp, sz, vp]),
     "xmh_text_backward": (i32, [C.POINTER(TextWeights), vp, vp, vp, i64, i32, vp, sz, vp, C.POINTER(TextGrads), i32, vp, sz, vp]),
+    "xmh_vit_train_tokens_saved_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_vit_train_tokens_ws_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "xmh_vit_train_forward_tokens": (i32, [C.POINTER(VitWeights), vp, i64, vp, vp, vp, sz, vp, sz, vp]),
+    "xmh_vit_backward_tokens": (i32, [C.POINTER(VitWeights), vp, i64, vp, sz, vp, vp, C.POINTER(VitGrads), i32, vp, sz, vp]),
+    "xmh_text_train_tokens_saved_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_text_train_tokens_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_text_train_forward_tokens": (i32, [C.POINTER(TextWeights), vp, vp, i64, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "xmh_text_backward_tokens": (i32, [C.POINTER(TextWeights), vp, vp, vp, i64, i32, vp, sz, vp, vp, C.POINTER(TextGrads), i32, vp, sz, vp]),
     "xmh_head_workspace_bytes": (sz, [i64, i32, i32]),
     "xmh_head_dcmht": (i32, [C.POINTER(DcmhtHead), vp, i64, i32, vp, vp, vp, vp, sz, vp]),
     "xmh_head_dsph": (i32, [C.POINTER(Linear), vp, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

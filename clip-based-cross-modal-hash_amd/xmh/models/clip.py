@@ -298,28 +298,55 @@ class CLIP(nn.Module):
         no_grad, or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
         vis = self.visual
         if self.return_patches or vis.return_patches:
-            raise NotImplementedError("encode_image_train returns the cls feature only: the patch tokens (return_patches=True) feed MITH's "
-                                      "head, whose backward (MITHHashLayer.encode_img_train) returns their gradient, but the tower's "
-                                      "training forward does not return them")
+            raise NotImplementedError("encode_image_train returns the cls feature only: on a return_patches=True model the patch tokens "
+                                      "feed MITH's head, and encode_image_train_tokens returns them with the cls feature")
+        from . import clip_train
+        return clip_train.encode_image(vis, self._train_image(image))
+
+    def _train_image(self, image):
+        """the image batch as the training towers take it, checked"""
+        vis = self.visual
         image = ops._f32c(image).contiguous()
         if image.dim() != 4 or image.shape[1:] != (3, vis.input_resolution, vis.input_resolution):
             raise ValueError("image batch is %s, the tower takes [B, 3, %d, %d]" % (tuple(image.shape), vis.input_resolution, vis.input_resolution))
+        return image
+
+    def _train_ids(self, text):
+        if not text.is_cuda:
+            raise RuntimeError("xmh ops need CUDA/HIP tensors (got %s); there is no CPU fallback" % text.device)
+        ids = text.to(torch.int64).contiguous()
+        if ids.dim() != 2 or ids.shape[1] > self.context_length:
+            raise ValueError("token batch is %s, the tower takes [B, L] with L <= %d" % (tuple(ids.shape), self.context_length))
+        return ids
+
+    def encode_image_train_tokens(self, image):
+        """encode_image of a return_patches=True model in exact fp32 behind torch.autograd -> (cls [B, E], tokens
+        [L - 1, B, E]): ln_post and proj run on every row (reference models/CLIP/model.py:257-267), the backward is ONE call of
+        xmh_vit_backward_tokens and takes the gradient of either output or of both.  `return_patches` is not looked at.  Under no_grad,
+        or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
         from . import clip_train
-        return clip_train.encode_image(vis, image)
+        cls, tokens = clip_train.encode_image_tokens(self.visual, self._train_image(image))
+        return cls, tokens.permute(1, 0, 2)
+
+    def encode_text_train_tokens(self, text, key_padding_mask=None):
+        """encode_text of a return_patches=True model in exact fp32 behind torch.autograd -> (eos [B, E], tokens [L, B, E], new_mask):
+        ln_final and text_projection on every row (reference :386-395), every row computed (no row packing in training); new_mask is
+        encode_text's, key_padding_mask | (text == 49407), or None without a mask."""
+        ids = self._train_ids(text)
+        kpm = _kpm_u8(key_padding_mask, ids.device)
+        from . import clip_train
+        eos, tokens = clip_train.encode_text_tokens(self, ids, kpm)
+        new_mask = None if kpm is None else (kpm.bool() | (ids == self.vocab_size - 1))
+        return eos, tokens.permute(1, 0, 2), new_mask
 
     def encode_text_train(self, text, key_padding_mask=None):
         """encode_text in exact fp32 behind torch.autograd, on the padded rows: gradients go to exactly the parameters of the text
         tower with requires_grad (logit_scale is no input: its .grad stays None, as in the reference, where nothing reads it).  Under
         no_grad, or with nothing to differentiate, this is the plain exact-mode forward and no record is kept."""
         if self.return_patches:
-            raise NotImplementedError("encode_text_train returns the EOS feature only: the token outputs (return_patches=True) feed MITH's "
-                                      "head, whose backward (MITHHashLayer.encode_txt_train) returns their gradient, but the tower's "
-                                      "training forward does not return them")
-        if not text.is_cuda:
-            raise RuntimeError("xmh ops need CUDA/HIP tensors (got %s); there is no CPU fallback" % text.device)
-        ids = text.to(torch.int64).contiguous()
-        if ids.dim() != 2 or ids.shape[1] > self.context_length:
-            raise ValueError("token batch is %s, the tower takes [B, L] with L <= %d" % (tuple(ids.shape), self.context_length))
+            raise NotImplementedError("encode_text_train returns the EOS feature only: on a return_patches=True model the token outputs "
+                                      "feed MITH's head, and encode_text_train_tokens returns them with the EOS feature")
+        ids = self._train_ids(text)
         from . import clip_train
         return clip_train.encode_text(self, ids, _kpm_u8(key_padding_mask, ids.device))
 

@@ -1,6 +1,7 @@
 """The CLIP block stack and the two towers behind torch.autograd: exact fp32 over the parameters in place, one C call
 for the forward that keeps the record and one for the whole backward.  ``Transformer.run_train``, ``CLIP.encode_image_train`` and
-``CLIP.encode_text_train`` (models/clip.py) check their arguments and call ``run_blocks`` / ``encode_image`` / ``encode_text`` here.
+``CLIP.encode_text_train`` (models/clip.py) check their arguments and call ``run_blocks`` / ``encode_image`` / ``encode_text`` here;
+``CLIP.encode_image_train_tokens`` / ``encode_text_train_tokens`` call ``encode_image_tokens`` / ``encode_text_tokens``.
 
 Which parameter is which is stated once, in the three tables below: (field of the grads struct in include/xmh.h, attribute path on
 the module), in the struct's field order.  The parameter list handed to ``Function.apply``, the weights descriptor, the gradient
@@ -230,6 +231,114 @@ class _TextTrain(torch.autograd.Function):
         check(lib.xmh_text_backward(ctypes.byref(ctx.desc), ptr(ids), ptr(ctx.kpm), ptr(eos), B, L, ptr(buf), buf.numel() * 4, ptr(gg),
                                     ctypes.byref(grads), 0, ptr(ws), ctx.nbytes, current_stream()), "xmh_text_backward")
         return (None, None, None, *gp)
+
+
+# ---- the two towers with their token outputs --------------------------------------------------------------------------
+def _grad_or_none(g):
+    return None if g is None else _upstream(g)
+
+
+class _VitTokensTrain(torch.autograd.Function):
+    """forward = xmh_vit_train_forward_tokens -> (cls [B, E], tokens [B, L - 1, E]), backward = xmh_vit_backward_tokens over the forward's
+    descriptor; an output the loss does not use hands None to backward, which the C entry takes as zeros"""
+
+    @staticmethod
+    def forward(ctx, vis, image, *params):
+        B, L = image.shape[0], vis.positional_embedding.shape[0]
+        ctx.set_materialize_grads(False)
+        ctx.keep = []
+        ctx.desc = d = vit_desc(vis, params, ctx.keep)
+        sbytes = lib.xmh_vit_train_tokens_saved_bytes(B, L, d.width, d.layers)
+        ctx.nbytes = lib.xmh_vit_train_tokens_ws_bytes(B, L, d.width, d.conv1.k, d.out_dim)
+        buf, ws, cls = _train_buffers(d, sbytes, ctx.nbytes, B, image.device)
+        tokens = torch.empty(B, L - 1, d.out_dim, dtype=torch.float32, device=image.device)
+        check(lib.xmh_vit_train_forward_tokens(ctypes.byref(d), ptr(image), B, ptr(cls), ptr(tokens), ptr(buf), sbytes, ptr(ws), ctx.nbytes,
+                                               current_stream()), "xmh_vit_train_forward_tokens")
+        ctx.save_for_backward(image, buf, *params)      # saved parameters: autograd notices an in-place change before backward
+        return cls, tokens
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls, g_tokens):
+        image, buf, *params = ctx.saved_tensors         # first: this is where that in-place change raises
+        if g_cls is None and g_tokens is None:
+            return (None, None, *(None for _ in params))
+        gp = _grad_buffers(params, ctx.needs_input_grad[2:])
+        grads = tower_grads(_lib.VitGrads, VIT, gp)
+        gc, gt = _grad_or_none(g_cls), _grad_or_none(g_tokens)
+        ws = _workspace(ctx.nbytes, image.device)
+        check(lib.xmh_vit_backward_tokens(ctypes.byref(ctx.desc), ptr(image), image.shape[0], ptr(buf), buf.numel() * 4, ptr(gc), ptr(gt),
+                                          ctypes.byref(grads), 0, ptr(ws), ctx.nbytes, current_stream()), "xmh_vit_backward_tokens")
+        return (None, None, *gp)
+
+
+class _TextTokensTrain(torch.autograd.Function):
+    """forward = xmh_text_train_forward_tokens -> (eos [B, E], tokens [B, L, E]), backward = xmh_text_backward_tokens"""
+
+    @staticmethod
+    def forward(ctx, clip, ids, kpm, *params):
+        B, L = ids.shape
+        ctx.set_materialize_grads(False)
+        ctx.keep = []
+        ctx.desc = d = text_desc(clip, params, ctx.keep)
+        sbytes = lib.xmh_text_train_tokens_saved_bytes(B, L, d.width, d.layers)
+        ctx.nbytes = lib.xmh_text_train_tokens_ws_bytes(B, L, d.width, d.out_dim)
+        buf, ws, out = _train_buffers(d, sbytes, ctx.nbytes, B, ids.device)
+        tokens = torch.empty(B, L, d.out_dim, dtype=torch.float32, device=ids.device)
+        eos = torch.empty(B, dtype=torch.int32, device=ids.device)
+        check(lib.xmh_text_train_forward_tokens(ctypes.byref(d), ptr(ids), ptr(kpm), B, L, ptr(out), ptr(tokens), ptr(eos), ptr(buf), sbytes, ptr(ws),
+                                                ctx.nbytes, current_stream()), "xmh_text_train_forward_tokens")
+        ctx.kpm = kpm
+        ctx.save_for_backward(ids, eos, buf, *params)
+        return out, tokens
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_eos, g_tokens):
+        ids, eos, buf, *params = ctx.saved_tensors
+        if g_eos is None and g_tokens is None:
+            return (None, None, None, *(None for _ in params))
+        B, L = ids.shape
+        gp = _grad_buffers(params, ctx.needs_input_grad[3:])
+        grads = tower_grads(_lib.TextGrads, TEXT, gp)
+        ge, gt = _grad_or_none(g_eos), _grad_or_none(g_tokens)
+        ws = _workspace(ctx.nbytes, ids.device)
+        check(lib.xmh_text_backward_tokens(ctypes.byref(ctx.desc), ptr(ids), ptr(ctx.kpm), ptr(eos), B, L, ptr(buf), buf.numel() * 4, ptr(ge), ptr(gt),
+                                           ctypes.byref(grads), 0, ptr(ws), ctx.nbytes, current_stream()), "xmh_text_backward_tokens")
+        return (None, None, None, *gp)
+
+
+def encode_image_tokens(vis, image):
+    """-> (cls [B, E], tokens [B, L - 1, E]), dense"""
+    params = tower_params(vis, VIT)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return _VitTokensTrain.apply(vis, image, *params)
+    keep = []
+    d = vit_desc(vis, params, keep)
+    B, L = image.shape[0], vis.positional_embedding.shape[0]
+    nbytes = lib.xmh_clip_workspace_bytes(B, L, d.width, d.conv1.k, d.out_dim, ops.PREC_F32X)
+    ws = _workspace(nbytes, image.device)
+    y = torch.empty(B, L, d.out_dim, dtype=torch.float32, device=image.device)
+    check(lib.xmh_vit_b32_forward(ctypes.byref(d), ptr(image), B, ops.PREC_F32X, None, ptr(y), ptr(ws), nbytes, current_stream()),
+          "xmh_vit_b32_forward")
+    return y[:, 0, :], y[:, 1:, :]
+
+
+def encode_text_tokens(clip, ids, kpm):
+    """-> (eos [B, E], tokens [B, L, E]); every row is computed"""
+    params = tower_params(clip, TEXT)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return _TextTokensTrain.apply(clip, ids, kpm, *params)
+    keep = []
+    d = text_desc(clip, params, keep)
+    B, L = ids.shape
+    nbytes = lib.xmh_clip_workspace_bytes(B, L, d.width, 0, d.out_dim, ops.PREC_F32X)
+    ws = _workspace(nbytes, ids.device)
+    eos = torch.empty(B, d.out_dim, dtype=torch.float32, device=ids.device)
+    y = torch.empty(B, L, d.out_dim, dtype=torch.float32, device=ids.device)
+    check(lib.xmh_text_forward(ctypes.byref(d), ptr(ids), ptr(kpm), B, L, ops.PREC_F32X, ptr(eos), ptr(y), None, ptr(ws), nbytes, current_stream()),
+          "xmh_text_forward")
+    return eos, y
 
 
 def encode_image(vis, image):

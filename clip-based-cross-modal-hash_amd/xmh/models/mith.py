@@ -381,8 +381,20 @@ class MITH(BaseModel):
         return self.hash.encode_txt(txt_eos, txt_tokens, new_mask)
 
     def forward_train(self, image, text):
-        raise NotImplementedError("MITH's head has its backward (forward_train_heads trains it over a frozen backbone), but it reads the "
-                                  "towers' token outputs (return_patches=True), which the differentiable towers do not return")
+        raise NotImplementedError("MITH.forward_train(image, text) has no key padding mask, which MITH's text path needs for the token "
+                                  "outputs its head reads: forward_train_towers(image, text, key_padding_mask) trains MITH end to end, "
+                                  "forward_train_heads its head over a frozen backbone")
+
+    def forward_train_towers(self, image, text, key_padding_mask=None):
+        """The eight tensors of ``forward``, in its order, with a graph through the hash head AND both towers: the towers
+        run through encode_image_train_tokens / encode_text_train_tokens -- exact fp32, every row, one stream -- and the head through
+        encode_img_train / encode_txt_train with the text tower's new_mask.  With MITHTrainer.compute_loss and build_optimizer this is
+        the reference's training step (runners/MITH/runner.py:98-123)."""
+        if key_padding_mask is not None and key_padding_mask.device != text.device:
+            key_padding_mask = key_padding_mask.to(text.device)
+        cls_token, seq_tokens = self.backbone.encode_image_train_tokens(image)
+        txt_eos, txt_tokens, new_mask = self.backbone.encode_text_train_tokens(text, key_padding_mask=key_padding_mask)
+        return (*self.hash.encode_img_train(cls_token, seq_tokens), *self.hash.encode_txt_train(txt_eos, txt_tokens, new_mask))
 
     def forward_train_heads(self, image, text, key_padding_mask=None):
         """The eight tensors of ``forward``, in its order, with a graph through the hash head only: the towers run as in

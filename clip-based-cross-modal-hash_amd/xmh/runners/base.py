@@ -208,12 +208,15 @@ class BaseTrainer:
         for epoch in range(self.epochs):
             self.train_epoch(epoch=epoch)
             self.valid(epoch, k=self.top_k)
+        self._log_finished()
+
+    def _log_finished(self):
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t}, mAP: {self.max_mapt2i}")
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("train_epoch is built for DCMHT and DSPH only (their losses, hash heads and both CLIP towers have a "
-                                  "backward, and build_optimizer gives the reference's BertAdam): the backward of MITH's and TwDH's "
-                                  "heads is still missing, and MITH needs the token outputs of the towers differentiable too")
+        raise NotImplementedError("train_epoch is built for DCMHT and DSPH (their losses, hash heads and both CLIP towers have a "
+                                  "backward, and build_optimizer gives the reference's BertAdam) and, as train_epoch_towers, for MITH; "
+                                  "the backward of TwDH's head is still missing")
 
     def compute_loss(self, *a, **k):
         raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")

@@ -42,10 +42,25 @@ class _MethodTrainer(BaseTrainer):
                    world_size=world_size, distributed=distributed, **extra)
 
 
-def _train_epoch(trainer, epoch: int):
-    """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser).  The
-    optimiser is built on the first call, when the instance has none yet.  A batch of raw photos (uint8, stacked or a list of
-    different sizes: the file layout's training split) goes through the GPU training transform; a float batch goes on as it is."""
+def _step_pair(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch of DCMHT / DSPH: the two codes of forward_train into the objective (the text tower takes no key padding mask)"""
+    hash_img, hash_text = trainer.model.forward_train(image, text)
+    return trainer.compute_loss(img_hash=hash_img, txt_hash=hash_text, label=label, index=index, epoch=epoch, times=times,
+                                global_step=trainer.global_step)
+
+
+def _step_mith(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch of MITH (runners/MITH/runner.py:109-115): the eight outputs of the head over both towers into the objective"""
+    out = trainer.model.forward_train_towers(image, text, key_padding_mask=key_padding_mask)
+    return trainer.compute_loss(*out, label=label, index=index, epoch=epoch, times=times, global_step=trainer.global_step)
+
+
+def _train_epoch(trainer, epoch: int, step=_step_pair):
+    """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser); with
+    step=_step_mith, runners/MITH/runner.py:98-123.  `step(trainer, image, text, key_padding_mask, label, index, epoch, times)`
+    returns the loss of one batch.  The optimiser is built on the first call, when the instance has none yet.  A batch of raw
+    photos (uint8, stacked or a list of different sizes: the file layout's training split) goes through the GPU training
+    transform; a float batch goes on as it is."""
     if trainer.distributed:
         raise NotImplementedError("train_epoch with distributed=True: there is no all-reduce of the gradients")
     if getattr(trainer, "optimizer", None) is None:
@@ -66,9 +81,7 @@ def _train_epoch(trainer, epoch: int):
             image = image.to(trainer.device, non_blocking=True)
         text = text.to(trainer.device, non_blocking=True)
         index = index.numpy()
-        hash_img, hash_text = trainer.model.forward_train(image, text)
-        loss = trainer.compute_loss(img_hash=hash_img, txt_hash=hash_text, label=label, index=index, epoch=epoch, times=times,
-                                    global_step=trainer.global_step)
+        loss = step(trainer, image, text, key_padding_mask, label, index, epoch, times)
         all_loss += loss.detach()
         trainer.optimizer.zero_grad()
         if optimizer_loss is not None:
@@ -176,9 +189,20 @@ class MITHTrainer(_MethodTrainer):
         return all_loss
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("MITHTrainer.train_epoch: MITH's head trains over a frozen backbone (MITH.forward_train_heads with "
-                                  "compute_loss and build_optimizer); an epoch that also trains the towers needs their token outputs "
-                                  "(return_patches=True) to be differentiable, which they are not")
+        raise NotImplementedError("MITHTrainer.train_epoch: the epoch that trains MITH's head and both towers, the reference's, is "
+                                  "train_epoch_towers (train() runs it); over a frozen backbone the head trains through "
+                                  "MITH.forward_train_heads with compute_loss and build_optimizer")
+
+    def train_epoch_towers(self, epoch: int):
+        """runners/MITH/runner.py:98-123: the backbone at backbone_lr and the head at lr, the text tower with the key padding mask"""
+        _train_epoch(self, epoch, step=_step_mith)
+
+    def train(self):
+        """runners/base.py:287-294 with this class's epoch"""
+        for epoch in range(self.epochs):
+            self.train_epoch_towers(epoch)
+            self.valid(epoch, k=self.top_k)
+        self._log_finished()
 
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)

@@ -535,6 +535,31 @@ int xmh_text_backward(const xmh_text_weights* w, const int64_t* ids, const uint8
                       int64_t B, int L, const void* saved, size_t saved_bytes, const float* g, const xmh_text_grads* grads,
                       int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
 
+/* The same towers with their TOKEN outputs (return_patches=True, models/CLIP/model.py:257-267 and :386-395): the last
+ * LayerNorm and the projection run on all B * L rows, as xmh_vit_b32_forward / xmh_text_forward run them for out_tokens in
+ * precision 2 (same bits), and the backward takes a gradient for the one row and for the tokens.  Descriptors, grads structs,
+ * limits, return codes and the conventions above are unchanged; `saved` holds all B * L rows entering the last LayerNorm instead
+ * of B, and the workspace the B * L rows of the back end (xmh_*_train_tokens_saved_bytes / _ws_bytes: not the sizes above).
+ *   image  out_cls [B, out_dim] (row 0) and out_tokens [B, L - 1, out_dim] (rows 1...), both dense and both required
+ *   text   out_eos [B, out_dim] (row eos_index[b]), out_tokens [B, L, out_dim] and eos_index [B], all required
+ *   backward  g_cls / g_eos [B, out_dim] and g_tokens (the shape of out_tokens); either may be NULL and counts as zeros, both NULL
+ *             is -22.  g_eos[b] is added onto row eos_index[b] (clamped to [0, L)), which also carries its row of g_tokens. */
+size_t xmh_vit_train_tokens_saved_bytes(int64_t B, int L, int width, int layers);
+size_t xmh_vit_train_tokens_ws_bytes(int64_t B, int L, int width, int conv_k, int out_dim);
+int xmh_vit_train_forward_tokens(const xmh_vit_weights* w, const float* image, int64_t B, float* out_cls, float* out_tokens, void* saved,
+                                 size_t saved_bytes, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+int xmh_vit_backward_tokens(const xmh_vit_weights* w, const float* image, int64_t B, const void* saved, size_t saved_bytes,
+                            const float* g_cls, const float* g_tokens, const xmh_vit_grads* grads, int accumulate, void* workspace,
+                            size_t workspace_bytes, xmh_stream_t stream);
+size_t xmh_text_train_tokens_saved_bytes(int64_t B, int L, int width, int layers);
+size_t xmh_text_train_tokens_ws_bytes(int64_t B, int L, int width, int out_dim);
+int xmh_text_train_forward_tokens(const xmh_text_weights* w, const int64_t* ids, const uint8_t* key_padding_mask, int64_t B, int L,
+                                  float* out_eos, float* out_tokens, int32_t* eos_index, void* saved, size_t saved_bytes,
+                                  void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+int xmh_text_backward_tokens(const xmh_text_weights* w, const int64_t* ids, const uint8_t* key_padding_mask, const int32_t* eos_index,
+                             int64_t B, int L, const void* saved, size_t saved_bytes, const float* g_eos, const float* g_tokens,
+                             const xmh_text_grads* grads, int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
 /* One modality of the DCMHT head in eval mode (models/DCMHT/hash/hash.py:15-82): MultiheadAttention over a length-1
  * sequence == out_proj(v_proj(x)) (softmax over one key is 1), BatchNorm1d with running statistics (image) or LayerNorm
  * (text), fc2 + relu, softmax over each (off, on) pair. */
