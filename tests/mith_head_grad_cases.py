@@ -223,6 +223,23 @@ def grad_name(key):
     return "g_" + key
 
 
+def e2e_key(name):
+    """parameter name under model.hash -> (group: gcl / i / t, the restatement's key, row of a stacked hash tensor or None)"""
+    p = name.split(".")
+    if p[0].startswith("gcl"):
+        if p[1] == "common_concept_embedding":
+            return "gcl", "concept", None
+        if p[2] == "lns":
+            return "gcl", "mlp%s.ln_%s" % (p[3], p[4][0]), None
+        return "gcl", "mlp%s.fc%d_%s" % (p[3], 1 if p[4] == "0" else 2, p[5][0]), None
+    if p[0].startswith("lct"):
+        g = p[0][-1]
+        if p[1] == "transformer":
+            return g, "blk." + ".".join(p[2:]), None
+        return g, "hash_w" if p[-1] == "weight" else "hash_b", int(p[3])
+    return p[0][0], "proj_w" if p[-1] == "weight" else "proj_b", None
+
+
 def run_restatement(sd, cls, tok, mask, ups, heads, top_k, dtype, keep=None, scores_out=None):
     """sum_i (output_i . up_i).sum().backward() over one modality of the head in `dtype` -> {tensor name: numpy array}: the four
     outputs, g_cls [B, D], g_tokens [L, B, D], g_<parameter> (g_mlp<i>_<field>, g_l<i>_<block field>), and "keep" [L, B, K] bool, the

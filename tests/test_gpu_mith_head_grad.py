@@ -473,23 +473,6 @@ def _e2e_trainer(out_dir):
     return t
 
 
-def _e2e_key(name):
-    """parameter name under model.hash -> (group: gcl / i / t, the restatement's key, row of a stacked hash tensor or None)"""
-    p = name.split(".")
-    if p[0].startswith("gcl"):
-        if p[1] == "common_concept_embedding":
-            return "gcl", "concept", None
-        if p[2] == "lns":
-            return "gcl", "mlp%s.ln_%s" % (p[3], p[4][0]), None
-        return "gcl", "mlp%s.fc%d_%s" % (p[3], 1 if p[4] == "0" else 2, p[5][0]), None
-    if p[0].startswith("lct"):
-        g = p[0][-1]
-        if p[1] == "transformer":
-            return g, "blk." + ".".join(p[2:]), None
-        return g, "hash_w" if p[-1] == "weight" else "hash_b", int(p[3])
-    return p[0][0], "proj_w" if p[-1] == "weight" else "proj_b", None
-
-
 def _e2e_trajectory(init, feats, keeps, Y0, sims, rows, weights, hyper, heads, top_k, dtype):
     """the heads' training steps restated in `dtype`: init {(group, key): array}, feats / keeps / sims / rows per step -> per step
     dict(loss, grad, p, m, v) of numpy arrays keyed like init"""
@@ -560,7 +543,7 @@ def test_three_bertadam_steps_of_the_heads_follow_the_float64_trajectory(tmp_pat
     named = {n[len("hash."):]: p for n, p in model.named_parameters() if n.startswith("hash.")}
     init = {}
     for n, p in named.items():
-        g, key, row = _e2e_key(n)
+        g, key, row = MC.e2e_key(n)
         if row is None:
             init[(g, key)] = p.detach().cpu().double().numpy()
         else:
@@ -598,7 +581,7 @@ def test_three_bertadam_steps_of_the_heads_follow_the_float64_trajectory(tmp_pat
         t.optimizer.step()
         rec = {"loss": float(loss.detach()), "grad": {}, "p": {}, "m": {}, "v": {}}
         for n, p in named.items():
-            g, key, row = _e2e_key(n)
+            g, key, row = MC.e2e_key(n)
             st = t.optimizer.state[p]
             for q, val in (("grad", pre[n]), ("p", p.detach()), ("m", st["next_m"]), ("v", st["next_v"])):
                 a = val.cpu().double().numpy()
