@@ -112,6 +112,11 @@ class MithGrads(C.Structure):                  # xmh_mith_grads
                [(n, vp) for n in ("hash_w", "hash_b", "proj_w", "proj_b", "d_cls", "d_tokens")]
 
 
+class TwdhStreams(C.Structure):                # xmh_twdh_streams
+    MAX = 8                                    # XMH_TWDH_MAX_STREAMS
+    _fields_ = [("n", i32), ("bit", i32 * 8), ("K", i32 * 8)]
+
+
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
 PROTOTYPES = {
     "xmh_version": (i32, []),
@@ -204,6 +209,12 @@ PROTOTYPES = {
     "xmh_quant_loss": (i32, [vp, i64, vp, vp]),
     "xmh_pair_similarity_loss_grad": (i32, [vp, vp, i64, i32, vp, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, i32, vp]),
     "xmh_quant_loss_grad": (i32, [vp, i64, C.c_float, vp, vp, i32, vp]),
+    "xmh_twdh_targets": (i32, [vp, i32, vp, vp, i64, i32, vp, vp]),
+    "xmh_twdh_loss_ws_bytes": (sz, [i64, i32]),
+    "xmh_twdh_loss": (i32, [C.POINTER(TwdhStreams), vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, vp, vp, sz, vp]),
+    "xmh_twdh_loss_grad": (i32, [C.POINTER(TwdhStreams), vp, vp, vp, i64, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "xmh_twdh_short_forward": (i32, [vp, vp, i64, i32, i32, vp, vp]),
+    "xmh_twdh_short_backward": (i32, [vp, vp, vp, i64, i32, i32, vp, i32, vp, sz, vp]),
     "xmh_hyp_loss_ws_bytes": (sz, [i64, i32, i32]),
     "xmh_hyp_loss": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, sz, vp, vp]),
     "xmh_hyp_loss_grad": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, i32, vp, sz, vp]),

@@ -215,8 +215,8 @@ class BaseTrainer:
 
     def train_epoch(self, epoch: int):
         raise NotImplementedError("train_epoch is built for DCMHT and DSPH (their losses, hash heads and both CLIP towers have a "
-                                  "backward, and build_optimizer gives the reference's BertAdam) and, as train_epoch_towers, for MITH; "
-                                  "the backward of TwDH's head is still missing")
+                                  "backward, and build_optimizer gives the reference's BertAdam), as train_epoch_towers for MITH and as "
+                                  "train_epoch_codes for TwDH")
 
     def compute_loss(self, *a, **k):
         raise NotImplementedError("training is outside the encode-and-retrieve path this package implements")

@@ -55,6 +55,13 @@ def _step_mith(trainer, image, text, key_padding_mask, label, index, epoch, time
     return trainer.compute_loss(*out, label=label, index=index, epoch=epoch, times=times, global_step=trainer.global_step)
 
 
+def _step_twdh(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch of TwDH (runners/TwDH/runner.py:129-130): the long code and the short codes of both modalities into the objective"""
+    img_long, img_short, txt_long, txt_short = trainer.model.forward_train_codes(image, text)
+    return trainer.compute_loss(long_img_hash=img_long, long_txt_hash=txt_long, short_img_hash=img_short, short_txt_hash=txt_short, label=label,
+                                index=index, epoch=epoch, times=times, global_step=trainer.global_step)
+
+
 def _train_epoch(trainer, epoch: int, step=_step_pair):
     """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser); with
     step=_step_mith, runners/MITH/runner.py:98-123.  `step(trainer, image, text, key_padding_mask, label, index, epoch, times)`
@@ -221,7 +228,30 @@ class TwDHTrainer(DCMHTTrainer):
         super().__init__(cfg, *a, **k)
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("TwDHTrainer.train_epoch: TwDH's head (the long code and its short-code transforms) has no backward")
+        raise NotImplementedError("TwDHTrainer.train_epoch: TwDH's head yields the long code and its short codes, four outputs where "
+                                  "the shared epoch expects a pair; the reference's epoch is train_epoch_codes (train() runs it)")
+
+    def train_epoch_codes(self, epoch: int):
+        """runners/TwDH/runner.py:116-137: one BertAdam over the backbone and the hash layer; the transforms and centres are constants"""
+        _train_epoch(self, epoch, step=_step_twdh)
+
+    def train(self):
+        """runners/base.py:287-294 with this class's epoch"""
+        for epoch in range(self.epochs):
+            self.train_epoch_codes(epoch)
+            self.valid(epoch, k=self.top_k)
+        self._log_finished()
+
+    def compute_loss(self, long_img_hash, long_txt_hash, short_img_hash, short_txt_hash, label=None, index=None, epoch=0, times=0,
+                     global_step=0, **kwags):
+        """runners/TwDH/runner.py:106-114: the objective of one batch (xmh_twdh.hip behind torch.autograd), differentiable with
+        respect to the long codes and every short code; the display line needs the training loop's loader and optimiser, which this
+        package does not build, and is skipped without them."""
+        all_loss, loss_dict = self.model.object_function(long_img_hash=long_img_hash, long_txt_hash=long_txt_hash, short_img_hash=short_img_hash,
+                                                         short_txt_hash=short_txt_hash, labels=label, indexs=index, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=long_img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
 
     def build_model(self, cfg_model, output_dim=16):
         super().build_model(cfg_model, output_dim=output_dim)

@@ -662,6 +662,51 @@ int xmh_quant_loss_grad(const float* code, int64_t n, float scale, const float* 
                         xmh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TwDH objective (models/TwDH/TwDH.py:125-230) and the backward of its short-code transforms.  A stream is one code
+ * length: stream 0 the long code, then every short length; stream s owns bits [bit[s], bit[s] + K[s]) of the K_tot target bits, the
+ * streams tiling [0, K_tot) in order.  Probabilities come per modality as long [B, 2 K[0]] and short [B, 2 (K_tot - K[0])] (the short
+ * streams side by side), one (off, on) pair per bit, fp32, 8-byte aligned.  B <= 4096, K_tot <= 4096, C <= 1024 (XMH_ENOTSUP beyond).
+ * No call synchronises with the host or allocates; every sum runs in one fixed order (two calls on equal inputs agree to the bit).
+ * ------------------------------------------------------------------------------------------- */
+#define XMH_TWDH_MAX_STREAMS 8
+typedef struct {
+    int32_t n;                               /* streams, the long one included */
+    int32_t bit[XMH_TWDH_MAX_STREAMS];       /* first target bit of the stream */
+    int32_t K[XMH_TWDH_MAX_STREAMS];         /* its code length */
+} xmh_twdh_streams;
+/* hash_convert(hash_center_multilables(labels, centre)) (:192-230) of all streams in one launch, as bits.  lab [B][ceil(C/32)] as
+ * xmh_pack_labels writes it; centres [C][K_tot] int8, every entry +1 or -1 (the caller checks); tie [K_tot] int8 +-1, the
+ * reference's random_center.  targets [B][ceil(K_tot/32)]: bit k = sign of the integer sum of the centres of the row's set labels,
+ * tie[k] > 0 where the sum is zero, 0 for a row without a label (the reference's NaN mean); padding bits 0. */
+int xmh_twdh_targets(const uint32_t* lab, int C, const int8_t* centres, const int8_t* tie, int64_t B, int K_tot, uint32_t* targets,
+                     xmh_stream_t stream);
+/* out (device, 1 + 6 * n doubles): out[0] the total (:160-164: (bce_img + bce_txt) / 2 + quan_alpha (q_img + q_txt) / 2 over
+ * the long stream plus low_rate times each of the two for every short stream); out[1 + (m * n + s) * 2 + t]: modality m (0 image,
+ * 1 text), stream s, t = 0 nn.BCELoss (mean over B * 2 K[s], each log clamped at -100) against the pair (1, 0) / (0, 1) of the
+ * target bit, t = 1 soft_argmax_hash_loss = 1 - mean((2 p - 1)^2); out[1 + 4 * n + 2 * s + t]: the mean of the two modalities' term t
+ * of stream s (the reference's short_nce_loss / short_quan_loss).  A modality whose pointers are NULL contributes zeros.  A NaN
+ * probability makes its terms and the total NaN.  Workspace: xmh_twdh_loss_ws_bytes(B, n) (XMH_ENOMEM when shorter).  2 launches. */
+size_t xmh_twdh_loss_ws_bytes(int64_t B, int n_streams);
+int xmh_twdh_loss(const xmh_twdh_streams* streams, const float* img_long, const float* img_short, const float* txt_long,
+                  const float* txt_short, const uint32_t* targets, int64_t B, double quan_alpha, double low_rate, double* out,
+                  void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* d total / d p of ONE modality, times upstream[0] (device float, NULL = 1): weight * ((p - t) / max(p (1 - p), 1e-12) / n), what
+ * autograd returns for nn.BCELoss, plus weight_q * (-4 (2 p - 1) / n), n = B * 2 K[s]; the weights 1/2 and quan_alpha / 2 for the
+ * long stream, low_rate / 2 for both terms of a short one.  d_long [B, 2 K[0]] / d_short are written; either may be NULL (then its
+ * streams are not computed: with low_rate == 0 the short gradient is an exact zero).  1 launch. */
+int xmh_twdh_loss_grad(const xmh_twdh_streams* streams, const float* p_long, const float* p_short, const uint32_t* targets, int64_t B,
+                       double quan_alpha, double low_rate, const float* upstream, float* d_long, float* d_short, xmh_stream_t stream);
+/* quantization(long_hash.matmul(trans)) (:66-85) of every short length at once: p_short [B, 2S] = pair_softmax(long_probs [B, 2L] .
+ * T_cat), the transforms concatenated along their columns; trans_t [2S, 2L] is T_cat TRANSPOSED (the nn.Linear layout
+ * xmh_gemm_nt_f32 takes).  Exact fp32 products.  2 launches (the product, the softmax in place). */
+int xmh_twdh_short_forward(const float* long_probs, const float* trans_t, int64_t B, int L2, int S2, float* p_short,
+                           xmh_stream_t stream);
+/* Its backward: g_z = p (g - (g0 p0 + g1 p1)) per pair, then g_long [B, 2L] = g_z . T_cat^T, added to g_long when accumulate != 0.
+ * trans [2L, 2S] is T_cat itself.  Workspace: 4 * B * 2S bytes (g_z), 8-byte aligned (XMH_ENOMEM when shorter).  2 launches. */
+int xmh_twdh_short_backward(const float* g_short, const float* p_short, const float* trans, int64_t B, int L2, int S2, float* g_long,
+                            int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * HyP loss of DSPH (models/DSPH/loss/HyP.py:18-70): forward, and its gradient with respect to the two code matrices and the
  * proxies (what loss.backward() of runners/DSPH/runner.py:123 hands to the hash heads and to the proxies' own optimiser).
  * x, y [B, K] fp32 (image / text codes), P [C, K] fp32 (proxies), lab [B][ceil(C/32)] as xmh_pack_labels writes it.
