@@ -236,6 +236,7 @@ int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p, const 
     int64_t nchunk = rounds * slots / nqt;
     if (S64 > 8) nchunk = nchunk * 8 / S64;       // long codes: S waves per tile already fill the slots; fewer chunks = smaller tables
     const bool mfma = fam != Family::kValu;
+    bool fill = false;                            // the chunk count is kept as computed instead of rounded to whole groups of 8
     if (mfma) {
         // k_scan_hist_b: 257 (513) bucket rows: three sets of blocks (COCO shape, sets 2 / 3 / 4 / 6: ternary 128 bit 0.93 / 0.78 / 0.83 / 0.83 ms, 256-bit
         // binary 0.85 / 0.73 / 0.75 / 0.76); ternary codes of at most 64 bits have 129 rows and smaller tables: six (0.65 -> 0.62 ms)
@@ -246,10 +247,18 @@ int make_plan(int64_t Q, int64_t R, int K, int ternary, xmh_scan_plan* p, const 
             int sets = K > 32 && K <= 64 ? 1 : 2;                   // k_scan_hist_r2 at 33..64 bits: one set (1 / 2 / 3: 0.178 / 0.187 / 0.199 ms)
             if (const char* e = xmh_experiment_env("XMH_R2_SETS")) sets = atoi(e) > 0 ? atoi(e) : sets;
             nchunk = (int64_t)sets * xmh::device_cu_count() * r2_geom(K).blocks_per_cu / (nqt * 64 / r2q);
+            // XMH_R2_FILL=1 (round 8, measured and NOT the default): k_scan_hist_r2 at 33..64 bits with a pair cache, one set, keeps the chunk
+            // count as computed -- every block slot filled.  All blocks of the launch are resident and run in lockstep, so pass 1 takes one
+            // block's time, and the rounding below leaves slots idle: Q 5000 x R 117 218 on 256 CUs is 20 query blocks, 512 slots, 25 chunks
+            // of 4736 (74 batches) against 24 of 4928 (77); the 25th chunk's blocks are dealt over the XCDs (xmh_scan_map.h).  24 / 25
+            // chunks: pass 1 0.1732-0.1740 / 0.1692-0.1706 ms in the ablation harness, the step 0.3346-0.3385 / 0.3328-0.3354 ms: 1.8 us
+            // at the medians, inside the spread of either (profiles/r08_scan_fill.txt).  Not worth moving every chunk boundary for: the
+            // per-chunk fp32 partial sums of pass 2 then add in another order than the ones every recorded result was computed with
+            if (const char* e = xmh_experiment_env("XMH_R2_FILL")) fill = atoi(e) != 0 && fam == Family::kR2 && sets == 1 && cache_shape && ap_r2_mode() != 1;
         }
     }
     if (nchunk < 1) nchunk = 1;
-    if (nchunk > 8) nchunk = (nchunk + 4) / 8 * 8;      // whole XCD groups: every XCD gets the same number of chunks
+    if (nchunk > 8 && !fill) nchunk = (nchunk + 4) / 8 * 8;      // whole XCD groups: every XCD gets the same number of chunks
     int64_t chunk = xmh::ceil_div(R, nchunk);
     if (chunk < kMinChunk) chunk = kMinChunk;
     if (chunk > kMaxChunk) chunk = kMaxChunk;
@@ -519,7 +528,7 @@ int check_common(const char* who, const ScanCall& c, const xmh_scan_plan& p) {
 
 ScanArgs make_args(const ScanCall& c, const xmh_scan_plan& p) {
     return ScanArgs{c.qbits, c.qzero, c.qlab, c.rbits, c.rzero, c.rlab, (int)c.Q, (int)c.R, c.K, (int)p.chunk, (int)p.nchunk, (int)p.nqtile, (int)p.qpad,
-                    (int)p.nbuckets, nullptr};
+                    (int)p.nbuckets, nullptr, (int)p.nqtile};
 }
 
 MfmaArgs r2_args(const ScanCall& c, const Launch& l, const xmh_scan_plan& p, int nqt) {
@@ -530,10 +539,13 @@ MfmaArgs r2_args(const ScanCall& c, const Launch& l, const xmh_scan_plan& p, int
 
 // ---- the geometry of a launch: what a Launch record means on a plan, for every launcher ------------------------------------------
 // nqt = query tiles of the kernel: a slotted wave owns 64 / S queries and a block NW waves; a block of k_scan_hist_r2 / r2w / ap_r2 owns NW x S
-// groups of 16, one of k_scan_hist_b kMfmaWaves groups.  Grid (map_block): 8 XCDs x tiles x chunk rounds.  LDS: the counters of a block -- u32 per
+// groups of 16, one of k_scan_hist_b kMfmaWaves groups.  nrun = the tiles the launch runs: pass 1 all of them (it writes the padded tiles' cache
+// entries and table columns: in a pass whose blocks run in lockstep they cost nothing), pass 2 only those that hold a query -- Q 5000 is padded
+// to 5120 for pass 1's blocks of 256, and seven of pass 2's 320 tiles of 16 would load their counters and stream their pair cache for sums
+// that nothing reads.  The layouts keep the padded count.  Grid (xmh_scan_map.h): tiles run x chunks.  LDS: the counters of a block -- u32 per
 // (bucket, query) in pass 1 and the packed pass 2, two words otherwise, 16 B-rounded per wave in the VALU kernels -- plus their gallery ring.
-struct Geom { unsigned grid, block; size_t lds; int nqt; };
-Geom launch_geom(const Launch& l, const xmh_scan_plan& p) {
+struct Geom { unsigned grid, block; size_t lds; int nqt, nrun; };
+Geom launch_geom(const Launch& l, const xmh_scan_plan& p, int64_t Q) {
     const size_t nb = (size_t)p.nbuckets;
     const bool ap = l.kern == Kern::kApS || l.kern == Kern::kApC || l.kern == Kern::kApR2;
     Geom g{0, 64u * (unsigned)l.NW, 0, 0};
@@ -547,7 +559,12 @@ Geom launch_geom(const Launch& l, const xmh_scan_plan& p) {
     } else {
         g.lds = (size_t)l.NW * l.S * nb * 16 * (ap ? 8 : 4); g.nqt = (int)(p.qpad / (l.NW * l.S * 16));
     }
-    g.grid = (unsigned)(8 * g.nqt * xmh::ceil_div(p.nchunk, 8));
+    g.nrun = g.nqt;
+    if (ap) {
+        static const bool all_tiles = xmh_experiment_env("XMH_AP_TILES") && atoi(xmh_experiment_env("XMH_AP_TILES")) == 0;      // A/B switch: 0 = the padded tiles too
+        if (!all_tiles) g.nrun = (int)xmh::ceil_div(Q, p.qpad / g.nqt);
+    }
+    g.grid = xmh::scan_grid_blocks(g.nrun, (int)p.nchunk);
     return g;
 }
 
@@ -581,7 +598,7 @@ struct ScanCtx {
     uint2* dpre() const { return at<uint2>(L.dpre); }
     uint32_t* cap_ws() const { return at<uint32_t>(L.cap); }
     float* ap_part() const { return at<float>(L.ap_part); }
-    ScanArgs args(const Geom& g, bool cached) const { ScanArgs as = a; as.nqt = g.nqt; as.pair_cache = cached ? pair_cache() : nullptr; return as; }
+    ScanArgs args(const Geom& g, bool cached) const { ScanArgs as = a; as.nqt = g.nqt; as.nrun = g.nrun; as.pair_cache = cached ? pair_cache() : nullptr; return as; }
     uint32_t* gate(int word = 0) const { return at<uint32_t>(L.gate) + word; }      // the control words: nrel_max, finalize ticket, size, kGateWrapped
     const uint32_t* gate_if(const Launch& l, unsigned g, int word) const { return (l.gate & g) ? gate(word) : nullptr; }
     uint4* pair_cache() const { return r.cache_bytes ? at<uint4>(L.pair_cache) : nullptr; }
@@ -601,7 +618,7 @@ void route_call(ScanCtx& x, Mode mode, const Overrides& ov) {
 // k_scan_hist_s: the cached instance where pass 1 leaves the pairs in the workspace (the shapes the pair cache is laid out for)
 int valu_hist(const ScanCtx& x) {
     const Launch& h = x.r.p1;
-    const Geom g = launch_geom(h, x.p);
+    const Geom g = launch_geom(h, x.p, x.c.Q);
     const ScanArgs as = x.args(g, h.cache);
     auto go = [&](auto kern, int S, int NW, bool cache) {
         xmh::ProfScope prof("scan_hist", x.st);
@@ -626,7 +643,7 @@ int valu_hist(const ScanCtx& x) {
 int mfma_hist(const ScanCtx& x) {
     const Launch& h = x.r.p1;
     const xmh_scan_plan& p = x.p;
-    const Geom g = launch_geom(h, p);
+    const Geom g = launch_geom(h, p, x.c.Q);
     uint32_t* chunk_hist = x.chunk_hist();
     uint4* cache = x.pair_cache();
     if (h.kern == Kern::kHistB) {
@@ -636,7 +653,7 @@ int mfma_hist(const ScanCtx& x) {
         return xmh::launch_scan_hist_bits(a, h.S, chunk_hist, cache, x.st);
     }
     // the launch in front of pass 1: clears the control words of the call and reads every chunk's packed words on the XCD that will scan it
-    hipLaunchKernelGGL(k_scan_touch, dim3((unsigned)(8 * kTouchPerChunk * xmh::ceil_div(p.nchunk, 8))), dim3(256), 0, x.st, x.c.rbits, x.c.rlab, x.c.R, h.W, h.LW,
+    hipLaunchKernelGGL(k_scan_touch, dim3(xmh::scan_grid_blocks(kTouchPerChunk, (int)p.nchunk)), dim3(256), 0, x.st, x.c.rbits, x.c.rlab, x.c.R, h.W, h.LW,
                        p.chunk, (int)p.nchunk, x.at<uint32_t>(x.L.tick), (int)((x.L.gate + 256 - x.L.tick) / 4));
     XMH_LAUNCH_CHECK("xmh_hamming_hist control words");
     const MfmaArgs a = r2_args(x.c, h, p, g.nqt);
@@ -754,7 +771,7 @@ int ap_offsets(const ScanCtx& x, const Pass2& o) {
 // rows of 16 queries leave few waves per CU -- 65..128-bit codes (129 rows: 16.5 KB per wave); 16 / 64 / 128 bit, 4 x 16 against 8 x 8:
 // 0.154 / 0.185, 0.171 / 0.182, 0.220 / 0.189 ms.  On the 12-bit entries of the two-byte layout: 8 x 8.
 int ap_launch_c(const ScanCtx& x, const Launch& l) {
-    const Geom g = launch_geom(l, x.p);
+    const Geom g = launch_geom(l, x.p, x.c.Q);
     const ScanArgs as = x.args(g, true);
     xmh::ProfScope prof("scan_ap", x.st);
     auto go = [&](auto kc, int S) {                                  // S: the slots of the instance (64 / S queries per wave)
@@ -768,8 +785,8 @@ int ap_launch_c(const ScanCtx& x, const Launch& l) {
 
 // k_scan_ap_r2: the pairs evaluated again on the MFMA from the packed words
 int ap_launch_r2(const ScanCtx& x, const Launch& l) {
-    const Geom g = launch_geom(l, x.p);
-    const MfmaArgs ma = r2_args(x.c, l, x.p, g.nqt);
+    const Geom g = launch_geom(l, x.p, x.c.Q);
+    const MfmaArgs ma = r2_args(x.c, l, x.p, g.nrun);
     xmh::ProfScope prof("scan_ap", x.st);
     auto go = [&](auto kern) {
         return start("xmh_hamming_ap", l, g, x.st, kern, kAp2Groups, kAp2Waves, l.cache, ma, x.below(), (const uint2*)x.dpre(), (const uint32_t*)x.cap_ws(), x.ap_part(),
@@ -781,7 +798,7 @@ int ap_launch_r2(const ScanCtx& x, const Launch& l) {
 
 // k_scan_ap_s: the cached kernel or the one that evaluates the pairs from the codes, in one of the two counter widths
 int ap_launch_s(const ScanCtx& x, const Launch& l) {
-    const Geom g = launch_geom(l, x.p);
+    const Geom g = launch_geom(l, x.p, x.c.Q);
     const ScanArgs as = x.args(g, l.cache);                           // cached: pass 1 of this call pair left the pairs in the workspace
     auto go = [&](auto kern, int S, int NW, bool cache, const uint32_t* run_if) {
         xmh::ProfScope prof(l.p32 ? "scan_ap32" : "scan_ap", x.st);

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * NW * NSH / NQT) void k_scan_hist_b(xmh::ScanBi
     constexpr int WH = TERN ? NMC : 2 * NMC;                        // words of one plane half of the operand (TERN: 2 WH words in all)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x [nb][16] u32 counters
     const int b = blockIdx.x;
-    const int qtile = (b >> 3) % a.nqt, chunk_id = (b & 7) + 8 * ((b >> 3) / a.nqt);        // as mfma_map_block (xmh_scan.hip)
+    const int qtile = (b >> 3) % a.nqt, chunk_id = (b & 7) + 8 * ((b >> 3) / a.nqt);        // chunk c on XCD c % 8, as the whole groups of xmh_scan_map.h; a last partial group leaves empty blocks
     if (chunk_id >= a.nchunk) return;
     constexpr int NWV = NW / NQT;                                    // waves of one share; each takes NQT query tiles
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) % NWV, share = (threadIdx.x >> 6) / NWV;

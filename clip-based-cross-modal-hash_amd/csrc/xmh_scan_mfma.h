@@ -4,6 +4,7 @@
 // hundred VALU kernels: two minutes); in the library only xmh_scan.hip includes it (and xmh_scan_kernels.h, the VALU kernels, behind it).
 #pragma once
 #include "xmh_common.h"
+#include "xmh_scan_map.h"
 #include <type_traits>
 
 namespace {
@@ -21,19 +22,14 @@ struct ScanArgs {
     const uint32_t* rzero;
     const uint32_t* rlab;
     int Q, R, K;
-    int chunk, nchunk, nqt, qpad, nb;
+    int chunk, nchunk, nqt, qpad, nb;    // nqt: the launch's query tiles in the LAYOUT (pair cache strides: the padded count)
     uint4* pair_cache;      // pass 1 -> pass 2: (distance << 1 | relevant) of every pair, see k_scan_hist_s; null = recompute
+    int nrun;               // the query tiles LAUNCHED: nqt, or in pass 2 only those that hold a query (launch_geom)
 };
 
-// blockIdx -> (chunk, query tile).  Block b runs on XCD b%8 (observed, speed only): pin chunk c to XCD c%8
-// and sweep the query tiles of one chunk back-to-back so the chunk stays in that XCD's L2.
+// blockIdx -> (chunk, query tile): xmh_scan_map.h, over the tiles the launch runs
 __device__ __forceinline__ bool map_block(const ScanArgs& a, int& chunk_id, int& qtile) {
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int t = b >> 3;
-    qtile = t % a.nqt;
-    chunk_id = xcd + 8 * (t / a.nqt);
-    return chunk_id < a.nchunk;
+    return xmh::scan_block_map((int)blockIdx.x, a.nrun, a.nchunk, chunk_id, qtile);
 }
 
 // ===================================================================================================
@@ -64,7 +60,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 struct MfmaArgs {
     const uint32_t* qbits;
     int Q, R, K, W;
-    int chunk, nchunk, nqt, nb, qpad;
+    int chunk, nchunk, nqt, nb, qpad;    // nqt: the query tiles launched (the layouts of these kernels go by qpad)
     // the packed words the operands are built from
     const uint32_t* rbits = nullptr;
     const uint32_t* rlab = nullptr;
@@ -72,12 +68,8 @@ struct MfmaArgs {
     int LW = 0;
 };
 
-__device__ __forceinline__ bool mfma_map_block(const MfmaArgs& a, int& chunk_id, int& qtile) {
-    const int b = blockIdx.x;
-    const int xcd = b & 7, t = b >> 3;
-    qtile = t % a.nqt;
-    chunk_id = xcd + 8 * (t / a.nqt);
-    return chunk_id < a.nchunk;
+__device__ __forceinline__ bool map_block(const MfmaArgs& a, int& chunk_id, int& qtile) {
+    return xmh::scan_block_map((int)blockIdx.x, a.nqt, a.nchunk, chunk_id, qtile);
 }
 
 // The label tile of 65-128 classes (three or four label words; NML = 2 in the kernels below): ONE v_mfma_f32_16x16x128_f8f6f4 with FP4
@@ -142,7 +134,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
     constexpr bool REGS = true;                                      // (the operands come from the packed words; kept as a name in the expressions below)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters
     int chunk_id, qtile;
-    if (!mfma_map_block(a, chunk_id, qtile)) return;                 // a.nqt counts tiles of NW * NQ * 16 queries here
+    if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts tiles of NW * NQ * 16 queries here
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ql = lane & 15, slot = lane >> 4;
     const int t16 = (qtile * NW + wave) * NQ;                        // first 16-query tile of this wave
@@ -477,6 +469,8 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
             cnt[h * ncell + dpad * 16 + ql] -= (uint32_t)npad << 16;
         }
     }
+    // (round 8: one bucket row of the wave's 64 consecutive queries per instruction -- 256 contiguous bytes instead of four pieces of 64,
+    // 20 KB apart -- measured no faster: pass 1 0.1706 / 0.1700 ms in the ablation harness, the step 0.3297 / 0.3299 ms; this form stays)
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
         uint32_t* __restrict__ out = chunk_hist + ((int64_t)chunk_id * a.nb) * a.qpad + (t16 + h) * 16;
@@ -486,7 +480,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
 
 // What is left of k_scan_expand2 for k_scan_hist_r2: the control words of the call are cleared, and the packed words of every chunk are
 // read once by blocks that land on the XCD whose k_scan_hist_r2 blocks will read them (block b runs on XCD b & 7, chunk c is scanned on XCD
-// c & 7: mfma_map_block).  k_scan_hist_r2 fetches its words one batch ahead, which covers an L2 hit but not a miss to HBM behind the
+// c & 7, a leftover chunk on all eight: xmh_scan_map.h).  k_scan_hist_r2 fetches its words one batch ahead, which covers an L2 hit but not a miss to HBM behind the
 // 600 MB the previous evaluation's pass 2 streamed through: without this launch pass 1 measured 0.204 ms instead of 0.184 (the image
 // kernel it replaces had been warming the caches by accident).
 constexpr int kTouchPerChunk = 8;
@@ -494,13 +488,16 @@ __global__ __launch_bounds__(256) void k_scan_touch(const uint32_t* __restrict__
                                                     int nchunk, uint32_t* __restrict__ ctl, int ctl_words) {
     if (blockIdx.x == 0)
         for (int e = threadIdx.x; e < ctl_words; e += 256) ctl[e] = 0u;
-    const int b = blockIdx.x;
-    const int c = (b & 7) + 8 * ((b >> 3) / kTouchPerChunk), sub = (b >> 3) % kTouchPerChunk;
-    if (c >= nchunk) return;
+    int c, sub;
+    if (!xmh::scan_block_map((int)blockIdx.x, kTouchPerChunk, nchunk, c, sub)) return;
+    // a chunk of a whole group of 8 is scanned on one XCD: its kTouchPerChunk blocks there share it.  A leftover chunk is scanned on all
+    // eight (xmh_scan_map.h) and its kTouchPerChunk blocks run on one XCD each: every one of them reads the whole chunk
+    const int parts = c < (nchunk & ~7) ? kTouchPerChunk : 1;
+    if (parts == 1) sub = 0;
     const int64_t lo = (int64_t)c * chunk, hi = lo + chunk < R ? lo + chunk : R;
     uint32_t acc = 0u;
     auto sweep = [&](const uint32_t* base, int64_t w0, int64_t w1) {      // one load per 128-byte line is enough
-        for (int64_t w = w0 + ((int64_t)sub * 256 + threadIdx.x) * 32; w < w1; w += (int64_t)kTouchPerChunk * 256 * 32) acc ^= base[w];
+        for (int64_t w = w0 + ((int64_t)sub * 256 + threadIdx.x) * 32; w < w1; w += (int64_t)parts * 256 * 32) acc ^= base[w];
     };
     sweep(rbits, lo * W, hi * W);
     sweep(rlab, lo * LW, hi * LW);
@@ -564,7 +561,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
     constexpr int NMC = 2, NMI = NMC + 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters (all << 16 | relevant)
     int chunk_id, qtile;
-    if (!mfma_map_block(a, chunk_id, qtile)) return;                 // a.nqt counts tiles of NW * NQ * 16 queries here
+    if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts tiles of NW * NQ * 16 queries here
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ql = lane & 15, slot = lane >> 4;
     const int t16 = (qtile * NW + wave) * NQ;
@@ -1141,7 +1138,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
     constexpr int NMI = 2;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] 64-bit float-bit counters
     int chunk_id, qtile;
-    if (!mfma_map_block(a, chunk_id, qtile)) return;                 // a.nqt counts tiles of NW * NQ * 16 queries here
+    if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts tiles of NW * NQ * 16 queries here
     if (items_total && (int64_t)*items_total > kFloatBitsMaxItems) return;      // sharded call: the integer-counter kernel takes it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ql = lane & 15, slot = lane >> 4;

@@ -54,8 +54,10 @@ int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 50;
     // the library's plan for this shape (xmh_scan_plan_make): 256-query blocks, two per CU, one set
     const int qpad = 5120, nqt256 = qpad / 256;
-    int nchunk = 256 * 2 / nqt256;
-    nchunk = (nchunk + 4) / 8 * 8;
+    // argv[2]: the chunk count to plan for (default: the library's, 25 rounded to whole groups of 8 = 24; 25 = every block slot filled,
+    // XMH_R2_FILL=1 of the planner); argv[3] = 1: pass 2 over the padded query tiles too
+    int nchunk = argc > 2 && atoi(argv[2]) > 0 ? atoi(argv[2]) : (256 * 2 / nqt256 + 4) / 8 * 8;
+    const bool all_tiles = argc > 3 && atoi(argv[3]) == 1;
     int chunk = (R + nchunk - 1) / nchunk;
     chunk = (chunk + 63) / 64 * 64;
     nchunk = (R + chunk - 1) / chunk;
@@ -88,13 +90,13 @@ int main(int argc, char** argv) {
     auto k1n = k_scan_hist_r2<2, NW, NQ, false>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k1n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    const dim3 grid1((unsigned)(8 * a.nqt * ((nchunk + 7) / 8)));
+    const dim3 grid1(xmh::scan_grid_blocks(a.nqt, nchunk));
     ScanArgs s{};
     s.qbits = dq; s.qlab = dql; s.rbits = dr; s.rlab = drl; s.Q = Q; s.R = R; s.K = K;
-    s.chunk = chunk; s.nchunk = nchunk; s.nqt = qpad / 16; s.qpad = qpad; s.nb = nb; s.pair_cache = cache;
+    s.chunk = chunk; s.nchunk = nchunk; s.nqt = qpad / 16; s.nrun = all_tiles ? s.nqt : (Q + 15) / 16; s.qpad = qpad; s.nb = nb; s.pair_cache = cache;
     const size_t lds2 = (size_t)nb * 16 * 8;
     auto k2 = k_scan_ap_c<false, 8, false>;
-    const dim3 grid2((unsigned)(8 * s.nqt * ((nchunk + 7) / 8)));
+    const dim3 grid2(xmh::scan_grid_blocks(s.nrun, nchunk));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     auto timed = [&](const char* what, auto launch) {
@@ -110,7 +112,7 @@ int main(int argc, char** argv) {
         printf("%-34s %8.4f ms   %6.1f cycles per 64 pairs and SIMD\n", what, t * 1e3, t * 2.4e9 * 1024 / ((double)Q * R / 64));
         return t;
     };
-    auto touch = [&]() { hipLaunchKernelGGL(k_scan_touch, dim3((unsigned)(8 * kTouchPerChunk * ((nchunk + 7) / 8))), dim3(256), 0, 0, dr, drl, (int64_t)R, W, LW, (int64_t)chunk, nchunk, ctl, 64); };
+    auto touch = [&]() { hipLaunchKernelGGL(k_scan_touch, dim3(xmh::scan_grid_blocks(kTouchPerChunk, nchunk)), dim3(256), 0, 0, dr, drl, (int64_t)R, W, LW, (int64_t)chunk, nchunk, ctl, 64); };
     {
         int occ = 0;
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k1, 64 * NW, lds1));
