@@ -514,3 +514,22 @@ extern "C" int xmh_head_dsph_backward(const float* w, const float* x, const floa
     XMH_LAUNCH_CHECK(who);
     return XMH_OK;
 }
+
+// A plain linear layer y = x w^T + b behind autograd (DNPH's class-prediction layers): d_w = d_y^T x with d_b from the same pass,
+// d_x = d_y w, the products of the heads above.  Nothing is staged, so no workspace is needed: the two arguments are there for the
+// calling convention of the other backward entries and a NULL / 0 pair is accepted; a non-NULL one must be 256-byte aligned.
+extern "C" int xmh_linear_backward(const float* w, const float* x, const float* d_y, int64_t B, int E, int N, float* d_w, float* d_b, float* d_x,
+                                   int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_linear_backward");
+    const char* who = "xmh_linear_backward";
+    if (int rc = check_shape(who, B, E, N)) return rc;
+    if (!w || !x || !d_y) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u)) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
+    if (!workspace && workspace_bytes) return xmh::fail(XMH_EINVAL, "%s: %zu workspace bytes at a null pointer", who, workspace_bytes);
+    if (!d_w && !d_b && !d_x) return XMH_OK;
+    hipStream_t st = xmh::as_stream(stream);
+    weight_grads(st, d_y, x, (int)B, N, E, d_w, d_b, accumulate);
+    if (d_x) launch_nn(st, d_y, w, (int)B, N, E, d_x);                             // an activation gradient: written, never added to
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}

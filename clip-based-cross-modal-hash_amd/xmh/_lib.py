@@ -243,6 +243,12 @@ PROTOTYPES = {
     "xmh_topk_describe": (i32, [i64, i64, i32, i32, C.c_char_p, sz]),
     "xmh_topk_record_bytes": (sz, [i64, i32]),
     "xmh_topk_merge_host": (i32, [vp, i32, i64, i32, vp, vp]),
+    "xmh_dnph_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_dnph_loss": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, sz, vp, vp]),
+    "xmh_dnph_loss_grad": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                 sz, vp]),
+    "xmh_assign_min_cost": (i32, [vp, i32, vp]),
+    "xmh_linear_backward": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

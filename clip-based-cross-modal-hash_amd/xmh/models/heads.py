@@ -305,3 +305,114 @@ class DSPHHashLayer(nn.Module):
 
     def forward(self, img_embeds, txt_embeds):
         return self.encode_img(img_embeds), self.encode_txt(txt_embeds)
+
+
+# ---- DNPH (reference models/DNPH/hash/hash.py) -----------------------------------------------------------------------------------------
+def _weights_init_kaiming(fc: nn.Linear) -> nn.Linear:
+    """the Linear branch of the reference's ``weights_init_kaiming`` (models/common/hash.py:5-10)"""
+    nn.init.kaiming_uniform_(fc.weight, mode="fan_out")
+    nn.init.constant_(fc.bias, 0.0)
+    return fc
+
+
+def _linear_f32(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """x w^T + b as the exact-fp32 product (xmh_gemm_nt_f32 at XMH_PREC_F32), whatever the package's precision mode is: the
+    class-prediction layers feed a cross-entropy, in training only -> (y, x as the kernel read it)"""
+    if x.dim() != 2:
+        raise ValueError("a DNPH prediction layer takes [B, E] embeddings, got %s" % (tuple(x.shape),))
+    x = ops._f32c(x.detach()).contiguous()
+    w, b = _param(weight), _param(bias)
+    B, E = x.shape
+    N = w.shape[0]
+    y = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    check(lib.xmh_gemm_nt_f32(ptr(x), E, ptr(w), E, ptr(b), None, 0, ptr(y), N, B, N, E, ops.ACT_NONE, ops.PREC_F32, current_stream()),
+          "xmh_gemm_nt_f32")
+    return y, x
+
+
+class _LinearTrain(torch.autograd.Function):
+    """forward = xmh_gemm_nt_f32 (exact fp32), backward = xmh_linear_backward"""
+
+    @staticmethod
+    def forward(ctx, data, weight, bias):
+        y, x = _linear_f32(data, weight, bias)
+        ctx.meta, ctx.version = (data.shape, data.dtype), weight._version
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernels are not themselves differentiable: fail loudly on double backward
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        w = _param(weight)
+        if weight._version != ctx.version:
+            raise RuntimeError("fc.weight of a DNPH prediction layer was modified in place between forward and backward")
+        B, E = x.shape
+        N = w.shape[0]
+        need = ctx.needs_input_grad
+        gx = torch.empty_like(x) if need[0] else None
+        gw = torch.empty_like(w) if need[1] else None
+        gb = torch.empty(N, dtype=torch.float32, device=x.device) if need[2] else None
+        up = g.detach().float().contiguous()
+        check(lib.xmh_linear_backward(ptr(w), ptr(x), ptr(up), B, E, N, ptr(gw), ptr(gb), ptr(gx), 0, None, 0, current_stream()),
+              "xmh_linear_backward")
+        if gx is not None:
+            gx = gx.reshape(ctx.meta[0]).to(ctx.meta[1])
+        return gx, gw, gb
+
+
+class DNPHLinearHash(DSPHLinearHash):
+    """reference LinearHash of DNPH (:9-19): DSPH's Linear / Dropout(0.2) / tanh head, ``fc`` initialised by weights_init_kaiming"""
+
+    def __init__(self, inputDim=512, outputDim=64):
+        super().__init__(inputDim, outputDim)
+        _weights_init_kaiming(self.fc)
+
+
+class DNPHPreLayer(nn.Module):
+    """reference Pre_Layer (:22-30): the class-prediction layer, ``fc`` [nb_class, inputdim].  With a graph to build (a parameter or
+    the input requires grad, grad mode on) the forward goes through ``_LinearTrain``; otherwise it is the same product with nothing
+    kept.  There is no dropout or normalisation: .train() / .eval() compute the same numbers."""
+
+    def __init__(self, inputdim=512, nb_class=80):
+        super().__init__()
+        self.fc = _weights_init_kaiming(nn.Linear(inputdim, nb_class))
+
+    def forward(self, data):
+        if torch.is_grad_enabled() and (data.requires_grad or self.fc.weight.requires_grad or self.fc.bias.requires_grad):
+            return _LinearTrain.apply(data, self.fc.weight, self.fc.bias)
+        return _linear_f32(data, self.fc.weight, self.fc.bias)[0]
+
+
+class DNPHHashLayer(nn.Module):
+    """reference HashLayer of DNPH (:32-67) under its attribute names, so that a reference checkpoint loads strictly: two outputs per
+    modality, the code (``image_hash`` / ``text_hash``) and the class logits (``image_pre`` / ``text_pre``).  The reference's model
+    never hands ``num_classes`` on, so the prediction layers have 80 outputs whatever ``numclass`` is."""
+
+    def __init__(self, inputDim=512, outputDim=64, num_classes=80):
+        super().__init__()
+        self.image_hash = DNPHLinearHash(inputDim=inputDim, outputDim=outputDim)
+        self.text_hash = DNPHLinearHash(inputDim=inputDim, outputDim=outputDim)
+        self.image_pre = DNPHPreLayer(inputdim=inputDim, nb_class=num_classes)
+        self.text_pre = DNPHPreLayer(inputdim=inputDim, nb_class=num_classes)
+
+    @staticmethod
+    def _encode(hash_mod, pre_mod, embeds, keep):
+        code = hash_mod._train(embeds, keep) if hash_mod.training and keep is not _DRAW else hash_mod(embeds)
+        return code, pre_mod(embeds)
+
+    def encode_img(self, embeds, keep=_DRAW):
+        """-> (hash, pre); `keep` replays a stored dropout mask in train mode (uint8 [B, K], or None for no dropout)"""
+        return self._encode(self.image_hash, self.image_pre, embeds, keep)
+
+    def encode_txt(self, embeds, keep=_DRAW):
+        return self._encode(self.text_hash, self.text_pre, embeds, keep)
+
+    def quantization(self, code):
+        """reference :53-54, tanh_hash; called by nothing, in the reference or here (the heads apply their own tanh)"""
+        return torch.tanh(code)
+
+    def forward(self, img_embeds, txt_embeds):
+        img_hash, img_pre = self.encode_img(img_embeds)
+        txt_hash, txt_pre = self.encode_txt(txt_embeds)
+        return img_hash, txt_hash, img_pre, txt_pre

@@ -336,3 +336,53 @@ class TwDHTrainer(DCMHTTrainer):
                                  f"MAP(i->i): {mAPi2i}, MAX MAP(i->t): {self.max_short[name]['i2t']}, epoch: {self.best_epoch_short[name]['i2t']}, "
                                  f"MAX MAP(t->i): {self.max_short[name]['t2i']}, epoch: {self.best_epoch_short[name]['t2i']}")
         return {name: maps for name, (maps, _) in results.items()}
+
+
+def _step_dnph(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch of DNPH (runners/DNPH/runner.py:126-127): the code and the class logits of both modalities into the objective"""
+    img_hash, txt_hash, img_pre, txt_pre = trainer.model.forward_train(image, text)
+    return trainer.compute_loss(img_hash=img_hash, txt_hash=txt_hash, img_pre=img_pre, txt_pre=txt_pre, label=label, index=index, epoch=epoch,
+                                times=times, global_step=trainer.global_step)
+
+
+@registry.register_runner("DNPHTrainer")
+class DNPHTrainer(_MethodTrainer):
+    """runners/DNPH/runner.py: the model's encoders return (code, class logits); evaluation quantises the code by its sign."""
+
+    hash_scale = 1                                              # runners/DNPH/runner.py:41
+    loss_type = "l1"                                            # runners/DNPH/runner.py:30-34: only named in the display line
+
+    def __init__(self, cfg, *a, **k):
+        self.hash_func = cfg.model.get("hash_func", "tanh")
+        assert self.hash_func == "tanh", "DNPH must adopt the 'tanh' hash technique."
+        super().__init__(cfg, *a, **k)
+
+    def build_optimizer(self, cfg_optimizer=None, parameters=None):
+        """runners/DNPH/runner.py:86-92: BertAdam as in the base class, and a stock SGD over the loss's proxies at the rate of the
+        config's ``loss`` sub-section -> (optimizer, optimizer_loss, None)"""
+        optimizer, lr_schedu = super().build_optimizer(cfg_optimizer=cfg_optimizer, parameters=parameters)
+        loss = (cfg_optimizer.get("loss") if cfg_optimizer is not None else None) or {}
+        optimizer_loss = torch.optim.SGD(params=self.model.loss.parameters(), lr=loss.get("lr", 0.0001))
+        self.logger.info("Building optimizer!")
+        return optimizer, optimizer_loss, lr_schedu
+
+    def train_epoch(self, epoch: int):
+        """runners/DNPH/runner.py:113-136: the four outputs of the head over both towers into the objective; the proxies' SGD steps
+        beside BertAdam"""
+        _train_epoch(self, epoch, step=_step_dnph)
+
+    def compute_loss(self, img_hash=None, txt_hash=None, img_pre=None, txt_pre=None, label=None, index=None, epoch=0, times=0, global_step=0,
+                     **kwags):
+        """runners/DNPH/runner.py:102-110: the objective of one batch (xmh_dnph.hip behind torch.autograd), differentiable with
+        respect to the codes, the class logits and the model's loss.proxies; the display line needs the training loop's loader and
+        optimiser, which this package does not build, and is skipped without them."""
+        all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, img_pre=img_pre, txt_pre=txt_pre, labels=label,
+                                                         indexs=index, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
+    def generate_hash(self, image, text, key_padding_mask=None):
+        """runners/DNPH/runner.py:138-141: the codes alone; the class logits are a training signal"""
+        (image_hash, _), (text_hash, _) = towers.run_both(lambda: self.model.encode_image(image), lambda: self.model.encode_text(text))
+        return image_hash, text_hash

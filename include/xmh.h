@@ -907,6 +907,44 @@ size_t xmh_bertadam_ws_bytes(int64_t n_tensors, int64_t total_chunks);
 int xmh_bertadam_step(const xmh_bertadam_tensor* table, int64_t n_tensors, const xmh_bertadam_chunk_ref* chunk_map,
                       int64_t total_chunks, void* ws, size_t ws_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DNPH (reference models/DNPH): the proxy + class-prediction + noise objective, its gradients, the noise assignment, and the
+ * backward of a plain linear layer (the class-prediction layers).  DESIGN 3.18.
+ *
+ * f_img, f_txt [B, K] fp32 (the codes), p_img, p_txt [B, Cp] fp32 (class logits), P [C, K] fp32 (proxies), lab [B][ceil(C/32)] as
+ * xmh_pack_labels writes it for C classes, noise_img / noise_txt [B, K] fp32 +-1 or NULL (no noise term of that modality).
+ *   u = normalize(cat(f_img, f_txt)), q = normalize(P) (eps 1e-12); D[n][c] = |u_n - q_c|^2 + mrg l[n][c]
+ *   p_loss = mean over the 2B rows of sum_c -l log_softmax(-D[n][:])[c]
+ *   d_loss_m = mean_b CE(p_m[b], t[b]), t[b] the lowest set class of row b (0 for a row without one)
+ *   noise_m = mean_b sum_k f_m noise_m;  loss = p_loss + d_loss_img + d_loss_txt - noise_alpha (noise_img + noise_txt)
+ * Cp is the width of the prediction layers (the reference always builds them with 80 outputs), C the number of proxies: Cp >= C,
+ * else XMH_EINVAL.  B <= 4096, K <= 4096, C <= 1024, Cp <= 1024 (XMH_ENOTSUP beyond).  No host synchronisation, no allocation, no
+ * float atomics, every sum in one fixed order (two calls agree to the bit); non-finite inputs pass through as through the
+ * reference's expression.  Workspace: xmh_dnph_loss_ws_bytes(B, K, C, Cp) bytes of device memory, 256-byte aligned (0 for a shape
+ * outside the bounds; XMH_ENOMEM when shorter).  Argument errors are reported before any launch.  2 launches per call.
+ * ------------------------------------------------------------------------------------------- */
+size_t xmh_dnph_loss_ws_bytes(int64_t B, int K, int C, int Cp);
+/* out8 (device doubles): loss, p_loss, d_loss_img, d_loss_txt, noise_img, noise_txt, 0, 0 */
+int xmh_dnph_loss(const float* f_img, const float* f_txt, const float* p_img, const float* p_txt, const float* P, int64_t B, int K,
+                  int C, int Cp, const uint32_t* lab, float mrg, float noise_alpha, const float* noise_img, const float* noise_txt,
+                  void* ws, size_t ws_bytes, double* out8, xmh_stream_t stream);
+/* d loss times upstream[0] (a device float; NULL = 1) -> grad_f_img, grad_f_txt [B, K], grad_p_img, grad_p_txt [B, Cp], grad_P
+ * [C, K]: written, or added to when accumulate != 0.  Each may be NULL: that gradient is not formed. */
+int xmh_dnph_loss_grad(const float* f_img, const float* f_txt, const float* p_img, const float* p_txt, const float* P, int64_t B,
+                       int K, int C, int Cp, const uint32_t* lab, float mrg, float noise_alpha, const float* noise_img,
+                       const float* noise_txt, const float* upstream, float* grad_f_img, float* grad_f_txt, float* grad_p_img,
+                       float* grad_p_txt, float* grad_P, int accumulate, void* ws, size_t ws_bytes, xmh_stream_t stream);
+/* HOST function, no GPU call: the square linear sum assignment, exact (shortest augmenting paths, Jonker-Volgenant).  cost [n][n]
+ * row-major host doubles, all finite; col_of_row [n] receives the column of every row, the total cost minimal.  n <= 4096
+ * (XMH_ENOTSUP beyond).  A function of the matrix alone: ties are broken by column order. */
+int xmh_assign_min_cost(const double* cost, int n, int* col_of_row);
+/* y = x w^T + b backward: d_y [B, N], x [B, E], w [N, E] -> d_w [N, E], d_b [N] (written, or added to when accumulate != 0), d_x
+ * [B, E] (written); each may be NULL.  The fixed-order exact-fp32 products of the hash heads' backward.  B <= 4096, E <= 2048,
+ * N <= 1024 (XMH_ENOTSUP beyond).  No workspace is needed (NULL, 0 is accepted; a non-NULL one must be 256-byte aligned).
+ * 2 launches with every gradient asked for. */
+int xmh_linear_backward(const float* w, const float* x, const float* d_y, int64_t B, int E, int N, float* d_w, float* d_b, float* d_x,
+                        int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
