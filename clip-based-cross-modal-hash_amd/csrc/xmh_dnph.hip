@@ -94,14 +94,21 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return m;
 }
 
-// log sum_i exp(v[i]) over n values the block can read (n <= kMaxC), the maximum subtracted; valid on every thread
-__device__ __forceinline__ float block_lse(const float* v, int n, float* fsh, double* dsh) {
+// sum_i exp(v[i] - max) over n values the block can read (n <= kMaxC) and the maximum in *mx; valid on every thread
+__device__ __forceinline__ double block_exp_sum(const float* v, int n, float* fsh, double* dsh, float* mx) {
     float m = -INFINITY;
     for (int i = threadIdx.x; i < n; i += kThreads) m = fmaxf(m, v[i]);
     m = block_max(m, fsh);
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += kThreads) s += (double)expf(v[i] - m);
-    s = xmh::block_sum<kWaves>(s, dsh);
+    *mx = m;
+    return xmh::block_sum<kWaves>(s, dsh);
+}
+
+// log sum_i exp(v[i]), the maximum subtracted; valid on every thread
+__device__ __forceinline__ float block_lse(const float* v, int n, float* fsh, double* dsh) {
+    float m;
+    const double s = block_exp_sum(v, n, fsh, dsh, &m);
     return m + logf((float)s);
 }
 
@@ -282,10 +289,13 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
         if (gr.p[m]) {                                           // (softmax(p) - onehot(t)) / B
             const float* pr = a.p[m] + (int64_t)b * a.Cp;
             float* out = gr.p[m] + (int64_t)b * a.Cp;
-            const float lse = block_lse(pr, a.Cp, fsh, dsh);
+            // exp(p - max) / sum, not exp(p - lse): lse carries the rounding of the maximum's size (half an ulp of 375 is 1.5e-5
+            // of every softmax entry when the logits are that large), the quotient does not
+            float mx;
+            const float sum = (float)block_exp_sum(pr, a.Cp, fsh, dsh, &mx);
             const int t = ws.cnt[2 * b + 1];
             for (int c = threadIdx.x; c < a.Cp; c += kThreads) {
-                const float d = g * ((expf(pr[c] - lse) - (c == t ? 1.0f : 0.0f)) / (float)a.B);
+                const float d = g * ((expf(pr[c] - mx) / sum - (c == t ? 1.0f : 0.0f)) / (float)a.B);
                 out[c] = accumulate ? out[c] + d : d;
             }
         }
