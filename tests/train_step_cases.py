@@ -118,9 +118,10 @@ def kind_of(name):
 
 
 # ---- the pieces ---------------------------------------------------------------------------------------------------------------
-def dcmht_head(x, t, bn, eps=NORM_EPS):
+def dcmht_head(x, t, bn, eps=NORM_EPS, mask=None):
     """one DCMHT modality head in train mode, in the dtype of x -> (probs [B, 2K], dict(z: the fc2 pre-activations, n: fc2's input,
-    o: the normalisation's input)); t: the head's tensors under its own key names"""
+    o: the normalisation's input)); t: the head's tensors under its own key names.  mask: the relu decisions to take ([B, 2K] bool)
+    in place of z > 0, which is what None takes"""
     e = x.shape[1]
     F = torch.nn.functional
     o = F.linear(F.linear(x, t["atten.in_proj_weight"][2 * e:], t["atten.in_proj_bias"][2 * e:]), t["atten.out_proj.weight"],
@@ -130,8 +131,15 @@ def dcmht_head(x, t, bn, eps=NORM_EPS):
     else:
         n = F.layer_norm(o, (e,), t["norm.weight"], t["norm.bias"], eps)
     z = F.linear(n, t["fc2.weight"], t["fc2.bias"])
-    f = torch.relu(z)
+    f = torch.relu(z) if mask is None else torch.where(torch.as_tensor(mask), z, torch.zeros_like(z))
     return torch.softmax(f.view(f.shape[0], -1, 2), -1).view(f.shape[0], -1), {"z": z, "n": n, "o": o}
+
+
+def update_bn(buf, o, pre="hash.img_hash.norm."):
+    """BatchNorm's running statistics and batch count after a train-mode forward on the normalisation's input o"""
+    buf[pre + "running_mean"] = (1 - BN_MOMENTUM) * buf[pre + "running_mean"] + BN_MOMENTUM * o.mean(0)
+    buf[pre + "running_var"] = (1 - BN_MOMENTUM) * buf[pre + "running_var"] + BN_MOMENTUM * o.var(0, unbiased=True)
+    buf[pre + "num_batches_tracked"] += 1
 
 
 def tie_bound(n, w):
@@ -243,11 +251,7 @@ def _forward(arch, t, buf, image, ids, labels, mask, dtype):
     if arch == "DCMHT":
         pi, ai = dcmht_head(e_img, heads["img"], True)
         pt, at = dcmht_head(e_txt, heads["txt"], False)
-        o = ai["o"].detach()
-        pre = "hash.img_hash.norm."
-        buf[pre + "running_mean"] = (1 - BN_MOMENTUM) * buf[pre + "running_mean"] + BN_MOMENTUM * o.mean(0)
-        buf[pre + "running_var"] = (1 - BN_MOMENTUM) * buf[pre + "running_var"] + BN_MOMENTUM * o.var(0, unbiased=True)
-        buf[pre + "num_batches_tracked"] += 1
+        update_bn(buf, ai["o"].detach())
         rec["z"] = {mod: a["z"].detach().double().numpy() for mod, a in (("img", ai), ("txt", at))}
         rec["tie"] = {mod: tie_bound(a["n"].detach().numpy(), heads[mod]["fc2.weight"].detach().numpy()) for mod, a in (("img", ai), ("txt", at))}
         rec["loss_t"] = DC.terms(pi, pt, labels, K, "euclidean")[0]
