@@ -533,3 +533,317 @@ extern "C" int xmh_linear_backward(const float* w, const float* x, const float* 
     XMH_LAUNCH_CHECK(who);
     return XMH_OK;
 }
+
+// ---- DIMCH token-set head (reference models/DIMCH/hash/hash.py:18-52) ---------------------------------------------------
+//   tokens [B, T, E] -> c = relu(Conv1d(T -> M, kernel 3, padding 1) along E)  [B M, E]
+//                    -> a = dropout(relu(c W1^T + b1))                          [B M, H]
+//                    -> embeds = a W2^T + b2                                    [B, M, K]
+//                    -> pooled = mean over the M set members, hash = tanh(pooled) or the pair softmax of it   [B, K]
+//   forward   5 launches: k_dimch_conv, k_mm<NT>, k_dimch_relu_drop, k_mm<NT>, k_dimch_pool  (inference and train mode are the same
+//             launches: inference keeps c and a in its workspace, train mode in the saved buffer, so eval == train at p = 0 to the bit)
+//   backward  9 launches with every gradient asked for: k_dimch_pool_bwd (d embeds + d hash through the pooling), k_mm<TN> (dW2, db2),
+//             k_mm<NN> (da), k_dimch_mask (dropout scale and relu mask), k_mm<TN> (dW1, db1), k_mm<NN> (dc), k_dimch_mask (relu mask),
+//             k_dimch_conv_wgrad (dWc, dbc), k_dimch_conv_xgrad (d tokens)
+// The convolution sums over t in index order, its three taps in order, one fmaf chain per output; its weight gradient sums in double,
+// each thread over a strided subset of (b, e) and the 256 partial sums by a fixed tree.  No atomics: two calls agree to the bit.
+namespace {
+
+constexpr int kDimchMaxRows = 512 * 64, kDimchMaxT = 256, kDimchMaxK = 256;
+constexpr int kConvM = 8;                        // set members per thread of k_dimch_conv: one load of the token row feeds 8 outputs
+
+struct DimchSaved {
+    float* c;        // [B M, E] relu output of the convolution
+    float* a;        // [B M, H] relu output of the first linear layer, after the dropout
+    float* pooled;   // [B, K] mean over the set, before tanh / softmax
+};
+
+size_t dimch_saved_layout(int64_t B, int E, int H, int M, int K, void* base, DimchSaved* s) {
+    xmh::Arena ar(base);
+    DimchSaved v;
+    v.c = ar.take<float>((size_t)B * M * E);
+    v.a = ar.take<float>((size_t)B * M * H);
+    v.pooled = ar.take<float>((size_t)B * K);
+    if (s) *s = v;
+    return ar.used;
+}
+
+struct DimchWork {
+    float *ge, *ga, *gc;   // d embeds [B M, K], d a [B M, H], d c [B M, E]
+};
+
+size_t dimch_work_layout(int64_t B, int E, int H, int M, int K, void* base, DimchWork* w) {
+    xmh::Arena ar(base);
+    DimchWork v;
+    v.ge = ar.take<float>((size_t)B * M * K);
+    v.ga = ar.take<float>((size_t)B * M * H);
+    v.gc = ar.take<float>((size_t)B * M * E);
+    if (w) *w = v;
+    return ar.used;
+}
+
+// grid (ceil(E / 256), ceil(M / kConvM), B): thread = one column e of kConvM set members
+__global__ __launch_bounds__(kThreads) void k_dimch_conv(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                         int T, int E, int M, float* __restrict__ c) {
+    const int e = blockIdx.x * kThreads + threadIdx.x, m0 = blockIdx.y * kConvM, b = blockIdx.z;
+    if (e >= E) return;
+    float acc[kConvM];
+#pragma unroll
+    for (int i = 0; i < kConvM; ++i) acc[i] = 0.0f;
+    const float* xb = x + (int64_t)b * T * E;
+    for (int t = 0; t < T; ++t) {
+        const float* r = xb + (int64_t)t * E;
+        const float xl = e > 0 ? r[e - 1] : 0.0f, xc = r[e], xr = e + 1 < E ? r[e + 1] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < kConvM; ++i) {
+            if (m0 + i < M) {
+                const float* wt = w + ((int64_t)(m0 + i) * T + t) * 3;
+                acc[i] = fmaf(wt[2], xr, fmaf(wt[1], xc, fmaf(wt[0], xl, acc[i])));
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kConvM; ++i)
+        if (m0 + i < M) {
+            const float z = acc[i] + bias[m0 + i];
+            c[((int64_t)b * M + m0 + i) * E + e] = z > 0.0f ? z : (z != z ? z : 0.0f);      // relu that lets a NaN through
+        }
+}
+
+// a = relu(a), then the dropout: a * scale where keep, 0 elsewhere (keep NULL: no dropout)
+__global__ __launch_bounds__(kThreads) void k_dimch_relu_drop(float* a, const uint8_t* __restrict__ keep, float scale, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    float z = a[i];
+    z = z > 0.0f ? z : (z != z ? z : 0.0f);
+    if (keep) z = keep[i] ? z * scale : 0.0f;
+    a[i] = z;
+}
+
+__device__ inline void dimch_pair(const float* pooled, int64_t row, int k, float* p0, float* p1) {
+    const float z0 = pooled[row + (k & ~1)], z1 = pooled[row + (k | 1)], m = fmaxf(z0, z1);
+    const float e0 = expf(z0 - m), e1 = expf(z1 - m), inv = 1.0f / (e0 + e1);
+    *p0 = e0 * inv;
+    *p1 = e1 * inv;
+}
+
+// thread = one (b, k): the mean over the M set members in index order, then tanh or the pair softmax over (2j, 2j + 1)
+__global__ __launch_bounds__(kThreads) void k_dimch_pool(const float* __restrict__ embeds, int64_t B, int M, int K, int softmax,
+                                                         float* pooled, float* __restrict__ hash) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= B * K) return;
+    const int64_t b = i / K;
+    const int k = (int)(i - b * K);
+    auto mean = [&](int kk) {
+        float s = 0.0f;
+        for (int m = 0; m < M; ++m) s += embeds[(b * M + m) * K + kk];
+        return s / (float)M;
+    };
+    const float z = mean(k);
+    pooled[i] = z;
+    if (!softmax) {
+        hash[i] = tanhf(z);
+    } else {
+        const float zo = mean(k ^ 1), mx = fmaxf(z, zo);      // the partner of the pair, summed in the same order as its own thread does
+        const float ez = expf(z - mx), eo = expf(zo - mx);
+        const float e0 = (k & 1) ? eo : ez, e1 = (k & 1) ? ez : eo, inv = 1.0f / (e0 + e1);
+        hash[i] = ((k & 1) ? e1 : e0) * inv;
+    }
+}
+
+// ge [b, m, k] = d_embeds [b, m, k] + d pooled [b, k] / M, d pooled from d_hash through tanh or the pair softmax; either may be NULL
+__global__ __launch_bounds__(kThreads) void k_dimch_pool_bwd(const float* __restrict__ d_embeds, const float* __restrict__ d_hash,
+                                                             const float* __restrict__ pooled, int64_t B, int M, int K, int softmax,
+                                                             float* __restrict__ ge) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= B * M * K) return;
+    const int k = (int)(i % K);
+    const int64_t b = i / ((int64_t)M * K), row = b * K;
+    float g = d_embeds ? d_embeds[i] : 0.0f;
+    if (d_hash) {
+        float dz;
+        if (!softmax) {
+            const float h = tanhf(pooled[row + k]);
+            dz = d_hash[row + k] * (1.0f - h * h);
+        } else {
+            float p0, p1;
+            dimch_pair(pooled, row, k, &p0, &p1);
+            const float g0 = d_hash[row + (k & ~1)], g1 = d_hash[row + (k | 1)], dot = g0 * p0 + g1 * p1;
+            dz = (k & 1) ? p1 * (g1 - dot) : p0 * (g0 - dot);
+        }
+        g += dz / (float)M;
+    }
+    ge[i] = g;
+}
+
+// g = act > 0 ? g * scale : 0 in place (the relu mask is the sign of the stored output; after the dropout a dropped element is 0 too)
+__global__ __launch_bounds__(kThreads) void k_dimch_mask(float* g, const float* __restrict__ act, float scale, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    g[i] = act[i] > 0.0f ? g[i] * scale : 0.0f;
+}
+
+// grid (T + 1, M): block (t, m) owns dWc [m, t, 0..2]; block (T, m) owns dbc [m].  Sums over (b, e) in double.
+__global__ __launch_bounds__(kThreads) void k_dimch_conv_wgrad(const float* __restrict__ gc, const float* __restrict__ x, int64_t B, int T, int E,
+                                                               int M, float* dw, float* db, int accumulate) {
+    __shared__ double sh[3][kThreads];
+    const int t = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+    if (t == T ? !db : !dw) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int64_t n = B * E;
+    for (int64_t i = tid; i < n; i += kThreads) {
+        const int64_t b = i / E;
+        const int e = (int)(i - b * E);
+        const double g = (double)gc[(b * M + m) * E + e];
+        if (t == T) {
+            s0 += g;
+        } else {
+            const float* r = x + (b * T + t) * E;
+            if (e > 0) s0 += g * (double)r[e - 1];
+            s1 += g * (double)r[e];
+            if (e + 1 < E) s2 += g * (double)r[e + 1];
+        }
+    }
+    sh[0][tid] = s0;
+    sh[1][tid] = s1;
+    sh[2][tid] = s2;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            sh[0][tid] += sh[0][tid + h];
+            sh[1][tid] += sh[1][tid + h];
+            sh[2][tid] += sh[2][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (t == T) {
+            db[m] = accumulate ? db[m] + (float)sh[0][0] : (float)sh[0][0];
+        } else {
+            float* o = dw + ((int64_t)m * T + t) * 3;
+            for (int k = 0; k < 3; ++k) o[k] = accumulate ? o[k] + (float)sh[k][0] : (float)sh[k][0];
+        }
+    }
+}
+
+// grid (ceil(E / 256), T, B): d tokens [b, t, e] = sum_m sum_k Wc [m, t, k] gc [b, m, e - k + 1], m in index order
+__global__ __launch_bounds__(kThreads) void k_dimch_conv_xgrad(const float* __restrict__ gc, const float* __restrict__ w, int T, int E, int M,
+                                                               float* __restrict__ dx) {
+    const int e = blockIdx.x * kThreads + threadIdx.x, t = blockIdx.y, b = blockIdx.z;
+    if (e >= E) return;
+    float acc = 0.0f;
+    for (int m = 0; m < M; ++m) {
+        const float* g = gc + ((int64_t)b * M + m) * E;
+        const float* wt = w + ((int64_t)m * T + t) * 3;
+        const float gr = e + 1 < E ? g[e + 1] : 0.0f, gm = g[e], gl = e > 0 ? g[e - 1] : 0.0f;
+        acc = fmaf(wt[2], gl, fmaf(wt[1], gm, fmaf(wt[0], gr, acc)));
+    }
+    dx[((int64_t)b * T + t) * E + e] = acc;
+}
+
+bool dimch_shape_ok(int64_t B, int T, int E, int H, int M, int K) {
+    return B > 0 && T > 0 && E > 0 && H > 0 && M > 0 && K > 0 && B <= 65535 && B * M <= kDimchMaxRows && T <= kDimchMaxT && E <= kMaxE &&
+           H <= kMaxE && K <= kDimchMaxK;
+}
+
+int check_dimch(const char* who, const xmh_dimch_head* h, const float* tokens, int64_t B) {
+    if (!h || !tokens || !h->conv_w || !h->conv_b || !h->w1 || !h->b1 || !h->w2 || !h->b2) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (B <= 0 || h->T <= 0 || h->E <= 0 || h->H <= 0 || h->M <= 0 || h->K <= 0)
+        return xmh::fail(XMH_EINVAL, "%s: bad shape B=%lld T=%d E=%d H=%d M=%d K=%d", who, (long long)B, h->T, h->E, h->H, h->M, h->K);
+    if (h->hash_func != XMH_DIMCH_TANH && h->hash_func != XMH_DIMCH_SOFTMAX) return xmh::fail(XMH_EINVAL, "%s: hash_func=%d", who, h->hash_func);
+    if (h->hash_func == XMH_DIMCH_SOFTMAX && (h->K & 1)) return xmh::fail(XMH_EINVAL, "%s: K=%d is odd (one (off, on) pair per bit)", who, h->K);
+    if (!dimch_shape_ok(B, h->T, h->E, h->H, h->M, h->K))
+        return xmh::fail(XMH_ENOTSUP, "%s: B=%lld T=%d E=%d H=%d M=%d K=%d outside B M <= %d, T <= %d, E, H <= %d, K <= %d", who, (long long)B,
+                         h->T, h->E, h->H, h->M, h->K, kDimchMaxRows, kDimchMaxT, kMaxE, kDimchMaxK);
+    return XMH_OK;
+}
+
+int dimch_forward(const char* who, const xmh_dimch_head* h, const float* tokens, const uint8_t* keep, float p, int64_t B, float* embeds,
+                  float* hash, void* saved, size_t saved_bytes, xmh_stream_t stream) {
+    if (int rc = check_dimch(who, h, tokens, B)) return rc;
+    if (!embeds || !hash) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (!(p >= 0.0f && p < 1.0f)) return xmh::fail(XMH_EINVAL, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+    if (int rc = check_buffer(who, "buffer", saved, saved_bytes, dimch_saved_layout(B, h->E, h->H, h->M, h->K, nullptr, nullptr))) return rc;
+    DimchSaved s;
+    dimch_saved_layout(B, h->E, h->H, h->M, h->K, saved, &s);
+    hipStream_t st = xmh::as_stream(stream);
+    const int rows = (int)(B * h->M);
+    hipLaunchKernelGGL(k_dimch_conv, dim3((h->E + kThreads - 1) / kThreads, (h->M + kConvM - 1) / kConvM, (unsigned)B), dim3(kThreads), 0, st,
+                       tokens, h->conv_w, h->conv_b, h->T, h->E, h->M, s.c);
+    MmOut o = {};
+    o.C = s.a;
+    o.bias = h->b1;
+    launch_nt(st, s.c, h->w1, rows, h->H, h->E, o);
+    const int64_t n = (int64_t)rows * h->H;
+    hipLaunchKernelGGL(k_dimch_relu_drop, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s.a, keep, 1.0f / (1.0f - p), n);
+    o.C = embeds;
+    o.bias = h->b2;
+    launch_nt(st, s.a, h->w2, rows, h->K, h->H, o);
+    hipLaunchKernelGGL(k_dimch_pool, dim3((unsigned)((B * h->K + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, embeds, B, h->M, h->K,
+                       h->hash_func == XMH_DIMCH_SOFTMAX, s.pooled, hash);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t xmh_head_dimch_bytes(int64_t B, int T, int E, int H, int M, int K, size_t* workspace_bytes) {
+    const bool ok = dimch_shape_ok(B, T, E, H, M, K);
+    if (workspace_bytes) *workspace_bytes = ok ? dimch_work_layout(B, E, H, M, K, nullptr, nullptr) : 0;
+    return ok ? dimch_saved_layout(B, E, H, M, K, nullptr, nullptr) : 0;
+}
+
+extern "C" int xmh_head_dimch(const xmh_dimch_head* h, const float* tokens, int64_t B, float* embeds, float* hash, void* workspace,
+                              size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dimch");
+    return dimch_forward("xmh_head_dimch", h, tokens, nullptr, 0.0f, B, embeds, hash, workspace, workspace_bytes, stream);
+}
+
+extern "C" int xmh_head_dimch_train_forward(const xmh_dimch_head* h, const float* tokens, const uint8_t* keep, float p, int64_t B,
+                                            float* embeds, float* hash, void* saved, size_t saved_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dimch_train_forward");
+    return dimch_forward("xmh_head_dimch_train_forward", h, tokens, keep, keep ? p : 0.0f, B, embeds, hash, saved, saved_bytes, stream);
+}
+
+extern "C" int xmh_head_dimch_backward(const xmh_dimch_head* h, const float* tokens, int has_keep, float p, const float* d_embeds,
+                                       const float* d_hash, int64_t B, const void* saved, size_t saved_bytes, const xmh_dimch_head_grads* g,
+                                       int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dimch_backward");
+    const char* who = "xmh_head_dimch_backward";
+    if (int rc = check_dimch(who, h, tokens, B)) return rc;
+    if (!g) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (!(p >= 0.0f && p < 1.0f)) return xmh::fail(XMH_EINVAL, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+    const int E = h->E, H = h->H, M = h->M, K = h->K, T = h->T;
+    if (int rc = check_buffer(who, "saved buffer", saved, saved_bytes, dimch_saved_layout(B, E, H, M, K, nullptr, nullptr))) return rc;
+    if (int rc = check_buffer(who, "workspace", workspace, workspace_bytes, dimch_work_layout(B, E, H, M, K, nullptr, nullptr))) return rc;
+    const bool need_c = g->d_conv_w || g->d_conv_b || g->d_tokens;
+    const bool need_a = need_c || g->d_w1 || g->d_b1;
+    if ((!d_embeds && !d_hash) || (!need_a && !g->d_w2 && !g->d_b2)) return XMH_OK;
+    DimchSaved s;
+    DimchWork w;
+    dimch_saved_layout(B, E, H, M, K, const_cast<void*>(saved), &s);
+    dimch_work_layout(B, E, H, M, K, workspace, &w);
+    hipStream_t st = xmh::as_stream(stream);
+    const int rows = (int)(B * M);
+    auto blocks = [](int64_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); };
+    hipLaunchKernelGGL(k_dimch_pool_bwd, blocks((int64_t)rows * K), dim3(kThreads), 0, st, d_embeds, d_hash, s.pooled, B, M, K,
+                       h->hash_func == XMH_DIMCH_SOFTMAX, w.ge);
+    weight_grads(st, w.ge, s.a, rows, K, H, g->d_w2, g->d_b2, accumulate);
+    if (need_a) {
+        launch_nn(st, w.ge, h->w2, rows, K, H, w.ga);
+        hipLaunchKernelGGL(k_dimch_mask, blocks((int64_t)rows * H), dim3(kThreads), 0, st, w.ga, s.a, has_keep ? 1.0f / (1.0f - p) : 1.0f,
+                           (int64_t)rows * H);
+        weight_grads(st, w.ga, s.c, rows, H, E, g->d_w1, g->d_b1, accumulate);
+    }
+    if (need_c) {
+        launch_nn(st, w.ga, h->w1, rows, H, E, w.gc);
+        hipLaunchKernelGGL(k_dimch_mask, blocks((int64_t)rows * E), dim3(kThreads), 0, st, w.gc, s.c, 1.0f, (int64_t)rows * E);
+        if (g->d_conv_w || g->d_conv_b)
+            hipLaunchKernelGGL(k_dimch_conv_wgrad, dim3(T + 1, M), dim3(kThreads), 0, st, w.gc, tokens, B, T, E, M, g->d_conv_w, g->d_conv_b,
+                               accumulate);
+        if (g->d_tokens)
+            hipLaunchKernelGGL(k_dimch_conv_xgrad, dim3((E + kThreads - 1) / kThreads, T, (unsigned)B), dim3(kThreads), 0, st, w.gc, h->conv_w, T, E,
+                               M, g->d_tokens);
+    }
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}

@@ -118,6 +118,14 @@ class TwdhStreams(C.Structure):                # xmh_twdh_streams
 
 
 # name -> (restype, argtypes); mirrors include/xmh.h one to one
+class DimchHead(C.Structure):                  # xmh_dimch_head
+    _fields_ = [(k, vp) for k in ("conv_w", "conv_b", "w1", "b1", "w2", "b2")] + [(k, i32) for k in ("T", "E", "H", "M", "K", "hash_func")]
+
+
+class DimchHeadGrads(C.Structure):             # xmh_dimch_head_grads
+    _fields_ = [(k, vp) for k in ("d_conv_w", "d_conv_b", "d_w1", "d_b1", "d_w2", "d_b2", "d_tokens")]
+
+
 PROTOTYPES = {
     "xmh_version": (i32, []),
     "xmh_build_id": (C.c_char_p, []),
@@ -249,6 +257,13 @@ PROTOTYPES = {
                                  sz, vp]),
     "xmh_assign_min_cost": (i32, [vp, i32, vp]),
     "xmh_linear_backward": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
+    "xmh_dimch_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_dimch_loss": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp]),
+    "xmh_dimch_loss_grad": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "xmh_head_dimch_bytes": (sz, [i64, i32, i32, i32, i32, i32, C.POINTER(sz)]),
+    "xmh_head_dimch": (i32, [C.POINTER(DimchHead), vp, i64, vp, vp, vp, sz, vp]),
+    "xmh_head_dimch_train_forward": (i32, [C.POINTER(DimchHead), vp, vp, C.c_float, i64, vp, vp, vp, sz, vp]),
+    "xmh_head_dimch_backward": (i32, [C.POINTER(DimchHead), vp, i32, C.c_float, vp, vp, i64, vp, sz, C.POINTER(DimchHeadGrads), i32, vp, sz, vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

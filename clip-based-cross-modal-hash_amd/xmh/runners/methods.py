@@ -386,3 +386,70 @@ class DNPHTrainer(_MethodTrainer):
         """runners/DNPH/runner.py:138-141: the codes alone; the class logits are a training signal"""
         (image_hash, _), (text_hash, _) = towers.run_both(lambda: self.model.encode_image(image), lambda: self.model.encode_text(text))
         return image_hash, text_hash
+
+
+def _step_dimch(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch of DIMCH (runners/DIMCH/runner.py:132-133): the token embeddings and the codes of both modalities into the objective"""
+    img_embeds, img_hash, txt_embeds, txt_hash = trainer.model.forward_train(image, text)
+    return trainer.compute_loss(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash, label=label, index=index,
+                                epoch=epoch, times=times, global_step=trainer.global_step)
+
+
+@registry.register_runner("DIMCHTrainer")
+class DIMCHTrainer(_MethodTrainer):
+    """runners/DIMCH/runner.py: the model's encoders return (token embeddings, code); evaluation quantises the tanh code by its sign.
+    With ``hash_func: softmax`` the code is 2K wide and the reference writes it into its K-wide buffer and fails (:147-149 with
+    runners/base.py get_code); ``valid`` says so instead."""
+
+    loss_type = "l1"                                            # runners/DIMCH/runner.py:33: only named in the display line
+
+    def __init__(self, cfg, *a, **k):
+        self.hash_func = cfg.model.get("hash_func", "softmax")
+        self.hash_scale = 2 if self.hash_func == "softmax" else 1   # runners/DIMCH/runner.py:39-42
+        super().__init__(cfg, *a, **k)
+
+    def build_model(self, cfg_model, output_dim=16, **kwags):
+        """runners/DIMCH/runner.py:87-107: as the base class, and the text token count ``dataset.max_word`` handed on"""
+        arch = cfg_model.get("arch", "DIMCH")
+        cls = registry.get_model_class(arch)
+        assert cls is not None, "model '%s' is not registered (known: %s)" % (arch, registry.list_models())
+        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num,
+                                     txt_token_size=self.cfg.dataset.get("max_word", 32))
+        if os.path.isfile(self.model_state):
+            self.logger.info("loading model...")
+            self.model.load_state_dict(torch.load(self.model_state, map_location=f"cuda:{self.device}"))
+        self.model.float()
+        self.model.to(self.device)
+        self.logger.info("Building model!")
+        self.logger.info(f"Output dim: {self.output_dim}")
+
+    def train_epoch(self, epoch: int):
+        """runners/DIMCH/runner.py:119-140"""
+        _train_epoch(self, epoch, step=_step_dimch)
+
+    def compute_loss(self, img_embeds=None, img_hash=None, txt_embeds=None, txt_hash=None, label=None, index=None, epoch=0, times=0,
+                     global_step=0, **kwags):
+        """runners/DIMCH/runner.py:109-117: the objective of one batch (xmh_dimch.hip behind torch.autograd), differentiable with
+        respect to the token embeddings and the codes; the display line needs the training loop's loader and optimiser and is
+        skipped without them."""
+        all_loss, loss_dict = self.model.object_function(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash,
+                                                         labels=label, indexs=index, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=img_embeds.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
+    def merge_hash(self, image_embed, text_embed):
+        """runners/DIMCH/runner.py:142-145"""
+        return torch.sign((image_embed + text_embed).detach() / 2)
+
+    def generate_hash(self, image, text, key_padding_mask=None):
+        """runners/DIMCH/runner.py:147-149: the two codes; the token embeddings are a training signal"""
+        _, image_hash, _, text_hash = self.model(image, text)
+        return image_hash, text_hash
+
+    def valid(self, epoch, k=None):
+        if self.hash_func == "softmax":
+            raise NotImplementedError("DIMCHTrainer.valid with hash_func: softmax: the code is %d wide for %d bits, and the reference "
+                                      "writes it into its %d-wide buffer and fails; evaluation is built for hash_func: tanh"
+                                      % (2 * self.output_dim, self.output_dim, self.output_dim))
+        return super().valid(epoch, k=k)

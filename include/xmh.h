@@ -945,6 +945,93 @@ int xmh_assign_min_cost(const double* cost, int n, int* col_of_row);
 int xmh_linear_backward(const float* w, const float* x, const float* d_y, int64_t B, int E, int N, float* d_w, float* d_b, float* d_x,
                         int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DIMCH: the objective over token sets and codes (reference models/DIMCH/DIMCH.py:152-234) and its gradients (csrc/xmh_dimch.hip).
+ * e_img, e_txt [B, M, K] fp32 token embeddings (M set members per sample), h_img, h_txt [B, Kh] fp32 codes, lab: xmh_pack_labels
+ * of the [B, C] 0 / 1 labels.  N = B M; x, y = F.normalize (eps 1e-12) of the token rows viewed as [N, K]; G = u v^T.
+ *   s(u, v)[i][j] over the M x M block of G of set i of u and set j of v, by mode:
+ *     smooth_chamfer  (1 / den) [ (1 / (M tau sigma)) sum_a log sum_b exp(tau sigma G_ab) + (1 / (M tau)) sum_b log sum_a exp(tau G_ab) ]
+ *     chamfer         (1 / den) [ (1 / M) sum_a max_b G_ab + (1 / M) sum_b max_a G_ab ]
+ *     max             max_ab G_ab          avg   mean_ab sigmoid(G_ab)
+ *   D_i2t = clamp(1 - s(x, y), 0), D_t2i = clamp(1 - s(y, x), 0)
+ *   T(D, m): c[a][p] label overlap, sim = c > 0, Z[a] = sum_j (2^c_(j) - 1) / log2(j + 2) over row a sorted descending,
+ *            w = (2^c - 1) / Z, t[a][p][n] = (w[a][p] - w[a][n]) sim[a][p] (1 - sim[a][n]) (D[a][p] - D[a][n] + m),
+ *            T = sum max(t, 0) / (#{t > 1e-16} + 1e-16).  A row without a label makes it NaN, as in the reference.
+ *   MMD = mean exp(-gamma |x_a - x_b|) - 2 mean exp(-gamma |x_a - y_b|) + mean exp(-gamma |y_a - y_b|) over all N x N pairs
+ *   U(u) = sum_{a < b} exp(-20 |u_a - u_b|^2) / (M (M - 1) / 2) over all N rows, 0 for M = 1
+ *   Th_i2t = T(clamp(1 - cos(h_img, h_txt), 0), triplet_margin), Th_t2i with the roles swapped (cos clamps each norm at 1e-8)
+ *   Q = mean (h - sign h)^2 (tanh) or 1 - mean (2 h - 1)^2 (softmax)
+ *   loss = (T_i2t + T_t2i) / 2 triplet_alpha + mmd_alpha MMD + unif_alpha (U(x) + U(y)) + (Th_i2t + Th_t2i) / 2 hash_triplet_alpha
+ *          + (Q_img + Q_txt) / 2 quan_alpha
+ * B <= 512, M <= 64, K, Kh <= 256, C <= 127 (2^c leaves fp32 beyond) -- XMH_ENOTSUP outside.  No host synchronisation, no allocation,
+ * no float atomics, every sum in one fixed order (two calls agree to the bit); non-finite inputs pass through.  For max and chamfer
+ * the gradient goes to the first maximum.  Workspace: xmh_dimch_loss_ws_bytes(B, M, K, C) bytes of device memory, 256-byte aligned,
+ * O(N K + B^2) (0 for a shape outside the bounds; XMH_ENOMEM when shorter).  Argument errors are reported before any launch.
+ * xmh_dimch_loss: 4 launches.  xmh_dimch_loss_grad: 6 launches (it stands alone: nothing is kept from the forward call).
+ * ------------------------------------------------------------------------------------------- */
+#define XMH_DIMCH_SMOOTH_CHAMFER 0
+#define XMH_DIMCH_CHAMFER 1
+#define XMH_DIMCH_MAX 2
+#define XMH_DIMCH_AVG 3
+#define XMH_DIMCH_TANH 0
+#define XMH_DIMCH_SOFTMAX 1
+typedef struct xmh_dimch_consts {
+    int mode;      /* XMH_DIMCH_SMOOTH_CHAMFER .. XMH_DIMCH_AVG */
+    int hash_func; /* XMH_DIMCH_TANH or XMH_DIMCH_SOFTMAX: which quantisation term */
+    float denominator, temperature, temperature_txt_scale;
+    float token_triplet_margin, triplet_margin, mmd_gamma;
+    float triplet_alpha, mmd_alpha, unif_alpha, hash_triplet_alpha, quan_alpha;
+} xmh_dimch_consts;
+size_t xmh_dimch_loss_ws_bytes(int64_t B, int M, int K, int C);
+/* out12 (device doubles): loss, T_i2t, T_t2i, MMD, U(x) + U(y), Th_i2t, Th_t2i, Q_img, Q_txt, 0, 0, 0.  cst is read on the host. */
+int xmh_dimch_loss(const float* e_img, const float* e_txt, const float* h_img, const float* h_txt, int64_t B, int M, int K, int Kh,
+                   int C, const uint32_t* lab, const xmh_dimch_consts* cst, void* ws, size_t ws_bytes, double* out12,
+                   xmh_stream_t stream);
+/* d loss times upstream[0] (a device float; NULL = 1) -> grad_e_img, grad_e_txt [B, M, K], grad_h_img, grad_h_txt [B, Kh]: written,
+ * or added to when accumulate != 0.  Each may be NULL: that gradient is not formed.  The backward of the normalisation and of both
+ * clamps is included. */
+int xmh_dimch_loss_grad(const float* e_img, const float* e_txt, const float* h_img, const float* h_txt, int64_t B, int M, int K, int Kh,
+                        int C, const uint32_t* lab, const xmh_dimch_consts* cst, const float* upstream, float* grad_e_img,
+                        float* grad_e_txt, float* grad_h_img, float* grad_h_txt, int accumulate, void* ws, size_t ws_bytes,
+                        xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DIMCH token-set head, one modality (reference models/DIMCH/hash/hash.py:18-52; csrc/xmh_head_grad.hip):
+ *   tokens [B, T, E] -> relu(Conv1d(T -> M, kernel 3, padding 1) along E) -> relu(. w1^T + b1) [B M, H] -> dropout -> . w2^T + b2 =
+ *   embeds [B, M, K] -> mean over the M set members -> tanh, or the softmax over the pairs (2j, 2j + 1) = hash [B, K].
+ * All weights are plain fp32 device pointers in the reference's layouts; every product is exact fp32 with one fixed summation order.
+ * B M <= 32768, B <= 65535, T <= 256, E, H <= 2048, K <= 256 (XMH_ENOTSUP beyond; K even for the softmax).
+ * xmh_head_dimch_bytes -> bytes of the buffer that the forward fills (inference: its workspace; train mode: what backward reads -- the two
+ * relu outputs and the pooled pre-activation) and, through *workspace_bytes, of backward's workspace; both 0 outside the bounds.
+ * Buffers are device memory, 256-byte aligned.  The library draws no random numbers: keep is the caller's [B M, H] 0 / 1 byte mask.
+ * xmh_head_dimch and xmh_head_dimch_train_forward: 5 launches (the same kernels: train mode with keep == NULL is inference to the bit).
+ * xmh_head_dimch_backward: 9 launches with every gradient asked for, fewer otherwise.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_dimch_head {
+    const float* conv_w; /* [M, T, 3] */
+    const float* conv_b; /* [M] */
+    const float* w1;     /* [H, E] */
+    const float* b1;     /* [H] */
+    const float* w2;     /* [K, H] */
+    const float* b2;     /* [K] */
+    int T, E, H, M, K;
+    int hash_func;       /* XMH_DIMCH_TANH or XMH_DIMCH_SOFTMAX */
+} xmh_dimch_head;
+typedef struct xmh_dimch_head_grads { /* each may be NULL: that gradient is not formed */
+    float *d_conv_w, *d_conv_b, *d_w1, *d_b1, *d_w2, *d_b2; /* written, or added to when accumulate != 0 */
+    float* d_tokens;                                        /* [B, T, E], always written */
+} xmh_dimch_head_grads;
+size_t xmh_head_dimch_bytes(int64_t B, int T, int E, int H, int M, int K, size_t* workspace_bytes);
+int xmh_head_dimch(const xmh_dimch_head* h, const float* tokens, int64_t B, float* embeds, float* hash, void* workspace,
+                   size_t workspace_bytes, xmh_stream_t stream);
+/* keep == NULL: no dropout (p is ignored) */
+int xmh_head_dimch_train_forward(const xmh_dimch_head* h, const float* tokens, const uint8_t* keep, float p, int64_t B, float* embeds,
+                                 float* hash, void* saved, size_t saved_bytes, xmh_stream_t stream);
+/* d_embeds [B, M, K] and d_hash [B, K] enter through the two outputs; either may be NULL.  has_keep: the forward had a keep mask. */
+int xmh_head_dimch_backward(const xmh_dimch_head* h, const float* tokens, int has_keep, float p, const float* d_embeds,
+                            const float* d_hash, int64_t B, const void* saved, size_t saved_bytes, const xmh_dimch_head_grads* g,
+                            int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
