@@ -39,11 +39,13 @@
 
 #include "xmh_common.h"
 #include "xmh_device.h"
+#include "xmh_triplet.h"
 
 namespace {
 
-constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr int kMaxB = 512, kMaxM = 64, kMaxK = 256, kMaxC = 127;
+namespace trip = xmh::trip;                                     // the triplet term, shared with xmh_umoed.hip
+constexpr int kThreads = trip::kThreads, kWaves = trip::kWaves;
+constexpr int kMaxB = trip::kMaxB, kMaxM = 64, kMaxK = 256, kMaxC = 127;
 constexpr int kT = 64;                 // tile edge: the largest set
 constexpr int kKC = 32;                // k columns staged at a time
 constexpr int kLd = kT + 1;            // row stride of the staged operands and of the G tile
@@ -117,7 +119,7 @@ struct Grads {
 using xmh::wave_sum;
 
 __device__ __forceinline__ float inv_norm(float n, float eps) { return 1.0f / (n < eps ? eps : n); }   // a NaN norm stays NaN
-__device__ __forceinline__ float clamp0(float v) { return v < 0.0f ? 0.0f : v; }                       // torch.clamp(v, 0): NaN stays
+using trip::clamp0;                                                                                    // torch.clamp(v, 0): NaN stays
 
 // ---- preparation -----------------------------------------------------------------------------------------------------------------------
 // One wave per row.  Rows [0, 2N): token rows (x, then y).  Rows [2N, 2N + 2B): code rows, their norm only.
@@ -363,26 +365,7 @@ __global__ __launch_bounds__(kThreads) void k_dimch_tiles(Args a, Ws w) {
 // Anchor row a: label overlaps c[p], sim[p] = c > 0, weights w[p] = (2^c - 1) / Z, Z = sum_j (2^{c_(j)} - 1) / log2(j + 2) over the row
 // sorted descending (the rank of p: columns with a larger count, then equal ones to its left).  All in LDS [B].  Ends with a barrier.
 __device__ __forceinline__ void triplet_weights(const Args& a, int row, int* cs, float* wsh, float* sim, double* dsh) {
-    const int B = a.B;
-    for (int p = threadIdx.x; p < B; p += kThreads) {
-        int c = 0;
-        for (int l = 0; l < a.Lw; ++l) c += __popc(a.lab[(int64_t)row * a.Lw + l] & a.lab[(int64_t)p * a.Lw + l]);
-        cs[p] = c;
-    }
-    __syncthreads();
-    double z = 0.0;
-    for (int p = threadIdx.x; p < B; p += kThreads) {
-        const int c = cs[p];
-        int rank = 0;
-        for (int q = 0; q < B; ++q) rank += (cs[q] > c) || (cs[q] == c && q < p);
-        z += ((double)ldexpf(1.0f, c) - 1.0) / log2((double)(rank + 2));
-    }
-    const float Z = (float)xmh::block_sum<kWaves>(z, dsh);
-    for (int p = threadIdx.x; p < B; p += kThreads) {
-        wsh[p] = (ldexpf(1.0f, cs[p]) - 1.0f) / Z;               // Z = 0 (a row without a label): 0 / 0 = NaN, as in the reference
-        sim[p] = cs[p] > 0 ? 1.0f : 0.0f;
-    }
-    __syncthreads();
+    trip::weights(a.lab, a.Lw, a.B, row, cs, wsh, sim, dsh);     // xmh_triplet.h
 }
 
 // the distance row of anchor `row` of term t into ds [B]; ends with a barrier
@@ -413,27 +396,14 @@ __global__ __launch_bounds__(kThreads) void k_dimch_triplet(Args a, Ws w) {
     for (int t = 0; t < 4; ++t) {
         triplet_distances(a, w, row, t, ds);
         const float mg = term_margin(a, t);
-        double sum = 0.0, cnt = 0.0;
-        for (int p = threadIdx.x; p < B; p += kThreads) {
-            const float wp = wsh[p], sp = sim[p], dp = ds[p];
-            for (int n = 0; n < B; ++n) {
-                const float v = ((wp - wsh[n]) * (sp * (1.0f - sim[n]))) * ((dp - ds[n]) + mg);
-                sum += (double)clamp0(v);
-                cnt += v > 1e-16f ? 1.0 : 0.0;
-            }
-        }
-        sum = xmh::block_sum<kWaves>(sum, dsh);
-        cnt = xmh::block_sum<kWaves>(cnt, dsh);
+        double sum, cnt;
+        trip::row_terms(wsh, sim, ds, B, mg, dsh, &sum, &cnt);
         if (threadIdx.x == 0) w.tsum[t * B + row] = sum, w.tcnt[t * B + row] = cnt;
         __syncthreads();
     }
 }
 
-__device__ __forceinline__ double ordered_sum(const double* v, int n, double* dsh) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += kThreads) s += v[i];
-    return xmh::block_sum<kWaves>(s, dsh);
-}
+using trip::ordered_sum;
 
 __global__ __launch_bounds__(kThreads) void k_dimch_finalize(Args a, Ws w, double* __restrict__ out12) {
     __shared__ double dsh[kWaves];
@@ -475,18 +445,8 @@ __global__ __launch_bounds__(kThreads) void k_dimch_triplet_grad(Args a, Ws w, c
         triplet_distances(a, w, row, t, ds);
         const float mg = term_margin(a, t);
         for (int p = threadIdx.x; p < B; p += kThreads) {
-            const float wp = wsh[p], sp = sim[p], dp = ds[p];
-            double acc = 0.0;
-            for (int n = 0; n < B; ++n) {
-                const float c1 = (wp - wsh[n]) * (sp * (1.0f - sim[n]));          // p the positive, n the negative
-                const float v1 = c1 * ((dp - ds[n]) + mg);
-                acc += (double)(c1 * (v1 >= 0.0f ? 1.0f : 0.0f));
-                const float c2 = (wsh[n] - wp) * (sim[n] * (1.0f - sp));          // n the positive, p the negative
-                const float v2 = c2 * ((ds[n] - dp) + mg);
-                acc -= (double)(c2 * (v2 >= 0.0f ? 1.0f : 0.0f));
-            }
             const float s = t < 2 ? w.S[t][(int64_t)row * B + p] : (t == 2 ? w.Ch[(int64_t)row * B + p] : w.Ch[(int64_t)p * B + row]);
-            const float gd = (float)acc * scale;
+            const float gd = trip::col_grad(wsh, sim, ds, B, mg, p) * scale;
             w.gD[t][(int64_t)row * B + p] = -gd * ((1.0f - s) >= 0.0f ? 1.0f : 0.0f);       // clamp(1 - s, 0) backward
         }
         __syncthreads();

@@ -126,6 +126,21 @@ class DimchHeadGrads(C.Structure):             # xmh_dimch_head_grads
     _fields_ = [(k, vp) for k in ("d_conv_w", "d_conv_b", "d_w1", "d_b1", "d_w2", "d_b2", "d_tokens")]
 
 
+class UmoedLayer(C.Structure):                 # xmh_umoed_layer
+    NAMES = ("ln1_g", "ln1_b", "sa_in_w", "sa_in_b", "sa_out_w", "sa_out_b", "ln2_g", "ln2_b", "ca_in_w", "ca_in_b", "ca_out_w", "ca_out_b",
+             "ln3_g", "ln3_b", "lin_w", "lin_b", "phi", "exp_w", "exp_b", "lin2_w", "lin2_b")
+    _fields_ = [(k, vp) for k in NAMES]
+
+
+class UmoedHead(C.Structure):                  # xmh_umoed_head
+    _fields_ = [("layers", C.POINTER(UmoedLayer)), ("n_layers", i32)] + [(k, vp) for k in ("first_w", "first_b", "queries", "cls_w", "cls_b")] + \
+               [(k, i32) for k in ("E", "d", "heads", "F", "M", "V", "n_experts", "slots", "moe", "hash_func", "merge")] + [("ln_eps", C.c_float)]
+
+
+class UmoedConsts(C.Structure):                # xmh_umoed_consts
+    _fields_ = [("extreme", i32)] + [(k, C.c_float) for k in ("extreme_T", "token_triplet_margin", "triplet_alpha", "unif_alpha")]
+
+
 PROTOTYPES = {
     "xmh_version": (i32, []),
     "xmh_build_id": (C.c_char_p, []),
@@ -264,6 +279,11 @@ PROTOTYPES = {
     "xmh_head_dimch": (i32, [C.POINTER(DimchHead), vp, i64, vp, vp, vp, sz, vp]),
     "xmh_head_dimch_train_forward": (i32, [C.POINTER(DimchHead), vp, vp, C.c_float, i64, vp, vp, vp, sz, vp]),
     "xmh_head_dimch_backward": (i32, [C.POINTER(DimchHead), vp, i32, C.c_float, vp, vp, i64, vp, sz, C.POINTER(DimchHeadGrads), i32, vp, sz, vp]),
+    "xmh_head_umoed_bytes": (sz, [i64, i32, C.POINTER(UmoedHead)]),
+    "xmh_head_umoed": (i32, [C.POINTER(UmoedHead), vp, i64, i32, vp, vp, vp, sz, vp]),
+    "xmh_umoed_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
+    "xmh_umoed_loss": (i32, [vp, vp, i64, i32, i32, i32, vp, C.POINTER(UmoedConsts), vp, sz, vp, vp]),
+    "xmh_umoed_loss_grad": (i32, [vp, vp, i64, i32, i32, i32, vp, C.POINTER(UmoedConsts), vp, vp, vp, i32, vp, sz, vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

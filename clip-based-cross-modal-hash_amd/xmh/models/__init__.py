@@ -6,3 +6,4 @@ from .dnph import DNPH  # noqa: F401
 from .dsph import DSPH  # noqa: F401
 from .mith import MITH  # noqa: F401
 from .twdh import TwDH  # noqa: F401
+from .umoed import UMoED, UMoEDObjective  # noqa: F401

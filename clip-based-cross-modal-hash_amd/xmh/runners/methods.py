@@ -453,3 +453,126 @@ class DIMCHTrainer(_MethodTrainer):
                                       "writes it into its %d-wide buffer and fails; evaluation is built for hash_func: tanh"
                                       % (2 * self.output_dim, self.output_dim, self.output_dim))
         return super().valid(epoch, k=k)
+
+
+@registry.register_runner("UMoEDTrainer")
+class UMoEDTrainer(_MethodTrainer):
+    """runners/UMoED/runner.py: the model's encoders return (token logits, code); evaluation reports four mAPs (i->t, t->i, i->i, t->t),
+    keeps a best epoch for each and writes four .mat files with a fusion stream beside the usual keys.  The linear-subspace and tanh codes
+    are quantised by their sign, the pair softmax by its argmax.  The decoder head has no backward here, so ``train_epoch`` raises."""
+
+    loss_type = "l1"                                            # runners/UMoED/runner.py:35: only named in the display line
+    MAP_NAMES = ("i2t", "t2i", "i2i", "t2t")
+
+    def __init__(self, cfg, *a, **k):
+        if k.get("distributed", False):
+            raise NotImplementedError("UMoEDTrainer with distributed=True: the four-mAP evaluation and its .mat files are built for one process")
+        self.hash_func = cfg.model.get("hash_func", "softmax")
+        self.hash_scale = 2 if self.hash_func == "softmax" else 1   # runners/UMoED/runner.py:43-46
+        for name in self.MAP_NAMES:
+            setattr(self, "max_map" + name, 0)
+            setattr(self, "best_epoch_" + name, 0)
+        super().__init__(cfg, *a, **k)
+
+    def build_model(self, cfg_model, output_dim=16, **kwags):
+        """runners/UMoED/runner.py:104-124: as the base class, and the text token count ``dataset.max_word`` handed on"""
+        arch = cfg_model.get("arch", "UMoED")
+        cls = registry.get_model_class(arch)
+        assert cls is not None, "model '%s' is not registered (known: %s)" % (arch, registry.list_models())
+        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num,
+                                     txt_token_size=self.cfg.dataset.get("max_word", 32))
+        if os.path.isfile(self.model_state):
+            self.logger.info("loading model...")
+            self.model.load_state_dict(torch.load(self.model_state, map_location=f"cuda:{self.device}"))
+        self.model.float()
+        self.model.to(self.device)
+        self.logger.info("Building model!")
+        self.logger.info(f"Output dim: {self.output_dim}")
+
+    def compute_loss(self, img_embeds=None, img_hash=None, txt_embeds=None, txt_hash=None, fusion_embeds=None, fusion_hash=None, label=None,
+                     index=None, epoch=0, times=0, global_step=0, **kwags):
+        """runners/UMoED/runner.py:126-134: the objective of one batch (xmh_umoed.hip behind torch.autograd), differentiable with respect
+        to the two logit tensors; the display line needs the training loop's loader and optimiser and is skipped without them."""
+        all_loss, loss_dict = self.model.object_function(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash,
+                                                         fusion_embeds=fusion_embeds, fusion_hash=fusion_hash, labels=label, indexs=index, **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=img_embeds.shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
+    def train_epoch(self, epoch: int):
+        raise NotImplementedError("UMoEDTrainer.train_epoch: the backward of the decoder head is not built (xmh_head_umoed is inference only: "
+                                  "self- and cross-attention, the Soft-MoE routing and the experts have no gradient kernels); the objective "
+                                  "and its gradient are (compute_loss), and valid() / test() evaluate a trained checkpoint")
+
+    def train(self):
+        """runners/UMoED/runner.py:245-251: the reference's loop; with ``is_train: true`` it raises at once in train_epoch"""
+        for epoch in range(self.epochs):
+            self.train_epoch(epoch=epoch)
+            self.valid(epoch, k=self.top_k)
+        self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i2t}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t2i}, "
+                         f"mAP: {self.max_mapt2i}, I-I: {self.best_epoch_i2i}, MAP: {self.max_mapi2i}, T-T: {self.best_epoch_t2t}, MAP: {self.max_mapt2t}")
+
+    def generate_hash(self, image, text, key_padding_mask=None):
+        """runners/UMoED/runner.py:163-165 -> (image_hash, text_hash, fusion_hash); the model's forward leaves the fusion code None"""
+        _, image_hash, _, text_hash, _, fusion_hash = self.model(image, text)
+        return image_hash, text_hash, fusion_hash
+
+    def generate_hashes(self, image, text, key_padding_mask=None):
+        image_hash, text_hash, _ = self.generate_hash(image, text, key_padding_mask)
+        return {"": (image_hash, text_hash)}
+
+    def pack_hash_code(self, code, out, row_index, flags):
+        if self.hash_func == "softmax":
+            R.pack_pair_argmax(code.reshape(code.shape[0], -1), out=out, row_index=row_index)
+        else:
+            R.pack_sign(code, out=out, row_index=row_index, flags=flags)
+
+    def _check_code_width(self):
+        layer = self.model.hash
+        width = (layer.hash_module if layer.fusion else layer.img_token_hash).code_width
+        if width != self.output_dim * self.hash_scale:
+            raise NotImplementedError("UMoEDTrainer: hash_func %s with merge_func mean gives a code %d wide for %d bits (the vocabulary "
+                                      "2^(output_dim / setDim)), which the reference writes into its %d-wide buffer and fails; evaluation is "
+                                      "built for codes of output_dim bits" % (self.hash_func, width, self.output_dim, self.output_dim))
+
+    def get_code(self, data_loader, length: int):
+        """runners/UMoED/runner.py:167-190 -> (image, text, fusion) fp32 [length, K]; the reference allocates the fusion buffer and never
+        fills it (uninitialised memory): here it is all zero"""
+        self._check_code_width()
+        img, txt = super().get_code(data_loader, length)
+        return img, txt, torch.zeros_like(img)
+
+    def _save_codes(self, codes, save_file):
+        """one .mat with the reference's eight keys (:253-268); the four files of an epoch share the unpacked codes, and a second file
+        of the same codes is another name of the first"""
+        from ..utils import matfile
+        memo = self.__dict__.get("_mat_memo")
+        if memo is None or memo[0] is not codes:
+            q_img, q_txt, r_img, r_txt = (t.unpack() for t in codes)
+            memo = self._mat_memo = [codes, (q_img, q_txt, torch.zeros_like(q_img), r_img, r_txt, torch.zeros_like(r_img)), None]
+        if memo[2] is not None and os.path.exists(memo[2]):
+            matfile.link_or_copy(memo[2], save_file)
+            return
+        names = ("q_img", "q_txt", "q_fus", "r_img", "r_txt", "r_fus", "q_l", "r_l")
+        matfile.write_mat5(save_file, dict(zip(names, (*memo[1], self.query_labels, self.retrieval_labels))))
+        memo[2] = save_file
+
+    def valid(self, epoch, k=None):
+        """runners/UMoED/runner.py:192-243: four mAPs through the packed scan, four maxima and best epochs, four .mat files"""
+        assert self.query_loader is not None and self.retrieval_loader is not None
+        self._check_code_width()
+        save_dir = os.path.join(self.save_dir, "mat_files")
+        os.makedirs(save_dir, exist_ok=True)
+        self.logger.info("Valid.")
+        maps, codes = self._evaluate(k)
+        for name, value in zip(self.MAP_NAMES, maps):
+            if getattr(self, "max_map" + name) < value:
+                setattr(self, "best_epoch_" + name, epoch)
+                self._save_codes(codes, os.path.join(save_dir, name + "-best.mat"))
+            setattr(self, "max_map" + name, max(getattr(self, "max_map" + name), value))
+        self._mat_memo = None
+        mAPi2t, mAPt2i, mAPi2i, mAPt2t = maps
+        self.logger.info(f">>>>>> [{epoch}/{self.epochs}], MAP(i->t): {mAPi2t}, MAP(t->i): {mAPt2i}, MAP(t->t): {mAPt2t}, MAP(i->i): {mAPi2i}, "
+                         f"MAX MAP(i->t): {self.max_mapi2t}, epoch: {self.best_epoch_i2t}, MAX MAP(t->i): {self.max_mapt2i}, epoch: {self.best_epoch_t2i}, "
+                         f"MAX MAP(i->i): {self.max_mapi2i}, epoch: {self.best_epoch_i2i}, MAX MAP(t->t): {self.max_mapt2t}, epoch: {self.best_epoch_t2t}, ")
+        return mAPi2t, mAPt2i, mAPi2i, mAPt2t

@@ -1032,6 +1032,79 @@ int xmh_head_dimch_backward(const xmh_dimch_head* h, const float* tokens, int ha
                             const float* d_hash, int64_t B, const void* saved, size_t saved_bytes, const xmh_dimch_head_grads* g,
                             int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * UMoED soft-MoE decoder head, one modality, eval mode (reference models/UMoED/hash/hash_moe.py, hash/block/transformer.py,
+ * hash/block/SoftMoe.py, models/common/hash.py; csrc/xmh_umoed.hip).  d = width, M = setDim learned query rows, S = n_experts * slots:
+ *   mem = tokens [B, T, E], or relu(tokens first_w^T + first_b) [B, T, d] when first_w is given;  x = queries [M, d] repeated over B
+ *   per layer (post-norm):  x = LN1(x + out_proj(MHA(q = k = v = x)));  x = LN2(x + out_proj(MHA(q = x, k = v = mem)))  (no mask)
+ *     h = relu(x lin_w^T + lin_b) [B, M, F]
+ *     moe != 0:  logits = h phi [B, M, S];  D = softmax(logits) over the M rows, Cw = softmax(logits) over the S slots;
+ *                Xs = D^T h [B, S, F];  Ys[b, n, p] = Xs[b, n, p] W_n + bias_n;  x = LN3(x + Cw Ys)
+ *     moe == 0:  x = LN3(x + h lin2_w^T + lin2_b)
+ *   embeds = x cls_w^T + cls_b [B, M, V]
+ *   code: XMH_UMOED_LINEAR_SUBSPACE (merge XMH_UMOED_CONCATENATE): per row the argmax of the V logits (first index on a tie) written
+ *         as log2 V bits, most significant first, 1 -> +1 and 0 -> -1: code [B, M log2 V];
+ *         XMH_UMOED_TANH / XMH_UMOED_SOFTMAX (merge XMH_UMOED_MEAN): tanh, or the softmax over the pairs (2j, 2j + 1), of the mean of
+ *         embeds over M: code [B, V].
+ * All weights are plain fp32 device pointers in the reference's layouts; `layers` is a host array.  Every product is exact fp32
+ * (v_mfma_f32_32x32x2_f32 or fmaf chains) in one fixed summation order: two calls agree to the bit.  No allocation, no host
+ * synchronisation, no float atomics.  16 launches per MoE layer, 12 per plain layer, 2 (3 with a first layer) around them.
+ * Bounds (XMH_ENOTSUP beyond): d / heads == 64; M, T <= 128; E <= 2048; d <= 1024 (the width xmh_layernorm_f32 takes); F <= 4096; S <= 256; V <= 256, a power of two for linear_subspace; B max(M, T) <= 32768, B <= 65535.
+ * Workspace: xmh_head_umoed_bytes(B, T, h) bytes of device memory, 256-byte aligned (0 outside the bounds; XMH_ENOMEM when shorter).
+ * Argument errors are reported before any launch.
+ * ------------------------------------------------------------------------------------------- */
+#define XMH_UMOED_LINEAR_SUBSPACE 0
+#define XMH_UMOED_TANH 1
+#define XMH_UMOED_SOFTMAX 2
+#define XMH_UMOED_CONCATENATE 0
+#define XMH_UMOED_MEAN 1
+typedef struct xmh_umoed_layer {
+    const float *ln1_g, *ln1_b, *sa_in_w /* [3d, d] */, *sa_in_b, *sa_out_w /* [d, d] */, *sa_out_b;
+    const float *ln2_g, *ln2_b, *ca_in_w /* [3d, d] */, *ca_in_b, *ca_out_w /* [d, d] */, *ca_out_b;
+    const float *ln3_g, *ln3_b, *lin_w /* [F, d] */, *lin_b;
+    const float *phi /* [F, n, p] */, *exp_w /* [n, F, d] */, *exp_b /* [n, d] */; /* moe != 0 */
+    const float *lin2_w /* [d, F] */, *lin2_b;                                      /* moe == 0 */
+} xmh_umoed_layer;
+typedef struct xmh_umoed_head {
+    const xmh_umoed_layer* layers; /* host array [n_layers] */
+    int n_layers;
+    const float *first_w /* [d, E] */, *first_b; /* NULL when d == E */
+    const float *queries /* [M, d] */, *cls_w /* [V, d] */, *cls_b;
+    int E, d, heads, F, M, V, n_experts, slots, moe, hash_func, merge;
+    float ln_eps;
+} xmh_umoed_head;
+size_t xmh_head_umoed_bytes(int64_t B, int T, const xmh_umoed_head* h);
+int xmh_head_umoed(const xmh_umoed_head* h, const float* tokens, int64_t B, int T, float* embeds, float* code, void* ws, size_t ws_bytes,
+                   xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * UMoED: the objective of the pairwise / cosine / triplet family (reference models/UMoED/UMoED.py similarity_loss with
+ * distance/__init__.py pairwise_distance) and its gradient.  e_img, e_txt [B, M, V] fp32, lab: xmh_pack_labels of the [B, C] labels.
+ *   x, y = F.normalize (eps 1e-12) of the rows;  a, b = softmax(x / extreme_T), softmax(y / extreme_T) when extreme, else x, y
+ *   D[i][k] = mean_t (1 - max(a[i, t] . b[k, t], 0)): token t of one set meets token t of the other.  D_i2t = D, D_t2i = D^T.
+ *   T(D, m) the weighted triplet term defined above xmh_dimch_loss (one implementation, csrc/xmh_triplet.h), m = token_triplet_margin
+ *   U(u) = mean_b sum_{t < t'} exp(-20 |u[b, t] - u[b, t']|^2) / (M (M - 1) / 2), per set, on the normalised rows; 0 for M = 1.
+ *          Squared distances are sums of squared differences at every distance: identical rows give exactly 0.
+ *   loss = triplet_alpha (T_i2t + T_t2i) / 4 + unif_alpha (U(x) + U(y)) / 3
+ * B <= 512, M <= 128, V <= 256, C <= 127 -- XMH_ENOTSUP outside.  No host synchronisation, no allocation, no float atomics, every sum
+ * in one fixed order (two calls agree to the bit); a row without a label makes the triplet terms NaN, as in the reference.
+ * Workspace: xmh_umoed_loss_ws_bytes(B, M, V, C), 256-byte aligned (0 outside the bounds; XMH_ENOMEM when shorter).
+ * xmh_umoed_loss: 4 launches.  xmh_umoed_loss_grad: 5 launches (it stands alone).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_umoed_consts {
+    int extreme;
+    float extreme_T, token_triplet_margin, triplet_alpha, unif_alpha;
+} xmh_umoed_consts;
+size_t xmh_umoed_loss_ws_bytes(int64_t B, int M, int V, int C);
+/* out8 (device doubles): loss, T_i2t, T_t2i, U(x), U(y), 0, 0, 0.  cst is read on the host. */
+int xmh_umoed_loss(const float* e_img, const float* e_txt, int64_t B, int M, int V, int C, const uint32_t* lab, const xmh_umoed_consts* cst,
+                   void* ws, size_t ws_bytes, double* out8, xmh_stream_t stream);
+/* d loss times upstream[0] (a device float; NULL = 1) -> g_img, g_txt [B, M, V]: written, or added to when accumulate != 0.  Either may
+ * be NULL: that gradient is not formed.  The backward of the softmax, of the normalisation and of the clamp is included. */
+int xmh_umoed_loss_grad(const float* e_img, const float* e_txt, int64_t B, int M, int V, int C, const uint32_t* lab,
+                        const xmh_umoed_consts* cst, const float* upstream, float* g_img, float* g_txt, int accumulate, void* ws,
+                        size_t ws_bytes, xmh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
