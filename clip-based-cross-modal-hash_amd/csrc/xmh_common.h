@@ -22,6 +22,14 @@ inline int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// What the argument checks of an entry point with a caller-owned workspace end with: `need` bytes (what `sizer` returns for these
+// shapes) from a 256-byte aligned address.  short_code: the status the entry gives a short workspace.
+inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need, const char* sizer, int short_code) {
+    if (ws_bytes < need) return fail(short_code, "%s: workspace of %zu bytes < %zu (%s)", who, ws_bytes, need, sizer);
+    if (reinterpret_cast<uintptr_t>(ws) & 255u) return fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
+    return XMH_OK;
+}
+
 // Launch check: HIP reports bad configs at launch; asynchronous faults surface at the caller's sync.
 #define XMH_LAUNCH_CHECK(what)                                                                        \
     do {                                                                                              \

@@ -1,6 +1,8 @@
-// Device helpers shared by the training kernels (xmh_hyp, xmh_mith_loss, xmh_head_grad, xmh_block_grad), xmh_encode and xmh_dense, and
-// the workspace carver of the host entry points: wave and block reductions, the column kernels' group_sum.  The scan, top-k and GEMM
-// kernels keep their own hand-scheduled idioms; xmh_loss.hip keeps its block_sum, whose result lives on thread 0 only.
+// Device helpers shared by the training kernels (xmh_hyp, xmh_dnph, xmh_dimch, xmh_umoed, xmh_twdh, xmh_mith_loss, xmh_head_grad,
+// xmh_block_grad, xmh_optim), xmh_encode, xmh_forward and xmh_dense, and the workspace carver of the host entry points: wave and block reductions (sum,
+// maximum, log-sum-exp), the column kernels' group_sum.  xmh_rows.h (row normalisation) and xmh_triplet.h (the triplet term) build
+// on it.  The scan, top-k and GEMM kernels keep their own hand-scheduled idioms; xmh_loss.hip keeps its block_sum, whose result
+// lives on thread 0 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -49,6 +51,38 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
     for (int w = 1; w < kWaves; ++w) s += sh[w];
     __syncthreads();
     return s;
+}
+
+// Block maximum, valid on every thread.  fmaxf drops a NaN; every caller sums exp(v - max) afterwards, where it comes back.
+template <int kWaves>
+__device__ __forceinline__ float block_max(float v, float* sh) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float m = sh[0];
+    for (int w = 1; w < kWaves; ++w) m = fmaxf(m, sh[w]);
+    __syncthreads();
+    return m;
+}
+
+// sum_i exp(v[i] - max) over n values the block can read and the maximum in *mx; valid on every thread.  fsh, dsh: kWaves elements.
+template <int kWaves>
+__device__ __forceinline__ double block_exp_sum(const float* v, int n, float* fsh, double* dsh, float* mx) {
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += kWaves * 64) m = fmaxf(m, v[i]);
+    m = block_max<kWaves>(m, fsh);
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kWaves * 64) s += (double)expf(v[i] - m);
+    *mx = m;
+    return block_sum<kWaves>(s, dsh);
+}
+
+// log sum_i exp(v[i]), the maximum subtracted; valid on every thread
+template <int kWaves>
+__device__ __forceinline__ float block_lse(const float* v, int n, float* fsh, double* dsh) {
+    float m;
+    const double s = block_exp_sum<kWaves>(v, n, fsh, dsh, &m);
+    return m + logf((float)s);
 }
 
 // Column kernels (kCols adjacent columns x kGroups interleaved row groups per block): fixed-order sum of the row groups' partials of

@@ -38,7 +38,7 @@
 #include <math.h>
 
 #include "xmh_common.h"
-#include "xmh_device.h"
+#include "xmh_rows.h"
 #include "xmh_triplet.h"
 
 namespace {
@@ -118,7 +118,7 @@ struct Grads {
 
 using xmh::wave_sum;
 
-__device__ __forceinline__ float inv_norm(float n, float eps) { return 1.0f / (n < eps ? eps : n); }   // a NaN norm stays NaN
+using xmh::inv_norm;
 using trip::clamp0;                                                                                    // torch.clamp(v, 0): NaN stays
 
 // ---- preparation -----------------------------------------------------------------------------------------------------------------------
@@ -675,10 +675,7 @@ int check_args(const char* who, const float* e_img, const float* e_txt, const fl
         return xmh::fail(XMH_EINVAL, "%s: temperature %g and temperature_txt_scale %g must be positive", who, (double)cst->temperature,
                          (double)cst->temperature_txt_scale);
     if (cst->mode <= XMH_DIMCH_CHAMFER && !(cst->denominator != 0.0f)) return xmh::fail(XMH_EINVAL, "%s: denominator 0", who);
-    const size_t need = ws_layout(B, M, K, nullptr, nullptr);
-    if (ws_bytes < need) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes < %zu (xmh_dimch_loss_ws_bytes)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return XMH_OK;
+    return xmh::check_workspace(who, ws, ws_bytes, ws_layout(B, M, K, nullptr, nullptr), "xmh_dimch_loss_ws_bytes", XMH_ENOMEM);
 }
 
 Args make_args(const float* e_img, const float* e_txt, const float* h_img, const float* h_txt, int64_t B, int M, int K, int Kh, int C,

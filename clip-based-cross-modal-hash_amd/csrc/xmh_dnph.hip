@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "xmh_common.h"
-#include "xmh_device.h"
+#include "xmh_rows.h"
 
 namespace {
 
@@ -75,50 +75,10 @@ struct Args {
     float mrg, noise_alpha;
 };
 
+using xmh::has_label;
+using xmh::inv_norm;
+using xmh::wave_norm;
 using xmh::wave_sum;
-
-__device__ __forceinline__ float inv_norm(float n) { return 1.0f / (n < kEps ? kEps : n); }   // a NaN norm stays NaN (fmaxf drops it)
-
-__device__ __forceinline__ bool has_label(const uint32_t* lab, int Lw, int row, int c) {
-    return (lab[(int64_t)row * Lw + (c >> 5)] >> (c & 31)) & 1u;
-}
-
-// Block maximum, valid on every thread.  fmaxf drops a NaN; every caller sums exp(v - max) afterwards, where it comes back.
-__device__ __forceinline__ float block_max(float v, float* sh) {
-    v = xmh::wave_max(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = sh[0];
-    for (int w = 1; w < kWaves; ++w) m = fmaxf(m, sh[w]);
-    __syncthreads();
-    return m;
-}
-
-// sum_i exp(v[i] - max) over n values the block can read (n <= kMaxC) and the maximum in *mx; valid on every thread
-__device__ __forceinline__ double block_exp_sum(const float* v, int n, float* fsh, double* dsh, float* mx) {
-    float m = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += kThreads) m = fmaxf(m, v[i]);
-    m = block_max(m, fsh);
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += kThreads) s += (double)expf(v[i] - m);
-    *mx = m;
-    return xmh::block_sum<kWaves>(s, dsh);
-}
-
-// log sum_i exp(v[i]), the maximum subtracted; valid on every thread
-__device__ __forceinline__ float block_lse(const float* v, int n, float* fsh, double* dsh) {
-    float m;
-    const double s = block_exp_sum(v, n, fsh, dsh, &m);
-    return m + logf((float)s);
-}
-
-// |v|^2 of a row the wave can read, every lane in the same order wherever it is called
-__device__ __forceinline__ float wave_norm(const float* v, int K) {
-    const int lane = threadIdx.x & 63;
-    float s = 0.0f;
-    for (int k = lane; k < K; k += 64) s = fmaf(v[k], v[k], s);
-    return sqrtf(wave_sum(s));
-}
 
 // sum_k (u[k] - pc[k] ip)^2 by one wave: u the normalised code row, pc the raw proxy.  The products are rounded before the
 // subtraction (no contraction into an fma), so a code that equals its proxy gives an exact 0 here and in the gradient.
@@ -149,12 +109,12 @@ __device__ __forceinline__ float load_row_dists(const Args& a, int n, float* vs,
     for (int k = threadIdx.x; k < a.K; k += kThreads) vs[k] = row[k];
     __syncthreads();
     const float nv = wave_norm(vs, a.K);
-    const float iv = inv_norm(nv);
+    const float iv = inv_norm(nv, kEps);
     for (int k = threadIdx.x; k < a.K; k += kThreads) us[k] = __fmul_rn(vs[k], iv);
     __syncthreads();
     for (int c = wave; c < a.C; c += kWaves) {
         const float* pc = a.P + (int64_t)c * a.K;
-        const float d = wave_dist(us, pc, inv_norm(wave_norm(pc, a.K)), a.K);
+        const float d = wave_dist(us, pc, inv_norm(wave_norm(pc, a.K), kEps), a.K);
         if (lane == 0) ds[c] = d + (has_label(a.lab, a.Lw, b, c) ? a.mrg : 0.0f);
     }
     __syncthreads();
@@ -184,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_rows(Args a, WsView ws) {
     const float nv = load_row_dists(a, n, vs, us, ds);
     for (int c = threadIdx.x; c < a.C; c += kThreads) ds[c] = -ds[c];
     __syncthreads();
-    const float lse = block_lse(ds, a.C, fsh, dsh);
+    const float lse = xmh::block_lse<kWaves>(ds, a.C, fsh, dsh);
     const uint32_t mine = lane < a.Lw ? a.lab[(int64_t)b * a.Lw + lane] : 0u;
     const int npos = wave_sum((int)__popc(mine)), low = lowest_label(mine), t = low < a.C ? low : 0;   // bits past C are never set
     if (threadIdx.x == 0) {
@@ -203,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_rows(Args a, WsView ws) {
     }
     pl = xmh::block_sum<kWaves>(pl, dsh);
     const float* pr = a.p[m] + (int64_t)b * a.Cp;
-    const float ce = block_lse(pr, a.Cp, fsh, dsh) - pr[t];
+    const float ce = xmh::block_lse<kWaves>(pr, a.Cp, fsh, dsh) - pr[t];
     double nz = 0.0;
     if (a.noise[m]) {
         const float* nr = a.noise[m] + (int64_t)b * a.K;
@@ -240,31 +200,6 @@ __global__ __launch_bounds__(kThreads) void k_dnph_finalize(int B, float noise_a
     }
 }
 
-// dv of F.normalize for one row v (in LDS) with du in the thread's column slots, plus `extra` (a gradient that reaches v directly),
-// written / accumulated times g
-__device__ __forceinline__ void normalize_backward_store(const float* v, float nv, const float (&du)[kSlots], const float* extra, float ex, int K,
-                                                         float g, float* __restrict__ out, int accumulate, float* sh) {
-    const float iv = inv_norm(nv);
-    float vd = 0.0f;
-#pragma unroll
-    for (int r = 0; r < kSlots; ++r) {
-        const int k = threadIdx.x + r * kThreads;
-        if (k < K) vd = fmaf(v[k], du[r], vd);
-    }
-    vd = xmh::block_sum<kWaves>(vd, sh);
-    const float s = nv < kEps ? 0.0f : vd * iv;                  // u . du; a clamped row passes du / eps only, a NaN norm stays NaN
-#pragma unroll
-    for (int r = 0; r < kSlots; ++r) {
-        const int k = threadIdx.x + r * kThreads;
-        if (k < K) {
-            float d = (du[r] - v[k] * iv * s) * iv;
-            if (extra) d += ex * extra[k];
-            d *= g;
-            out[k] = accumulate ? out[k] + d : d;
-        }
-    }
-}
-
 struct Grads {
     float* f[2];              // grad_f_img, grad_f_txt
     float* p[2];              // grad_p_img, grad_p_txt
@@ -292,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
             // exp(p - max) / sum, not exp(p - lse): lse carries the rounding of the maximum's size (half an ulp of 375 is 1.5e-5
             // of every softmax entry when the logits are that large), the quotient does not
             float mx;
-            const float sum = (float)block_exp_sum(pr, a.Cp, fsh, dsh, &mx);
+            const float sum = (float)xmh::block_exp_sum<kWaves>(pr, a.Cp, fsh, dsh, &mx);
             const int t = ws.cnt[2 * b + 1];
             for (int c = threadIdx.x; c < a.Cp; c += kThreads) {
                 const float d = g * ((expf(pr[c] - mx) / sum - (c == t ? 1.0f : 0.0f)) / (float)a.B);
@@ -309,7 +244,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
         for (int c = threadIdx.x; c < a.C; c += kThreads) {
             const float l = has_label(a.lab, a.Lw, b, c) ? 1.0f : 0.0f;
             ds[c] = (l - L * expf(-ds[c] - lse)) * w2b;          // 0 * NaN stays NaN, as in log_softmax's backward
-            ips[c] = inv_norm(ws.np[c]);
+            ips[c] = inv_norm(ws.np[c], kEps);
         }
         __syncthreads();
         for (int c = 0; c < a.C; ++c) {
@@ -325,7 +260,8 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
 #pragma unroll
         for (int r = 0; r < kSlots; ++r) du[r] = (float)acc[r];
         const float* nr = a.noise[m] ? a.noise[m] + (int64_t)b * a.K : nullptr;
-        normalize_backward_store(vs, nv, du, nr, -a.noise_alpha / (float)a.B, a.K, g, gr.f[m] + (int64_t)b * a.K, accumulate, fsh);
+        xmh::normalize_backward_store<kThreads, kSlots, true>(vs, nv, kEps, du, a.K, g, gr.f[m] + (int64_t)b * a.K, accumulate, fsh, nr,
+                                                              -a.noise_alpha / (float)a.B);
     } else {
         if (!gr.P) return;
         const int c = blockIdx.x - 2 * a.B;
@@ -334,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
         float* wn = qs + a.K;                                    // [kChunk] d p_loss / d D[n][c]
         float* in = wn + kChunk;                                 // [kChunk] 1 / |f_n|
         for (int k = threadIdx.x; k < a.K; k += kThreads) ps[k] = a.P[(int64_t)c * a.K + k];
-        const float np = ws.np[c], ip = inv_norm(np);
+        const float np = ws.np[c], ip = inv_norm(np, kEps);
         __syncthreads();
         for (int k = threadIdx.x; k < a.K; k += kThreads) qs[k] = __fmul_rn(ps[k], ip);
         __syncthreads();
@@ -343,7 +279,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
             for (int ii = wave; ii < cnt; ii += kWaves) {
                 const int n = n0 + ii, m = n >= a.B, b = n - m * a.B;
                 const float* row = a.f[m] + (int64_t)b * a.K;
-                const float iv = inv_norm(ws.nf[n]);
+                const float iv = inv_norm(ws.nf[n], kEps);
                 float d = 0.0f;                                  // D[n][c] in the lane order of wave_dist
                 for (int k = lane; k < a.K; k += 64) {
                     const float df = __fmul_rn(row[k], iv) - qs[k];
@@ -372,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void k_dnph_grad(Args a, WsView ws, const
         }
 #pragma unroll
         for (int r = 0; r < kSlots; ++r) du[r] = (float)acc[r];
-        normalize_backward_store(ps, np, du, nullptr, 0.0f, a.K, g, gr.P + (int64_t)c * a.K, accumulate, fsh);
+        xmh::normalize_backward_store<kThreads>(ps, np, kEps, du, a.K, g, gr.P + (int64_t)c * a.K, accumulate, fsh);
     }
 }
 
@@ -385,10 +321,7 @@ int check_args(const char* who, const float* f_img, const float* f_txt, const fl
         return xmh::fail(XMH_ENOTSUP, "%s: B=%lld K=%d C=%d Cp=%d outside B <= %d, K <= %d, C <= %d, Cp <= %d", who, (long long)B, K, C, Cp, kMaxB,
                          kMaxK, kMaxC, kMaxC);
     if (!f_img || !f_txt || !p_img || !p_txt || !P || !lab || !ws) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
-    const size_t need = ws_layout(B, C, nullptr, nullptr);
-    if (ws_bytes < need) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes < %zu (xmh_dnph_loss_ws_bytes)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return XMH_OK;
+    return xmh::check_workspace(who, ws, ws_bytes, ws_layout(B, C, nullptr, nullptr), "xmh_dnph_loss_ws_bytes", XMH_ENOMEM);
 }
 
 Args make_args(const float* f_img, const float* f_txt, const float* p_img, const float* p_txt, const float* P, int64_t B, int K, int C, int Cp,

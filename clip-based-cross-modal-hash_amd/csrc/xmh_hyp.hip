@@ -26,7 +26,7 @@
 // whose norm is not finite therefore turns the x and y gradients of every row of M NaN (0 * NaN), here as there.
 // Bound: B = 100, K = 16..128, C = 80 (COCO, configs[4]) is a few tens of KB of L2-resident operands: launch-latency bound.
 #include "xmh_common.h"
-#include "xmh_device.h"
+#include "xmh_rows.h"
 
 namespace {
 
@@ -57,19 +57,16 @@ __host__ __device__ inline size_t ws_layout(int64_t B, int C, void* base, WsView
     return ar.used;
 }
 
+using xmh::has_label;
+using xmh::inv_norm;
+using xmh::wave_norm;
 using xmh::wave_sum;
-
-__device__ __forceinline__ float inv_norm(float n) { return 1.0f / (n < kEps ? kEps : n); }   // a NaN norm stays NaN (fmaxf drops it)
 
 // relu(v) as F.relu forms it: NaN stays NaN
 __device__ __forceinline__ float hinge(float v) { return isnan(v) ? v : fmaxf(v, 0.0f); }
 
 // relu'(sim - thr) * w, with a NaN similarity handed on as the weight: the reference's backward ends in NaN wherever it enters
 __device__ __forceinline__ float hinge_weight(float sim, float thr, float w) { return sim > thr ? w : (isnan(sim) ? sim : 0.0f); }
-
-__device__ __forceinline__ bool has_label(const uint32_t* lab, int Lw, int row, int c) {
-    return (lab[(int64_t)row * Lw + (c >> 5)] >> (c & 31)) & 1u;
-}
 
 // Row j (lanes < Lw hold its label words in w) against the row whose words are `mine` (itself in M).  in_m: j is in M as well (>= 2
 // labels).  disjoint: it is then a regulariser partner, sharing no class.  Wave-uniform.
@@ -94,10 +91,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
     if ((int)blockIdx.x >= B) {
         const int c = blockIdx.x - B;
         if (wave == 0) {
-            float s = 0.0f;
-            for (int k = lane; k < K; k += 64) s = fmaf(P[(int64_t)c * K + k], P[(int64_t)c * K + k], s);
-            s = wave_sum(s);
-            if (lane == 0) ws.np[c] = sqrtf(s);
+            const float n = wave_norm(P + (int64_t)c * K, K);
+            if (lane == 0) ws.np[c] = n;
         }
         return;
     }
@@ -109,13 +104,8 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
         ys[k] = y[(int64_t)i * K + k];
     }
     __syncthreads();
-    float sx = 0.0f, sy = 0.0f;
-    for (int k = lane; k < K; k += 64) {
-        sx = fmaf(xs[k], xs[k], sx);
-        sy = fmaf(ys[k], ys[k], sy);
-    }
-    const float nxi = sqrtf(wave_sum(sx)), nyi = sqrtf(wave_sum(sy));
-    const float ix = inv_norm(nxi), iy = inv_norm(nyi);
+    const float nxi = wave_norm(xs, K), nyi = wave_norm(ys, K);
+    const float ix = inv_norm(nxi, kEps), iy = inv_norm(nyi, kEps);
     const uint32_t mine = lane < Lw ? lab[(int64_t)i * Lw + lane] : 0u;
     const int npos = wave_sum((int)__popc(mine));
 
@@ -132,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
             }
             d = wave_sum(d);
             dt = wave_sum(dt);
-            const float ip = inv_norm(sqrtf(wave_sum(pp)));
+            const float ip = inv_norm(sqrtf(wave_sum(pp)), kEps);
             const float cs = d * ix * ip, ct = dt * iy * ip;
             if (has_label(lab, Lw, i, c)) {
                 acc[0] += (double)(1.0f - cs);
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_rows(const float* __restrict__
                     nx2 = fmaf(a, a, nx2);
                     ny2 = fmaf(b, b, ny2);
                 }
-                const float ixj = inv_norm(sqrtf(wave_sum(nx2))), iyj = inv_norm(sqrtf(wave_sum(ny2)));
+                const float ixj = inv_norm(sqrtf(wave_sum(nx2)), kEps), iyj = inv_norm(sqrtf(wave_sum(ny2)), kEps);
                 acc[4] += (double)hinge(wave_sum(dxx) * ix * ixj - thr);
                 acc[5] += (double)hinge(wave_sum(dyy) * iy * iyj - thr);
                 acc[6] += (double)hinge(wave_sum(dxy) * ix * iyj - thr);
@@ -215,28 +205,6 @@ __global__ __launch_bounds__(kThreads) void k_hyp_finalize(int B, int C, float a
     }
 }
 
-// dv of F.normalize for one row v (in LDS) with du in the thread's column slots, then written / accumulated times g
-__device__ __forceinline__ void normalize_backward_store(const float* v, float nv, const float (&du)[kSlots], int K, float g, float* __restrict__ out,
-                                                         int accumulate, float* sh) {
-    const float iv = inv_norm(nv);
-    float vd = 0.0f;
-#pragma unroll
-    for (int r = 0; r < kSlots; ++r) {
-        const int k = threadIdx.x + r * kThreads;
-        if (k < K) vd = fmaf(v[k], du[r], vd);
-    }
-    vd = xmh::block_sum<kWaves>(vd, sh);
-    const float s = nv < kEps ? 0.0f : vd * iv;                  // u . du; a clamped row passes du / eps only, a NaN norm stays NaN
-#pragma unroll
-    for (int r = 0; r < kSlots; ++r) {
-        const int k = threadIdx.x + r * kThreads;
-        if (k < K) {
-            const float d = g * ((du[r] - v[k] * iv * s) * iv);
-            out[k] = accumulate ? out[k] + d : d;
-        }
-    }
-}
-
 // Blocks [0, B): grad_x[i], grad_y[i].  Blocks [B, B + C): grad_P[c].  The global counts come from k_hyp_rows<false>.
 __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ P,
                                                        int B, int K, int C, const uint32_t* __restrict__ lab, int Lw, float thr, float alpha,
@@ -273,10 +241,10 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
             xs[k] = x[(int64_t)i * K + k];
             ys[k] = y[(int64_t)i * K + k];
         }
-        const float ix = inv_norm(ws.nx[i]), iy = inv_norm(ws.ny[i]);
+        const float ix = inv_norm(ws.nx[i], kEps), iy = inv_norm(ws.ny[i], kEps);
         __syncthreads();
         for (int c = wave; c < C; c += kWaves) {
-            const float ip = inv_norm(ws.np[c]);
+            const float ip = inv_norm(ws.np[c], kEps);
             float a = wpos * ip, b = wpos * ip;
             if (!has_label(lab, Lw, i, c)) {
                 const float* pc = P + (int64_t)c * K;
@@ -339,7 +307,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                             dxy = fmaf(xs[k], b, dxy);
                             dyx = fmaf(a, ys[k], dyx);               // x_j . y_i, the order the forward forms it for row j
                         }
-                        const float ixj = inv_norm(ws.nx[j]), iyj = inv_norm(ws.ny[j]);
+                        const float ixj = inv_norm(ws.nx[j], kEps), iyj = inv_norm(ws.ny[j], kEps);
                         // x-x and y-y: the pair masks are symmetric, so row i collects both (i, j) and (j, i)
                         c0 = hinge_weight(wave_sum(dxx) * ix * ixj, thr, 2.0f * wreg * ixj);   // x_j into d/dx_i
                         c1 = hinge_weight(wave_sum(dxy) * ix * iyj, thr, wreg * iyj);          // y_j into d/dx_i (x-y term, i first)
@@ -382,21 +350,21 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
                 __syncthreads();
             }
         }
-        normalize_backward_store(xs, ws.nx[i], ax, K, g, gx + (int64_t)i * K, accumulate, fsh);
-        normalize_backward_store(ys, ws.ny[i], ay, K, g, gy + (int64_t)i * K, accumulate, fsh);
+        xmh::normalize_backward_store<kThreads>(xs, ws.nx[i], kEps, ax, K, g, gx + (int64_t)i * K, accumulate, fsh);
+        xmh::normalize_backward_store<kThreads>(ys, ws.ny[i], kEps, ay, K, g, gy + (int64_t)i * K, accumulate, fsh);
     } else {
         const int c = blockIdx.x - B;
         float* ps = smem;                                        // P_c
         float* wx = ps + K;                                      // [kChunk] weight of x_i in d/dP_c
         float* wy = wx + kChunk;                                 // [kChunk] weight of y_i
         for (int k = threadIdx.x; k < K; k += kThreads) ps[k] = P[(int64_t)c * K + k];
-        const float ip = inv_norm(ws.np[c]);
+        const float ip = inv_norm(ws.np[c], kEps);
         __syncthreads();
         for (int i0 = 0; i0 < B; i0 += kChunk) {
             const int n = min(kChunk, B - i0);
             for (int ii = wave; ii < n; ii += kWaves) {
                 const int i = i0 + ii;
-                const float ixi = inv_norm(ws.nx[i]), iyi = inv_norm(ws.ny[i]);
+                const float ixi = inv_norm(ws.nx[i], kEps), iyi = inv_norm(ws.ny[i], kEps);
                 float a = wpos * ixi, b = wpos * iyi;
                 if (!has_label(lab, Lw, i, c)) {
                     const float* xi = x + (int64_t)i * K;
@@ -429,7 +397,7 @@ __global__ __launch_bounds__(kThreads) void k_hyp_grad(const float* __restrict__
             }
             __syncthreads();
         }
-        normalize_backward_store(ps, ws.np[c], ax, K, g, gP + (int64_t)c * K, accumulate, fsh);
+        xmh::normalize_backward_store<kThreads>(ps, ws.np[c], kEps, ax, K, g, gP + (int64_t)c * K, accumulate, fsh);
     }
 }
 
@@ -440,10 +408,7 @@ int check_args(const char* who, const float* x, const float* y, const float* P, 
     if (B > kMaxB || K > kMaxK || C > kMaxC)
         return xmh::fail(XMH_ENOTSUP, "%s: B=%lld K=%d C=%d outside B <= %d, K <= %d, C <= %d", who, (long long)B, K, C, kMaxB, kMaxK, kMaxC);
     if (!x || !y || !P || !lab || !ws) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
-    const size_t need = ws_layout(B, C, nullptr, nullptr);
-    if (ws_bytes < need) return xmh::fail(XMH_EINVAL, "%s: workspace of %zu bytes < %zu (xmh_hyp_loss_ws_bytes)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return XMH_OK;
+    return xmh::check_workspace(who, ws, ws_bytes, ws_layout(B, C, nullptr, nullptr), "xmh_hyp_loss_ws_bytes", XMH_EINVAL);
 }
 
 }  // namespace

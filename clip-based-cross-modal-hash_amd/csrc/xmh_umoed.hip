@@ -38,7 +38,7 @@
 #include <math.h>
 
 #include "xmh_common.h"
-#include "xmh_device.h"
+#include "xmh_rows.h"
 #include "xmh_triplet.h"
 
 namespace {
@@ -374,9 +374,7 @@ extern "C" int xmh_head_umoed(const xmh_umoed_head* h, const float* tokens, int6
         if (!common || (h->moe ? !(y.phi && y.exp_w && y.exp_b) : !(y.lin2_w && y.lin2_b)))
             return xmh::fail(XMH_EINVAL, "%s: null pointer in layer %d", who, l);
     }
-    const size_t need = head_layout(B, T, h, nullptr, nullptr);
-    if (ws_bytes < need) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes < %zu (xmh_head_umoed_bytes)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
+    XMH_TRY(xmh::check_workspace(who, ws, ws_bytes, head_layout(B, T, h, nullptr, nullptr), "xmh_head_umoed_bytes", XMH_ENOMEM));
     HeadWs w;
     head_layout(B, T, h, ws, &w);
     hipStream_t st = xmh::as_stream(stream);
@@ -491,7 +489,7 @@ struct LossArgs {
     xmh_umoed_consts c;
 };
 
-__device__ __forceinline__ float inv_norm(float n, float eps) { return 1.0f / (n < eps ? eps : n); }   // a NaN norm stays NaN
+using xmh::inv_norm;
 using trip::clamp0;
 
 // One wave per row of [0, 2N): the normalised row, its norm, and softmax(row / T) when extreme.  V <= 256: four elements per lane.
@@ -733,10 +731,7 @@ int check_loss(const char* who, const float* e_img, const float* e_txt, int64_t 
                          kMaxV, kMaxC);
     if (!e_img || !e_txt || !lab || !cst || !ws) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
     if (cst->extreme && !(cst->extreme_T > 0.0f)) return xmh::fail(XMH_EINVAL, "%s: extreme_T %g must be positive", who, (double)cst->extreme_T);
-    const size_t need = loss_layout(B, M, V, 1, nullptr, nullptr);
-    if (ws_bytes < need) return xmh::fail(XMH_ENOMEM, "%s: workspace of %zu bytes < %zu (xmh_umoed_loss_ws_bytes)", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255u) return xmh::fail(XMH_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return XMH_OK;
+    return xmh::check_workspace(who, ws, ws_bytes, loss_layout(B, M, V, 1, nullptr, nullptr), "xmh_umoed_loss_ws_bytes", XMH_ENOMEM);
 }
 
 LossArgs make_loss_args(const float* e_img, const float* e_txt, int64_t B, int M, int V, int C, const uint32_t* lab, const xmh_umoed_consts* cst) {

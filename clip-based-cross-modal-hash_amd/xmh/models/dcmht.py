@@ -13,6 +13,7 @@ from .._lib import check, current_stream, lib, ptr
 from ..common.register import registry
 from .base import BaseModel
 from .heads import DCMHTHashLayer
+from .objective import need_cuda
 
 
 @registry.register_model("DCMHT")
@@ -35,8 +36,7 @@ class DCMHT(BaseModel):
     # ---- loss (reference :72-155) ---------------------------------------------------------------------------------------------
     @staticmethod
     def _codes(x):
-        if not x.is_cuda:
-            raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % x.device)
+        need_cuda(x)
         return x.detach().float().reshape(x.shape[0], -1).contiguous()
 
     def _branch(self):

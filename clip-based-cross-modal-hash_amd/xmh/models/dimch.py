@@ -22,6 +22,7 @@ from .._lib import check, current_stream, lib, ptr, workspace
 from ..common.register import registry
 from .base import BaseModel
 from .heads import _DRAW, _param
+from .objective import Objective, Spec, need_cuda
 
 MODES = ("smooth_chamfer", "chamfer", "max", "avg")          # XMH_DIMCH_SMOOTH_CHAMFER .. XMH_DIMCH_AVG
 HASH_FUNCS = ("tanh", "softmax")                             # XMH_DIMCH_TANH, XMH_DIMCH_SOFTMAX
@@ -43,42 +44,19 @@ def mode_index(mode):
     raise ValueError("DIMCH distance mode %r is none of %s" % (mode, ", ".join(MODES)))
 
 
-class _Objective(torch.autograd.Function):
-    """forward = xmh_dimch_loss -> fp32 [9], backward = xmh_dimch_loss_grad (all four gradients, one call; only element 0 carries one)"""
+def _pack(consts, aux, ts):
+    e1, e2, h1, h2 = ts
+    B, M, K = e1.shape
+    Kh = h1.shape[1]
+    cst, C_ = consts
+    return (B, M, K, Kh, C_), (ptr(e1), ptr(e2), ptr(h1), ptr(h2), B, M, K, Kh, C_, ptr(aux[0]), C.byref(cst))
 
-    @staticmethod
-    def _args(cst, lab, C_, e1, e2, h1, h2):
-        B, M, K = e1.shape
-        Kh = h1.shape[1]
-        nbytes = lib.xmh_dimch_loss_ws_bytes(B, M, K, C_)
-        if nbytes == 0 or Kh > 256:
-            raise RuntimeError("DIMCH objective: B=%d M=%d K=%d Kh=%d C=%d outside B <= 512, M <= 64, K, Kh <= 256, C <= 127" % (B, M, K, Kh, C_))
-        ws = workspace(nbytes, e1.device)
-        return (ptr(e1), ptr(e2), ptr(h1), ptr(h2), B, M, K, Kh, C_, ptr(lab), C.byref(cst)), ws
 
-    @staticmethod
-    def forward(ctx, cst, lab, C_, *inputs):
-        ts = [t.detach().float().contiguous() for t in inputs]
-        args, ws = _Objective._args(cst, lab, C_, *ts)
-        out = torch.empty(12, dtype=torch.float64, device=ts[0].device)
-        check(lib.xmh_dimch_loss(*args, ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_dimch_loss")
-        ctx.cst, ctx.C_ = cst, C_
-        ctx.meta = [(t.shape, t.dtype) for t in inputs]
-        ctx.save_for_backward(lab, *ts)
-        return out[:9].float()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable: fail loudly on double backward
-    def backward(ctx, g):
-        lab, *ts = ctx.saved_tensors
-        args, ws = _Objective._args(ctx.cst, lab, ctx.C_, *ts)
-        up = g.detach().float()[:1].contiguous()      # only element 0 (the loss) carries a gradient
-        need = ctx.needs_input_grad[3:]
-        grads = [torch.empty_like(t) if nd else None for t, nd in zip(ts, need)]
-        check(lib.xmh_dimch_loss_grad(*args, ptr(up), *[ptr(t) for t in grads], 0, ptr(ws), ws.numel(), current_stream()),
-              "xmh_dimch_loss_grad")
-        grads = [None if t is None else t.reshape(s).to(d) for t, (s, d) in zip(grads, ctx.meta)]
-        return (None, None, None, *grads)
+# forward = xmh_dimch_loss -> fp32 [9], backward = xmh_dimch_loss_grad (all four gradients, one call; only element 0 carries one).
+# The codes' width does not enter the workspace; its bound is the embeddings'.
+_DIMCH = Spec(lib.xmh_dimch_loss, lib.xmh_dimch_loss_grad, _pack,
+              lambda B, M, K, Kh, C_: 0 if Kh > 256 else lib.xmh_dimch_loss_ws_bytes(B, M, K, C_),
+              "DIMCH objective: B=%d M=%d K=%d Kh=%d C=%d outside B <= 512, M <= 64, K, Kh <= 256, C <= 127", out_len=12, terms=9)
 
 
 class DIMCHObjective(nn.Module):
@@ -109,9 +87,7 @@ class DIMCHObjective(nn.Module):
 
     def terms(self, img_embeds, img_hash, txt_embeds, txt_hash, labels):
         """-> fp32 [9] on the device (TERMS); element 0 carries the gradient"""
-        for t in (img_embeds, img_hash, txt_embeds, txt_hash):
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        need_cuda(img_embeds, img_hash, txt_embeds, txt_hash)
         labels = torch.as_tensor(labels)
         B = img_embeds.shape[0]
         if img_embeds.dim() != 3 or txt_embeds.shape != img_embeds.shape or img_hash.dim() != 2 or txt_hash.shape != img_hash.shape \
@@ -120,7 +96,7 @@ class DIMCHObjective(nn.Module):
                                % (tuple(img_embeds.shape), tuple(txt_embeds.shape), tuple(img_hash.shape), tuple(txt_hash.shape),
                                   tuple(labels.shape)))
         lab = R.pack_labels((labels == 1).to(torch.uint8).to(img_embeds.device))
-        return _Objective.apply(self.consts, lab, labels.shape[1], img_embeds, txt_embeds, img_hash, txt_hash)
+        return Objective.apply(_DIMCH, (self.consts, labels.shape[1]), (lab,), img_embeds, txt_embeds, img_hash, txt_hash)
 
     def forward(self, img_embeds, img_hash, txt_embeds, txt_hash, labels=None):
         """reference :152-242 -- (loss, loss_dict); without labels every sample is its own class (object_function, :237-242)"""

@@ -18,10 +18,11 @@ import torch
 import torch.nn as nn
 
 from .. import retrieval as R
-from .._lib import check, current_stream, lib, ptr, workspace
+from .._lib import check, lib, ptr
 from ..common.register import registry
 from .base import BaseModel
 from .heads import DNPHHashLayer
+from .objective import Objective, Spec, need_cuda
 
 
 def assign_min_cost(cost):
@@ -69,9 +70,7 @@ class DNPHLoss(nn.Module):
         """-> fp32 [6] on the device: loss, p_loss, d_loss of the image and of the text prediction, and the two noise means (0
         without noises); element 0 carries the gradient.  With ``noise_1`` / ``noise_2`` ([B, K] +-1) element 0 is the whole
         objective of DNPH.compute_loss, ``loss1 - noise_alpha (noise_img + noise_txt)``, from the same two library calls."""
-        for t in (feature_1, feature_2, predict_1, predict_2, self.proxies):
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        need_cuda(feature_1, feature_2, predict_1, predict_2, self.proxies)
         label_1 = torch.as_tensor(label_1)
         if label_2 is not None and label_2 is not label_1 and not torch.equal(torch.as_tensor(label_2).to(label_1.device), label_1):
             raise ValueError("DNPH loss: the two label matrices differ; both modalities of a pair carry the same labels")
@@ -90,49 +89,21 @@ class DNPHLoss(nn.Module):
             if n is not None and n.shape != feature_1.shape:
                 raise RuntimeError("DNPH loss: noises %s for codes %s" % (tuple(n.shape), tuple(feature_1.shape)))
         lab = R.pack_labels((label_1 == 1).to(torch.uint8).to(feature_1.device))          # the reference tests `label == 1` (:24)
-        return _Objective.apply(float(self.mrg), float(noise_alpha), lab, noises[0], noises[1], feature_1, feature_2, predict_1, predict_2,
-                                self.proxies)
+        return Objective.apply(_DNPH, (float(self.mrg), float(noise_alpha)), (lab, *noises), feature_1, feature_2, predict_1, predict_2,
+                               self.proxies)
 
 
-class _Objective(torch.autograd.Function):
-    """forward = xmh_dnph_loss -> fp32 [6], backward = xmh_dnph_loss_grad (all five gradients, one call; only element 0 carries one)"""
+def _pack(consts, aux, ts):
+    f1, f2, p1, p2, P = ts
+    B, K = f1.shape
+    C, Cp = P.shape[0], p1.shape[1]
+    lab, n1, n2 = aux
+    return (B, K, C, Cp), (ptr(f1), ptr(f2), ptr(p1), ptr(p2), ptr(P), B, K, C, Cp, ptr(lab), *consts, ptr(n1), ptr(n2))
 
-    @staticmethod
-    def _args(mrg, alpha, lab, n1, n2, f1, f2, p1, p2, P):
-        B, K = f1.shape
-        C, Cp = P.shape[0], p1.shape[1]
-        nbytes = lib.xmh_dnph_loss_ws_bytes(B, K, C, Cp)
-        if nbytes == 0:
-            raise RuntimeError("DNPH loss: B=%d K=%d C=%d Cp=%d outside B <= 4096, K <= 4096, Cp >= C, C, Cp <= 1024" % (B, K, C, Cp))
-        ws = workspace(nbytes, f1.device)
-        return (ptr(f1), ptr(f2), ptr(p1), ptr(p2), ptr(P), B, K, C, Cp, ptr(lab), mrg, alpha, ptr(n1), ptr(n2)), ws
 
-    @staticmethod
-    def forward(ctx, mrg, alpha, lab, n1, n2, *inputs):
-        ts = [t.detach().float().contiguous() for t in inputs]
-        args, ws = _Objective._args(mrg, alpha, lab, n1, n2, *ts)
-        out = torch.empty(8, dtype=torch.float64, device=ts[0].device)
-        check(lib.xmh_dnph_loss(*args, ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_dnph_loss")
-        ctx.consts = (mrg, alpha)
-        ctx.has_noise = (n1 is not None, n2 is not None)
-        ctx.meta = [(t.shape, t.dtype) for t in inputs]
-        ctx.save_for_backward(lab, *[n for n in (n1, n2) if n is not None], *ts)
-        return out[:6].float()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable: fail loudly on double backward
-    def backward(ctx, g):
-        lab, *rest = ctx.saved_tensors
-        n1 = rest.pop(0) if ctx.has_noise[0] else None
-        n2 = rest.pop(0) if ctx.has_noise[1] else None
-        ts = rest
-        args, ws = _Objective._args(*ctx.consts, lab, n1, n2, *ts)
-        up = g.detach().float()[:1].contiguous()      # only element 0 (the loss) carries a gradient
-        need = ctx.needs_input_grad[5:]
-        grads = [torch.empty_like(t) if nd else None for t, nd in zip(ts, need)]
-        check(lib.xmh_dnph_loss_grad(*args, ptr(up), *[ptr(t) for t in grads], 0, ptr(ws), ws.numel(), current_stream()), "xmh_dnph_loss_grad")
-        grads = [None if t is None else t.reshape(s).to(d) for t, (s, d) in zip(grads, ctx.meta)]
-        return (None, None, None, None, None, *grads)
+# forward = xmh_dnph_loss -> fp32 [6], backward = xmh_dnph_loss_grad (all five gradients, one call; only element 0 carries one)
+_DNPH = Spec(lib.xmh_dnph_loss, lib.xmh_dnph_loss_grad, _pack, lib.xmh_dnph_loss_ws_bytes,
+             "DNPH loss: B=%d K=%d C=%d Cp=%d outside B <= 4096, K <= 4096, Cp >= C, C, Cp <= 1024", out_len=8, terms=6)
 
 
 @registry.register_model("DNPH")

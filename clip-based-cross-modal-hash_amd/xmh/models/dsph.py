@@ -15,11 +15,12 @@ import torch
 import torch.nn as nn
 
 from .. import retrieval as R
-from .._lib import check, current_stream, lib, ptr, workspace
+from .._lib import lib, ptr
 from ..common.register import registry
 from .base import BaseModel
 from .codetable import hyp_threshold
 from .heads import DSPHHashLayer
+from .objective import Objective, Spec, need_cuda
 
 
 class HyPProxies(nn.Module):
@@ -41,50 +42,26 @@ class HyPProxies(nn.Module):
         if self.threshold is None:
             raise ValueError("DSPH's HyP loss has no threshold: set `threshold` in the model config, or `codetable` to the path of "
                              "the reference's codetable.xlsx")
-        for t in (x, y, self.proxies):
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        need_cuda(x, y, self.proxies)
         if x.dim() != 2 or y.shape != x.shape or label.dim() != 2 or label.shape[0] != x.shape[0] \
                 or label.shape[1] != self.proxies.shape[0] or x.shape[1] != self.proxies.shape[1]:
             raise RuntimeError("HyP loss: x %s, y %s, label %s, proxies %s do not fit together"
                                % (tuple(x.shape), tuple(y.shape), tuple(label.shape), tuple(self.proxies.shape)))
         if label.device != x.device:
             label = label.to(x.device)
-        return _HyP.apply(self, x, y, self.proxies, R.pack_labels(label))
+        return Objective.apply(_HYP, (float(self.threshold), float(self.alpha)), (R.pack_labels(label),), x, y, self.proxies)
 
 
-class _HyP(torch.autograd.Function):
-    """forward = xmh_hyp_loss, backward = xmh_hyp_loss_grad (both with respect to x, y and the proxies, one call)"""
+def _pack(consts, aux, ts):
+    x, y, P = ts
+    B, K = x.shape
+    C = P.shape[0]
+    return (B, K, C), (ptr(x), ptr(y), ptr(P), B, K, C, ptr(aux[0]), *consts)
 
-    @staticmethod
-    def _args(hyp, x, y, P, lab):
-        B, K = x.shape
-        C = P.shape[0]
-        ws = workspace(lib.xmh_hyp_loss_ws_bytes(B, K, C), x.device)
-        return (ptr(x), ptr(y), ptr(P), B, K, C, ptr(lab), float(hyp.threshold), float(hyp.alpha)), ws
 
-    @staticmethod
-    def forward(ctx, hyp, x, y, proxies, lab):
-        xs, ys, P = (t.detach().float().contiguous() for t in (x, y, proxies))
-        args, ws = _HyP._args(hyp, xs, ys, P, lab)
-        out = torch.empty(8, dtype=torch.float64, device=xs.device)
-        check(lib.xmh_hyp_loss(*args, ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_hyp_loss")
-        ctx.hyp = hyp
-        ctx.meta = ((x.shape, x.dtype), (y.shape, y.dtype), (proxies.shape, proxies.dtype))
-        ctx.save_for_backward(xs, ys, P, lab)
-        return out[0].float()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable: fail loudly on double backward
-    def backward(ctx, g):
-        xs, ys, P, lab = ctx.saved_tensors
-        args, ws = _HyP._args(ctx.hyp, xs, ys, P, lab)
-        up = g.detach().float().reshape(1).contiguous()
-        gx, gy, gP = torch.empty_like(xs), torch.empty_like(ys), torch.empty_like(P)
-        check(lib.xmh_hyp_loss_grad(*args, ptr(up), ptr(gx), ptr(gy), ptr(gP), 0, ptr(ws), ws.numel(), current_stream()),
-              "xmh_hyp_loss_grad")
-        grads = [t.reshape(s).to(d) if need else None for t, (s, d), need in zip((gx, gy, gP), ctx.meta, ctx.needs_input_grad[1:4])]
-        return (None, *grads, None)
+# forward = xmh_hyp_loss -> the loss as a 0-dim tensor, backward = xmh_hyp_loss_grad (with respect to x, y and the proxies, one call)
+_HYP = Spec(lib.xmh_hyp_loss, lib.xmh_hyp_loss_grad, _pack, lib.xmh_hyp_loss_ws_bytes,
+            "HyP loss: B=%d K=%d C=%d outside B <= 4096, K <= 4096, C <= 1024", out_len=8, terms=0, null_grads=False)
 
 
 @registry.register_model("DSPH")

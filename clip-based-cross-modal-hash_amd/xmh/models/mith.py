@@ -30,6 +30,7 @@ from . import clip as _clip
 from . import clip_train as _ct
 from .base import BaseModel
 from .clip import Transformer
+from .objective import need_cuda
 
 
 class ResidualMLPs(nn.Module):
@@ -426,9 +427,7 @@ class MITH(BaseModel):
             raise RuntimeError("MITH loss: inputs %s and label_sim %s do not fit a [%d, %d] buffer"
                                % ([tuple(t.shape) for t in xs], tuple(label_sim.shape), N, K))
         rows = self._rows(indexs, N, B)                   # host indices are checked before anything is launched
-        for t in xs:
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        need_cuda(*xs)
         dev = img_cls_hash.device
         if self.img_buffer_cls.device != dev:             # :170-173 -- all four names end up on the one device tensor
             self._bind_buffer(self.img_buffer_cls.to(dev, non_blocking=True))

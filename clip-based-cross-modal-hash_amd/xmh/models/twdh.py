@@ -23,6 +23,7 @@ from .._lib import check, current_stream, lib, ptr
 from ..common.register import registry
 from .base import BaseModel
 from .heads import DCMHTHashLayer
+from .objective import need_cuda
 from .weights import _gen
 
 
@@ -170,8 +171,7 @@ class TwDH(BaseModel):
     def soft_argmax_hash_loss(self, code):
         """reference :125-130 -- 1 - mean((2 code - 1)^2), a 0-dim fp32 device tensor, differentiable with respect to `code` as the
         reference's is (xmh_quant_loss / xmh_quant_loss_grad)"""
-        if not code.is_cuda:
-            raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % code.device)
+        need_cuda(code)
         return _Quant.apply(code)
 
     def draw_ties(self):
@@ -223,8 +223,7 @@ class TwDH(BaseModel):
         xs = [long_img_hash, long_txt_hash] + [short_img_hash[k] for k in keys] + [short_txt_hash[k] for k in keys]
         want = [2 * self.long_dim] * 2 + [2 * int(k) for k in keys] * 2
         for t, w in zip(xs, want):
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+            need_cuda(t)
             if t.dim() != 2 or tuple(t.shape) != (B, w):
                 raise ValueError("TwDH loss: a code of shape %s where [%d, %d] is expected" % (tuple(t.shape), B, w))
         if torch.as_tensor(labels).shape[0] != B:

@@ -23,6 +23,7 @@ from .._lib import check, current_stream, lib, ptr, workspace
 from ..common.register import registry
 from .base import BaseModel
 from .heads import _param
+from .objective import Objective, Spec, need_cuda
 
 HASH_FUNCS = ("linear_subspace", "tanh", "softmax")          # XMH_UMOED_LINEAR_SUBSPACE, XMH_UMOED_TANH, XMH_UMOED_SOFTMAX
 MERGE_FUNCS = ("concatenate", "mean")                        # XMH_UMOED_CONCATENATE, XMH_UMOED_MEAN
@@ -31,40 +32,16 @@ TERMS = ("loss", "T_i2t", "T_t2i", "U_img", "U_txt")
 
 
 # ---- the objective (reference UMoED.py similarity_loss) ---------------------------------------------------------------------------------
-class _Objective(torch.autograd.Function):
-    """forward = xmh_umoed_loss -> fp32 [5], backward = xmh_umoed_loss_grad (both gradients, one call; only element 0 carries one)"""
+def _pack(consts, aux, ts):
+    e1, e2 = ts
+    B, M, V = e1.shape
+    cst, C_ = consts
+    return (B, M, V, C_), (ptr(e1), ptr(e2), B, M, V, C_, ptr(aux[0]), C.byref(cst))
 
-    @staticmethod
-    def _args(cst, lab, C_, e1, e2):
-        B, M, V = e1.shape
-        nbytes = lib.xmh_umoed_loss_ws_bytes(B, M, V, C_)
-        if nbytes == 0:
-            raise RuntimeError("UMoED objective: B=%d M=%d V=%d C=%d outside B <= 512, M <= 128, V <= 256, C <= 127" % (B, M, V, C_))
-        ws = workspace(nbytes, e1.device)
-        return (ptr(e1), ptr(e2), B, M, V, C_, ptr(lab), C.byref(cst)), ws
 
-    @staticmethod
-    def forward(ctx, cst, lab, C_, e_img, e_txt):
-        ts = [t.detach().float().contiguous() for t in (e_img, e_txt)]
-        args, ws = _Objective._args(cst, lab, C_, *ts)
-        out = torch.empty(8, dtype=torch.float64, device=ts[0].device)
-        check(lib.xmh_umoed_loss(*args, ptr(ws), ws.numel(), ptr(out), current_stream()), "xmh_umoed_loss")
-        ctx.cst, ctx.C_ = cst, C_
-        ctx.meta = [(t.shape, t.dtype) for t in (e_img, e_txt)]
-        ctx.save_for_backward(lab, *ts)
-        return out[:5].float()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable      # the gradient kernel is not itself differentiable
-    def backward(ctx, g):
-        lab, *ts = ctx.saved_tensors
-        args, ws = _Objective._args(ctx.cst, lab, ctx.C_, *ts)
-        up = g.detach().float()[:1].contiguous()      # only element 0 (the loss) carries a gradient
-        grads = [torch.empty_like(t) if nd else None for t, nd in zip(ts, ctx.needs_input_grad[3:])]
-        check(lib.xmh_umoed_loss_grad(*args, ptr(up), ptr(grads[0]), ptr(grads[1]), 0, ptr(ws), ws.numel(), current_stream()),
-              "xmh_umoed_loss_grad")
-        grads = [None if t is None else t.reshape(s).to(d) for t, (s, d) in zip(grads, ctx.meta)]
-        return (None, None, None, *grads)
+# forward = xmh_umoed_loss -> fp32 [5], backward = xmh_umoed_loss_grad (both gradients, one call; only element 0 carries one)
+_UMOED = Spec(lib.xmh_umoed_loss, lib.xmh_umoed_loss_grad, _pack, lib.xmh_umoed_loss_ws_bytes,
+              "UMoED objective: B=%d M=%d V=%d C=%d outside B <= 512, M <= 128, V <= 256, C <= 127", out_len=8, terms=5)
 
 
 class UMoEDObjective(nn.Module):
@@ -98,16 +75,14 @@ class UMoEDObjective(nn.Module):
 
     def terms(self, img_embeds, txt_embeds, labels):
         """-> fp32 [5] on the device (TERMS); element 0 carries the gradient"""
-        for t in (img_embeds, txt_embeds):
-            if not t.is_cuda:
-                raise RuntimeError("xmh losses need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        need_cuda(img_embeds, txt_embeds)
         labels = torch.as_tensor(labels)
         B = img_embeds.shape[0]
         if img_embeds.dim() != 3 or txt_embeds.shape != img_embeds.shape or labels.dim() != 2 or labels.shape[0] != B:
             raise RuntimeError("UMoED objective: embeddings %s / %s, labels %s do not fit together"
                                % (tuple(img_embeds.shape), tuple(txt_embeds.shape), tuple(labels.shape)))
         lab = R.pack_labels((labels == 1).to(torch.uint8).to(img_embeds.device))
-        return _Objective.apply(self.consts, lab, labels.shape[1], img_embeds, txt_embeds)
+        return Objective.apply(_UMOED, (self.consts, labels.shape[1]), (lab,), img_embeds, txt_embeds)
 
     def forward(self, img_embeds, txt_embeds, labels=None):
         """-> (loss, loss_dict) with the reference's nested names; without labels every sample is its own class (object_function)"""

@@ -58,6 +58,8 @@ class ContiguousShardSampler(Sampler):
 
 
 class BaseTrainer:
+    MODEL_ARCH = "DCMHT"            # the registered model a configuration without ``model.arch`` gets (the reference's default)
+    EPOCH = "train_epoch"           # the method train() runs once per epoch
 
     def __init__(self, cfg, is_train=True, device=None, world_size=torch.cuda.device_count(), output_dim=16, train_num=10000,
                  query_num=5000, epochs=100, save_dir="./result", display_step=20, top_k=5000, model_state="", batch_size=128,
@@ -112,11 +114,15 @@ class BaseTrainer:
             dist.init_process_group("gloo" if share else "nccl", rank=rank, world_size=world_size)     # "nccl" is RCCL on ROCm
 
     # ---- builders ---------------------------------------------------------------------------------------
+    def model_kwargs(self):
+        """further keywords of the model's ``from_config``, beside ``output_dim`` and ``train_num``"""
+        return {}
+
     def build_model(self, cfg_model, output_dim=16, **kwags):
-        arch = cfg_model.get("arch", "DCMHT")
+        arch = cfg_model.get("arch", self.MODEL_ARCH)
         cls = registry.get_model_class(arch)
         assert cls is not None, "model '%s' is not registered (known: %s)" % (arch, registry.list_models())
-        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num)
+        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num, **self.model_kwargs())
         if os.path.isfile(self.model_state):
             self.logger.info("loading model...")
             self.model.load_state_dict(torch.load(self.model_state, map_location=f"cuda:{self.device}"))
@@ -206,7 +212,7 @@ class BaseTrainer:
 
     def train(self):
         for epoch in range(self.epochs):
-            self.train_epoch(epoch=epoch)
+            getattr(self, self.EPOCH)(epoch)
             self.valid(epoch, k=self.top_k)
         self._log_finished()
 

@@ -16,7 +16,14 @@ from .base import BaseTrainer
 
 
 class _MethodTrainer(BaseTrainer):
-    MODEL_ARCH = None
+    """What a method declares, as data: MODEL_ARCH; LOSS_INPUTS, the keyword names of its objective's inputs in the order compute_loss
+    takes them; BITS_FROM, the one of them whose last extent over ``hash_scale`` is the code length of the display line; FORWARD, the
+    model's train-forward method, FORWARD_MASK whether it takes the key padding mask, and FORWARD_OUTPUTS, the keyword names of its
+    outputs in its own order (None: they go to compute_loss positionally); LOSS_OPTIONAL, the inputs a caller may leave out (None then)."""
+    LOSS_INPUTS = ("img_hash", "txt_hash")
+    LOSS_OPTIONAL = ()
+    BITS_FROM = "img_hash"
+    FORWARD, FORWARD_MASK, FORWARD_OUTPUTS = "forward_train", False, LOSS_INPUTS
 
     def __init__(self, cfg, is_train=True, logger=None, device=None, world_size=torch.cuda.device_count(), output_dim=16,
                  train_num=10000, query_num=5000, epochs=100, save_dir="./result", batch_size=128, num_workers=4, pin_memory=True,
@@ -41,30 +48,42 @@ class _MethodTrainer(BaseTrainer):
                    model_state=run.get("resume_model", ""), display_step=run.get("display_step", 20), top_k=run.get("top_k", None),
                    world_size=world_size, distributed=distributed, **extra)
 
+    def loss_extras(self, inputs, label):
+        """further keywords of the model's object_function, made from the batch (MITH: label_sim)"""
+        return {}
 
-def _step_pair(trainer, image, text, key_padding_mask, label, index, epoch, times):
-    """one batch of DCMHT / DSPH: the two codes of forward_train into the objective (the text tower takes no key padding mask)"""
-    hash_img, hash_text = trainer.model.forward_train(image, text)
-    return trainer.compute_loss(img_hash=hash_img, txt_hash=hash_text, label=label, index=index, epoch=epoch, times=times,
+    def compute_loss(self, *args, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
+        """The objective of one batch, the reference's compute_loss of every runner (the lines are with each class): LOSS_INPUTS
+        positionally or by keyword, handed to the model's object_function.  The returned loss is differentiable with respect to what
+        the class names.  The display line needs the training loop's loader and optimiser and is skipped without them."""
+        inputs = dict(zip(self.LOSS_INPUTS, args))
+        rest = self.LOSS_INPUTS[len(args):]
+        missing = [n for n in rest if n not in kwags and n not in self.LOSS_OPTIONAL]
+        if missing or len(args) > len(self.LOSS_INPUTS):
+            raise TypeError("%s.compute_loss takes %s (missing: %s)" % (type(self).__name__, ", ".join(self.LOSS_INPUTS), ", ".join(missing) or "none"))
+        inputs.update((n, kwags.pop(n, None)) for n in rest)
+        all_loss, loss_dict = self.model.object_function(**inputs, labels=label, indexs=index, **self.loss_extras(inputs, label), **kwags)
+        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
+            self.print_loss_dict(loss_dict, bits=inputs[self.BITS_FROM].shape[-1] // self.hash_scale, epoch=epoch, times=times)
+        return all_loss
+
+
+def _step(trainer, image, text, key_padding_mask, label, index, epoch, times):
+    """one batch: the outputs of the model's train-forward (trainer.FORWARD) into the objective (trainer.FORWARD_OUTPUTS).  DCMHT /
+    DSPH: the two codes; MITH (runners/MITH/runner.py:109-115): the eight outputs of the head over both towers, the text tower with
+    the key padding mask; TwDH (runners/TwDH/runner.py:129-130): the long code and the short codes of both modalities; DNPH
+    (runners/DNPH/runner.py:126-127): the code and the class logits; DIMCH (runners/DIMCH/runner.py:132-133): the token embeddings
+    and the codes."""
+    forward = getattr(trainer.model, trainer.FORWARD)
+    out = forward(image, text, key_padding_mask=key_padding_mask) if trainer.FORWARD_MASK else forward(image, text)
+    args, names = (out, ()) if trainer.FORWARD_OUTPUTS is None else ((), trainer.FORWARD_OUTPUTS)
+    return trainer.compute_loss(*args, **dict(zip(names, out)), label=label, index=index, epoch=epoch, times=times,
                                 global_step=trainer.global_step)
 
 
-def _step_mith(trainer, image, text, key_padding_mask, label, index, epoch, times):
-    """one batch of MITH (runners/MITH/runner.py:109-115): the eight outputs of the head over both towers into the objective"""
-    out = trainer.model.forward_train_towers(image, text, key_padding_mask=key_padding_mask)
-    return trainer.compute_loss(*out, label=label, index=index, epoch=epoch, times=times, global_step=trainer.global_step)
-
-
-def _step_twdh(trainer, image, text, key_padding_mask, label, index, epoch, times):
-    """one batch of TwDH (runners/TwDH/runner.py:129-130): the long code and the short codes of both modalities into the objective"""
-    img_long, img_short, txt_long, txt_short = trainer.model.forward_train_codes(image, text)
-    return trainer.compute_loss(long_img_hash=img_long, long_txt_hash=txt_long, short_img_hash=img_short, short_txt_hash=txt_short, label=label,
-                                index=index, epoch=epoch, times=times, global_step=trainer.global_step)
-
-
-def _train_epoch(trainer, epoch: int, step=_step_pair):
-    """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser); with
-    step=_step_mith, runners/MITH/runner.py:98-123.  `step(trainer, image, text, key_padding_mask, label, index, epoch, times)`
+def _train_epoch(trainer, epoch: int, step=_step):
+    """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser); with MITH's
+    declaration, runners/MITH/runner.py:98-123.  `step(trainer, image, text, key_padding_mask, label, index, epoch, times)`
     returns the loss of one batch.  The optimiser is built on the first call, when the instance has none yet.  A batch of raw
     photos (uint8, stacked or a list of different sizes: the file layout's training split) goes through the GPU training
     transform; a float batch goes on as it is."""
@@ -103,7 +122,11 @@ def _train_epoch(trainer, epoch: int, step=_step_pair):
 
 @registry.register_runner("DCMHTTrainer")
 class DCMHTTrainer(_MethodTrainer):
-    """runners/DCMHT/runner.py: the model emits 2K pair probabilities; bit j = +1 iff p[j,1] > p[j,0] (:82-95)."""
+    """runners/DCMHT/runner.py: the model emits 2K pair probabilities; bit j = +1 iff p[j,1] > p[j,0] (:82-95).
+    compute_loss (:97-105): differentiable with respect to img_hash / txt_hash (xmh_loss.hip behind torch.autograd), and through them
+    -- when they come from `model.hash` in .train() mode -- with respect to every parameter of the heads (xmh_head_grad.hip)."""
+
+    MODEL_ARCH = "DCMHT"
 
     def __init__(self, cfg, *a, **k):
         self.hash_func = cfg.model.get("hash_func", "softmax")
@@ -126,21 +149,13 @@ class DCMHTTrainer(_MethodTrainer):
         """runners/DCMHT/runner.py:107-128"""
         _train_epoch(self, epoch)
 
-    def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
-        """runners/DCMHT/runner.py:97-105: the objective of one batch.  The returned loss is differentiable with respect to
-        img_hash / txt_hash (xmh_loss.hip behind torch.autograd), and through them -- when they come from `model.hash` in
-        .train() mode -- with respect to every parameter of the heads (xmh_head_grad.hip); the display line of :101-103 needs the training loop's
-        loader and optimiser, which this package does not build, and is skipped without them."""
-        all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, labels=label, indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
-
 
 @registry.register_runner("DSPHTrainer")
 class DSPHTrainer(_MethodTrainer):
-    """runners/DSPH/runner.py: base generate_hash + sign quantiser."""
+    """runners/DSPH/runner.py: base generate_hash + sign quantiser.  compute_loss (:93-101): the HyP objective (xmh_hyp.hip behind
+    torch.autograd), differentiable with respect to img_hash / txt_hash and the model's hyp.proxies."""
 
+    MODEL_ARCH = "DSPH"
     hash_scale = 1                                              # runners/DSPH/runner.py:38
     loss_type = "l1"                                            # runners/DSPH/runner.py:27-31: only named in the display line
 
@@ -158,42 +173,31 @@ class DSPHTrainer(_MethodTrainer):
         """runners/DSPH/runner.py:104-127: as DCMHT's, and the proxies' SGD steps beside BertAdam"""
         _train_epoch(self, epoch)
 
-    def compute_loss(self, img_hash=None, txt_hash=None, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
-        """runners/DSPH/runner.py:93-101: the HyP objective of one batch (xmh_hyp.hip behind torch.autograd), differentiable with
-        respect to img_hash / txt_hash and the model's hyp.proxies; the display line needs the training loop's loader and
-        optimiser, which this package does not build, and is skipped without them."""
-        all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, labels=label, indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
-
 
 @registry.register_runner("MITHTrainer")
 class MITHTrainer(_MethodTrainer):
-    """runners/MITH/runner.py:125-131: code = sign(cls_hash + tokens_hash); the text tower gets the padding mask."""
+    """runners/MITH/runner.py:125-131: code = sign(cls_hash + tokens_hash); the text tower gets the padding mask.  compute_loss
+    (:84-96): the objective of xmh_mith_loss.hip behind torch.autograd, differentiable with respect to the eight head outputs."""
 
+    MODEL_ARCH = "MITH"
+    LOSS_INPUTS = ("res_img_cls", "img_cls_hash", "tokens_hash_i", "trans_tokens_i", "res_txt_cls", "txt_cls_hash", "tokens_hash_t",
+                   "trans_tokens_t")
+    BITS_FROM = "img_cls_hash"
+    FORWARD, FORWARD_MASK, FORWARD_OUTPUTS = "forward_train_towers", True, None
+    EPOCH = "train_epoch_towers"
+    train = BaseTrainer.train                                   # the one loop, entered in this class too: train() is MITH's own entry point
     hash_scale = 1                                              # runners/MITH/runner.py:39
     loss_type = "l1"                                            # runners/MITH/runner.py:28-32: only named in the display line
 
-    def compute_loss(self, res_img_cls, img_cls_hash, tokens_hash_i, trans_tokens_i, res_txt_cls, txt_cls_hash, tokens_hash_t,
-                     trans_tokens_t, label=None, index=None, epoch=0, times=0, global_step=0, **kwags):
-        """runners/MITH/runner.py:84-96: the objective of one batch (xmh_mith_loss.hip behind torch.autograd), differentiable with
-        respect to the eight head outputs.  label_sim = calc_label_sim(train_labels, label), [train_num, B], is formed on the codes'
-        device, with the packed train labels kept there between calls; the display line needs the training loop's loader and
-        optimiser, which this package does not build, and is skipped without them."""
-        dev = img_cls_hash.device
+    def loss_extras(self, inputs, label):
+        """label_sim = calc_label_sim(train_labels, label), [train_num, B], formed on the codes' device, with the packed train labels
+        kept there between calls"""
+        dev = inputs["img_cls_hash"].device
         cached = getattr(self, "_train_lab", None)
         if cached is None or cached[0] is not self.train_labels or cached[1] != dev:
             tl = torch.as_tensor(self.train_labels)
             cached = self._train_lab = (self.train_labels, dev, R.pack_labels(tl.to(dev)), tl.shape[1])
-        label_sim = R.label_sim(cached[2], R.pack_labels(torch.as_tensor(label).to(dev)), cached[3])
-        all_loss, loss_dict = self.model.object_function(res_img_cls=res_img_cls, img_cls_hash=img_cls_hash, tokens_hash_i=tokens_hash_i,
-                                                         trans_tokens_i=trans_tokens_i, res_txt_cls=res_txt_cls, txt_cls_hash=txt_cls_hash,
-                                                         tokens_hash_t=tokens_hash_t, trans_tokens_t=trans_tokens_t, labels=label,
-                                                         indexs=index, label_sim=label_sim, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_cls_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
+        return {"label_sim": R.label_sim(cached[2], R.pack_labels(torch.as_tensor(label).to(dev)), cached[3])}
 
     def train_epoch(self, epoch: int):
         raise NotImplementedError("MITHTrainer.train_epoch: the epoch that trains MITH's head and both towers, the reference's, is "
@@ -202,14 +206,7 @@ class MITHTrainer(_MethodTrainer):
 
     def train_epoch_towers(self, epoch: int):
         """runners/MITH/runner.py:98-123: the backbone at backbone_lr and the head at lr, the text tower with the key padding mask"""
-        _train_epoch(self, epoch, step=_step_mith)
-
-    def train(self):
-        """runners/base.py:287-294 with this class's epoch"""
-        for epoch in range(self.epochs):
-            self.train_epoch_towers(epoch)
-            self.valid(epoch, k=self.top_k)
-        self._log_finished()
+        _train_epoch(self, epoch)
 
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)
@@ -220,7 +217,14 @@ class MITHTrainer(_MethodTrainer):
 class TwDHTrainer(DCMHTTrainer):
     """runners/TwDH/runner.py: one forward yields the long code and every short code (:138-143); evaluation reports the four
     mAPs per code length (:181-228).  Code streams: "long" (long_dim bits) and one per short length, all quantised by the
-    DCMHT pair-argmax (:82-95 of the DCMHT runner, inherited)."""
+    DCMHT pair-argmax (:82-95 of the DCMHT runner, inherited).  compute_loss (:106-114): the objective of xmh_twdh.hip behind
+    torch.autograd, differentiable with respect to the long codes and every short code."""
+
+    MODEL_ARCH = "TwDH"
+    LOSS_INPUTS = ("long_img_hash", "long_txt_hash", "short_img_hash", "short_txt_hash")
+    BITS_FROM = "long_img_hash"
+    FORWARD, FORWARD_OUTPUTS = "forward_train_codes", ("long_img_hash", "short_img_hash", "long_txt_hash", "short_txt_hash")
+    EPOCH = "train_epoch_codes"
 
     def __init__(self, cfg, *a, **k):
         self.long_dim = cfg.model.get("long_dim", 512)
@@ -233,25 +237,7 @@ class TwDHTrainer(DCMHTTrainer):
 
     def train_epoch_codes(self, epoch: int):
         """runners/TwDH/runner.py:116-137: one BertAdam over the backbone and the hash layer; the transforms and centres are constants"""
-        _train_epoch(self, epoch, step=_step_twdh)
-
-    def train(self):
-        """runners/base.py:287-294 with this class's epoch"""
-        for epoch in range(self.epochs):
-            self.train_epoch_codes(epoch)
-            self.valid(epoch, k=self.top_k)
-        self._log_finished()
-
-    def compute_loss(self, long_img_hash, long_txt_hash, short_img_hash, short_txt_hash, label=None, index=None, epoch=0, times=0,
-                     global_step=0, **kwags):
-        """runners/TwDH/runner.py:106-114: the objective of one batch (xmh_twdh.hip behind torch.autograd), differentiable with
-        respect to the long codes and every short code; the display line needs the training loop's loader and optimiser, which this
-        package does not build, and is skipped without them."""
-        all_loss, loss_dict = self.model.object_function(long_img_hash=long_img_hash, long_txt_hash=long_txt_hash, short_img_hash=short_img_hash,
-                                                         short_txt_hash=short_txt_hash, labels=label, indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=long_img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
+        _train_epoch(self, epoch)
 
     def build_model(self, cfg_model, output_dim=16):
         super().build_model(cfg_model, output_dim=output_dim)
@@ -338,17 +324,14 @@ class TwDHTrainer(DCMHTTrainer):
         return {name: maps for name, (maps, _) in results.items()}
 
 
-def _step_dnph(trainer, image, text, key_padding_mask, label, index, epoch, times):
-    """one batch of DNPH (runners/DNPH/runner.py:126-127): the code and the class logits of both modalities into the objective"""
-    img_hash, txt_hash, img_pre, txt_pre = trainer.model.forward_train(image, text)
-    return trainer.compute_loss(img_hash=img_hash, txt_hash=txt_hash, img_pre=img_pre, txt_pre=txt_pre, label=label, index=index, epoch=epoch,
-                                times=times, global_step=trainer.global_step)
-
-
 @registry.register_runner("DNPHTrainer")
 class DNPHTrainer(_MethodTrainer):
-    """runners/DNPH/runner.py: the model's encoders return (code, class logits); evaluation quantises the code by its sign."""
+    """runners/DNPH/runner.py: the model's encoders return (code, class logits); evaluation quantises the code by its sign.
+    compute_loss (:102-110): the objective of xmh_dnph.hip behind torch.autograd, differentiable with respect to the codes, the class
+    logits and the model's loss.proxies."""
 
+    MODEL_ARCH = "DNPH"
+    LOSS_INPUTS = FORWARD_OUTPUTS = ("img_hash", "txt_hash", "img_pre", "txt_pre")
     hash_scale = 1                                              # runners/DNPH/runner.py:41
     loss_type = "l1"                                            # runners/DNPH/runner.py:30-34: only named in the display line
 
@@ -369,18 +352,7 @@ class DNPHTrainer(_MethodTrainer):
     def train_epoch(self, epoch: int):
         """runners/DNPH/runner.py:113-136: the four outputs of the head over both towers into the objective; the proxies' SGD steps
         beside BertAdam"""
-        _train_epoch(self, epoch, step=_step_dnph)
-
-    def compute_loss(self, img_hash=None, txt_hash=None, img_pre=None, txt_pre=None, label=None, index=None, epoch=0, times=0, global_step=0,
-                     **kwags):
-        """runners/DNPH/runner.py:102-110: the objective of one batch (xmh_dnph.hip behind torch.autograd), differentiable with
-        respect to the codes, the class logits and the model's loss.proxies; the display line needs the training loop's loader and
-        optimiser, which this package does not build, and is skipped without them."""
-        all_loss, loss_dict = self.model.object_function(img_hash=img_hash, txt_hash=txt_hash, img_pre=img_pre, txt_pre=txt_pre, labels=label,
-                                                         indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_hash.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
+        _train_epoch(self, epoch)
 
     def generate_hash(self, image, text, key_padding_mask=None):
         """runners/DNPH/runner.py:138-141: the codes alone; the class logits are a training signal"""
@@ -388,19 +360,16 @@ class DNPHTrainer(_MethodTrainer):
         return image_hash, text_hash
 
 
-def _step_dimch(trainer, image, text, key_padding_mask, label, index, epoch, times):
-    """one batch of DIMCH (runners/DIMCH/runner.py:132-133): the token embeddings and the codes of both modalities into the objective"""
-    img_embeds, img_hash, txt_embeds, txt_hash = trainer.model.forward_train(image, text)
-    return trainer.compute_loss(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash, label=label, index=index,
-                                epoch=epoch, times=times, global_step=trainer.global_step)
-
-
 @registry.register_runner("DIMCHTrainer")
 class DIMCHTrainer(_MethodTrainer):
     """runners/DIMCH/runner.py: the model's encoders return (token embeddings, code); evaluation quantises the tanh code by its sign.
     With ``hash_func: softmax`` the code is 2K wide and the reference writes it into its K-wide buffer and fails (:147-149 with
-    runners/base.py get_code); ``valid`` says so instead."""
+    runners/base.py get_code); ``valid`` says so instead.  compute_loss (:109-117): the objective of xmh_dimch.hip behind
+    torch.autograd, differentiable with respect to the token embeddings and the codes."""
 
+    MODEL_ARCH = "DIMCH"
+    LOSS_INPUTS = FORWARD_OUTPUTS = ("img_embeds", "img_hash", "txt_embeds", "txt_hash")
+    BITS_FROM = "img_embeds"
     loss_type = "l1"                                            # runners/DIMCH/runner.py:33: only named in the display line
 
     def __init__(self, cfg, *a, **k):
@@ -408,35 +377,13 @@ class DIMCHTrainer(_MethodTrainer):
         self.hash_scale = 2 if self.hash_func == "softmax" else 1   # runners/DIMCH/runner.py:39-42
         super().__init__(cfg, *a, **k)
 
-    def build_model(self, cfg_model, output_dim=16, **kwags):
-        """runners/DIMCH/runner.py:87-107: as the base class, and the text token count ``dataset.max_word`` handed on"""
-        arch = cfg_model.get("arch", "DIMCH")
-        cls = registry.get_model_class(arch)
-        assert cls is not None, "model '%s' is not registered (known: %s)" % (arch, registry.list_models())
-        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num,
-                                     txt_token_size=self.cfg.dataset.get("max_word", 32))
-        if os.path.isfile(self.model_state):
-            self.logger.info("loading model...")
-            self.model.load_state_dict(torch.load(self.model_state, map_location=f"cuda:{self.device}"))
-        self.model.float()
-        self.model.to(self.device)
-        self.logger.info("Building model!")
-        self.logger.info(f"Output dim: {self.output_dim}")
+    def model_kwargs(self):
+        """runners/DIMCH/runner.py:87-107: the text token count ``dataset.max_word`` handed on"""
+        return {"txt_token_size": self.cfg.dataset.get("max_word", 32)}
 
     def train_epoch(self, epoch: int):
         """runners/DIMCH/runner.py:119-140"""
-        _train_epoch(self, epoch, step=_step_dimch)
-
-    def compute_loss(self, img_embeds=None, img_hash=None, txt_embeds=None, txt_hash=None, label=None, index=None, epoch=0, times=0,
-                     global_step=0, **kwags):
-        """runners/DIMCH/runner.py:109-117: the objective of one batch (xmh_dimch.hip behind torch.autograd), differentiable with
-        respect to the token embeddings and the codes; the display line needs the training loop's loader and optimiser and is
-        skipped without them."""
-        all_loss, loss_dict = self.model.object_function(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash,
-                                                         labels=label, indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_embeds.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
+        _train_epoch(self, epoch)
 
     def merge_hash(self, image_embed, text_embed):
         """runners/DIMCH/runner.py:142-145"""
@@ -459,8 +406,14 @@ class DIMCHTrainer(_MethodTrainer):
 class UMoEDTrainer(_MethodTrainer):
     """runners/UMoED/runner.py: the model's encoders return (token logits, code); evaluation reports four mAPs (i->t, t->i, i->i, t->t),
     keeps a best epoch for each and writes four .mat files with a fusion stream beside the usual keys.  The linear-subspace and tanh codes
-    are quantised by their sign, the pair softmax by its argmax.  The decoder head has no backward here, so ``train_epoch`` raises."""
+    are quantised by their sign, the pair softmax by its argmax.  The decoder head has no backward here, so ``train_epoch`` raises.
+    compute_loss (:126-134): the objective of xmh_umoed.hip behind torch.autograd, differentiable with respect to the two logit tensors."""
 
+    MODEL_ARCH = "UMoED"
+    # the six outputs of the model's forward; there is no train-forward yet (train_epoch raises), the names are what one would return
+    LOSS_INPUTS = FORWARD_OUTPUTS = ("img_embeds", "img_hash", "txt_embeds", "txt_hash", "fusion_embeds", "fusion_hash")
+    LOSS_OPTIONAL = ("fusion_embeds", "fusion_hash")
+    BITS_FROM = "img_embeds"
     loss_type = "l1"                                            # runners/UMoED/runner.py:35: only named in the display line
     MAP_NAMES = ("i2t", "t2i", "i2i", "t2t")
 
@@ -474,41 +427,17 @@ class UMoEDTrainer(_MethodTrainer):
             setattr(self, "best_epoch_" + name, 0)
         super().__init__(cfg, *a, **k)
 
-    def build_model(self, cfg_model, output_dim=16, **kwags):
-        """runners/UMoED/runner.py:104-124: as the base class, and the text token count ``dataset.max_word`` handed on"""
-        arch = cfg_model.get("arch", "UMoED")
-        cls = registry.get_model_class(arch)
-        assert cls is not None, "model '%s' is not registered (known: %s)" % (arch, registry.list_models())
-        self.model = cls.from_config(cfg_model, output_dim=output_dim, train_num=self.train_num,
-                                     txt_token_size=self.cfg.dataset.get("max_word", 32))
-        if os.path.isfile(self.model_state):
-            self.logger.info("loading model...")
-            self.model.load_state_dict(torch.load(self.model_state, map_location=f"cuda:{self.device}"))
-        self.model.float()
-        self.model.to(self.device)
-        self.logger.info("Building model!")
-        self.logger.info(f"Output dim: {self.output_dim}")
-
-    def compute_loss(self, img_embeds=None, img_hash=None, txt_embeds=None, txt_hash=None, fusion_embeds=None, fusion_hash=None, label=None,
-                     index=None, epoch=0, times=0, global_step=0, **kwags):
-        """runners/UMoED/runner.py:126-134: the objective of one batch (xmh_umoed.hip behind torch.autograd), differentiable with respect
-        to the two logit tensors; the display line needs the training loop's loader and optimiser and is skipped without them."""
-        all_loss, loss_dict = self.model.object_function(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash,
-                                                         fusion_embeds=fusion_embeds, fusion_hash=fusion_hash, labels=label, indexs=index, **kwags)
-        if global_step % self.display_step == 0 and getattr(self, "train_loader", None) is not None and getattr(self, "optimizer", None) is not None:
-            self.print_loss_dict(loss_dict, bits=img_embeds.shape[-1] // self.hash_scale, epoch=epoch, times=times)
-        return all_loss
+    def model_kwargs(self):
+        """runners/UMoED/runner.py:104-124: the text token count ``dataset.max_word`` handed on"""
+        return {"txt_token_size": self.cfg.dataset.get("max_word", 32)}
 
     def train_epoch(self, epoch: int):
         raise NotImplementedError("UMoEDTrainer.train_epoch: the backward of the decoder head is not built (xmh_head_umoed is inference only: "
                                   "self- and cross-attention, the Soft-MoE routing and the experts have no gradient kernels); the objective "
                                   "and its gradient are (compute_loss), and valid() / test() evaluate a trained checkpoint")
 
-    def train(self):
-        """runners/UMoED/runner.py:245-251: the reference's loop; with ``is_train: true`` it raises at once in train_epoch"""
-        for epoch in range(self.epochs):
-            self.train_epoch(epoch=epoch)
-            self.valid(epoch, k=self.top_k)
+    def _log_finished(self):
+        """runners/UMoED/runner.py:245-251: the line that ends train(), which with ``is_train: true`` raises at once in train_epoch"""
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i2t}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t2i}, "
                          f"mAP: {self.max_mapt2i}, I-I: {self.best_epoch_i2i}, MAP: {self.max_mapi2i}, T-T: {self.best_epoch_t2t}, MAP: {self.max_mapt2t}")
 

@@ -36,7 +36,7 @@ that moves by 2.2 between two float32 runs), and the two modalities' hashing lay
 
 The module was seen to fail under each of these edits on a scratch copy of the package (case narrow; the first failure of each, then
 what else): the backbone group given `lr` instead of `backbone_lr` (get_lr at step 0; the keep-sets from step 2 on, delta); the image
-tower's backward taking the cls gradient only (grad of every tensor of the image tower at step 0, ratios 8e3 to 5e4); _step_mith
+tower's backward taking the cls gradient only (grad of every tensor of the image tower at step 0, ratios 8e3 to 5e4); the step
 dropping key_padding_mask (the text keep-set at step 0, 264 entries, and the loss at step 0, 132.12 against 131.91); the text head's
 backward returning no gradient for the shared gcl parameters (grad of hash.gcl_i.mlp.* at step 0, e_port 0.3 to 0.97); the buffer's
 row write taking tokens_hash_i (the batch's buffer rows at step 0, the loss at step 0, 130.88 against 130.76); optimizer.zero_grad()

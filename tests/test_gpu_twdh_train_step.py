@@ -44,7 +44,7 @@ the measure was at fault, not the port -- the float32 restatement's own figure i
 parameter, which its noise does not explain either (twdh_train_step_cases) -- and with the storage term the budget is 4.8e-9.
 
 The module was seen to fail under each of these edits on a scratch copy of the package (case rated; the first failing check of
-each, then what else).  The text's short codes handed in as the image's in _step_twdh: codes img_short at step 0 (e_port 0.25, ratio
+each, then what else).  The text's short codes handed in as the image's in the step: codes img_short at step 0 (e_port 0.25, ratio
 3e5), the loss at step 0 (2.23467 against 2.23583) and its terms, every gradient at step 0.  _ShortCodes.backward returning zeros
 for the long code: grad of every tensor at step 0 (ratios 4e3 to 1.5e6, e_port 0.2 to 0.3), loss and codes of step 0 untouched.  The
 short streams' quantisation weight taken as quan_alpha instead of low_rate in k_twdh_loss_grad: grad of every tensor at step 0
