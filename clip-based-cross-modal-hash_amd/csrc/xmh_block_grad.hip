@@ -16,11 +16,13 @@
 // One product kernel, C[i][j] = sum_k A(i, k) B(j, k) over strided views (as k_mm of xmh_head_grad.hip), on v_mfma_f32_32x32x2_f32:
 // an exact fmaf chain per 32 consecutive k, the 32-blocks added in index order.  Every reduction here runs in one fixed order (no
 // float atomics), so two calls on equal inputs agree to the bit; no host synchronisation, no allocation.
-// The product, bias and LayerNorm kernels and their launch helpers are in xmh_grad_kernels.h (xmh_tower_grad.hip uses them too).
+// The product, bias and LayerNorm kernels and their launch helpers are in xmh_grad_kernels.hip (xmh_tower_grad.hip and xmh_mith_grad.hip use them).
 #include "xmh_clip_record.h"
 #include "xmh_grad_kernels.h"
 
 namespace {
+
+using namespace xmh::grad;
 
 // Attention backward of one (batch, head) per block.  K and V of the head stay in LDS (rows padded to 65 floats, key rows up to
 // LP = 4 NJ zero-filled); the queries go by in tiles of 32 rows: S = (q / sqrt(dh)) K^T + mask and P = softmax(S) are recomputed as

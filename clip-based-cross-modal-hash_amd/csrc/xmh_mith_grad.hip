@@ -1,6 +1,6 @@
 // Training forward and backward of one modality of MITH's hash head (models/MITH/hash/hash.py:231-247).  Exact fp32
 // throughout, for the reason xmh_block_grad.hip gives.  The token transformer runs through xmh_clip_blocks_forward_saved /
-// xmh_clip_blocks_backward, the products, bias sums and LayerNorm backward are the kernels of xmh_grad_kernels.h, the forward's
+// xmh_clip_blocks_backward, the products, bias sums and LayerNorm backward are the kernels of xmh_grad_kernels.hip, the forward's
 // LayerNorm, products and bitwise hash are the calls of xmh_head_mith in exact mode (same bits), and the LTA body is xmh_lta.h.
 //
 //   forward   cls path, kept per residual MLP: x_in | ln | fc_pre | fc_act (fc_pre from a second, epilogue-free product of the B
@@ -21,6 +21,9 @@
 #include "xmh_lta.h"
 
 namespace {
+
+using namespace xmh::grad;
+using xmh::wave_sum;
 
 constexpr int kMaxWidth = 1024;                  // the forward's LayerNorm kernel holds a row in 16 registers per lane
 constexpr int kMaxRes = 4;

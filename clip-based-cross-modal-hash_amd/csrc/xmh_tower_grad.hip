@@ -1,7 +1,7 @@
 // Training forward and backward of the two CLIP towers (models/CLIP/model.py:232-268, :373-396): the thin layers around the block
 // stack.  Exact fp32 throughout, for the reason xmh_block_grad.hip gives; the blocks themselves run through
 // xmh_clip_blocks_forward_saved / xmh_clip_blocks_backward, and the products, bias sums and LayerNorm backward are the kernels of
-// xmh_grad_kernels.h.
+// xmh_grad_kernels.hip.
 //
 //   image forward   im2col -> conv1 (fp32 MFMA) -> cls / pos / ln_pre (the rows in front of ln_pre are kept) -> blocks, saved ->
 //                   cls rows (kept) -> ln_post -> proj          the very calls of xmh_vit_b32_forward in exact mode: same bits
@@ -23,6 +23,8 @@
 #include "xmh_planes.h"
 
 namespace {
+
+using namespace xmh::grad;
 
 constexpr int kBatchChunk = 16;                  // items per partial of a sum over the batch
 constexpr int kMaxWidth = 1024;                  // the forward's LayerNorm kernels hold a row in 16 registers per lane

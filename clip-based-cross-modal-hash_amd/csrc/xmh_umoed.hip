@@ -16,8 +16,8 @@
 //     combine + residual, layernorm).  Plain: 12 (gemm linear + ReLU, gemm linear2 + residual, layernorm in place of the seven).
 //   per call: 1 (k_umoed_queries) + [1 first layer] + layers x 16 (12) + 1 (k_umoed_classify): 98 at the config's six MoE layers.
 //
-//   k_umoed_bmm is the 64 x 64 tile scheme of k_mfma_mm (xmh_grad_kernels.h: v_mfma_f32_32x32x2_f32, a 32-term chain per slab, slabs in
-//   order) with a batch on grid z, a two-level row stride for the A rows and the C rows (the experts' rows (b, p) of expert n lie
+//   k_umoed_bmm wraps the 64 x 64 tile core that k_mfma_mm wraps (xmh_mfma_mm.h: v_mfma_f32_32x32x2_f32, a 32-term chain per slab, slabs
+//   in order) with a batch on grid z, a two-level row stride for the A rows and the C rows (the experts' rows (b, p) of expert n lie
 //   S F apart in b and F apart in p) and bias / residual in the epilogue; the four soft-MoE products are its four argument sets.  The
 //   reduction is never split, so there is one summation order.  k_umoed_cross_attn: one block per (sample, head), K and V of the head
 //   in LDS, a thread per query row, scores in two passes (maximum, then sum and P V) so that no score table is kept; no mask.
@@ -38,11 +38,13 @@
 #include <math.h>
 
 #include "xmh_common.h"
+#include "xmh_mfma_mm.h"
 #include "xmh_rows.h"
 #include "xmh_triplet.h"
 
 namespace {
 
+namespace mm = xmh::mm;
 namespace trip = xmh::trip;
 using xmh::wave_max;
 using xmh::wave_sum;
@@ -54,10 +56,9 @@ constexpr int kMaxLossB = trip::kMaxB, kMaxC = 127;
 constexpr float kEps = 1e-12f;                 // F.normalize's eps
 constexpr float kUnifT = 20.0f;                // batchwise_uniformity_loss's t
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ---- batched exact-fp32 product -------------------------------------------------------------------------------------------------------
-constexpr int kTile = 64, kBK = 32, kLd = kTile + 1;
+using mm::kTile;
+static_assert(kThreads == mm::kThreads, "the tile core's block");
 
 struct BmmArgs {
     const float* A;           // A(z; i, k) = A[z sab + (i / adiv) sah + (i % adiv) sai + k sak]
@@ -75,77 +76,25 @@ struct BmmArgs {
 };
 
 // AK / BK: k is the unit-stride index of that operand (which index the lanes of a load walk; the arithmetic is the same).  Grid
-// (I tiles, J tiles, batch).  LDS holds the slab k-major, rows padded by one float, as k_mfma_mm.
+// (I tiles, J tiles, batch).  The reduction is the tile core's, whole: one chunk [0, Kd).
 template <bool AK, bool BK>
 __global__ __launch_bounds__(kThreads) void k_umoed_bmm(BmmArgs g) {
-    __shared__ float As[kBK][kLd];
-    __shared__ float Bs[kBK][kLd];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = blockIdx.x * kTile, j0 = blockIdx.y * kTile;
     const int64_t z = blockIdx.z;
-    const float* Ab = g.A + z * g.sab;
-    const float* Bb = g.B + z * g.sbb;
-    int64_t arow[8], brow[8];
-    bool aok[8], bok[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int ai = i0 + (AK ? (tid >> 5) + 8 * r : (tid & 63));
-        const int bj = j0 + (BK ? (tid >> 5) + 8 * r : (tid & 63));
-        aok[r] = ai < g.I, bok[r] = bj < g.J;
-        arow[r] = (int64_t)(ai / g.adiv) * g.sah + (int64_t)(ai % g.adiv) * g.sai;
-        brow[r] = (int64_t)bj * g.sbj;
-    }
-    float ra[8], rb[8];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int ak = k0 + (AK ? (tid & 31) : (tid >> 6) + 4 * r), bk = k0 + (BK ? (tid & 31) : (tid >> 6) + 4 * r);
-            ra[r] = (aok[r] && ak < g.Kd) ? Ab[arow[r] + (int64_t)ak * g.sak] : 0.0f;
-            rb[r] = (bok[r] && bk < g.Kd) ? Bb[brow[r] + (int64_t)bk * g.sbk] : 0.0f;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int ai = AK ? (tid >> 5) + 8 * r : (tid & 63), ak = AK ? (tid & 31) : (tid >> 6) + 4 * r;
-            const int bj = BK ? (tid >> 5) + 8 * r : (tid & 63), bk = BK ? (tid & 31) : (tid >> 6) + 4 * r;
-            As[ak][ai] = ra[r];
-            Bs[bk][bj] = rb[r];
-        }
-    };
-    const int fr = lane & 31, fh = lane >> 5;
-    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
-    f32x16 tot;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) tot[e] = 0.0f;
-    fetch(0);
-    for (int k0 = 0; k0 < g.Kd; k0 += kBK) {
-        stash();
-        __syncthreads();
-        if (k0 + kBK < g.Kd) fetch(k0 + kBK);    // the next slab's loads fly over this slab's MFMAs
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-#pragma unroll
-        for (int s = 0; s < kBK / 2; ++s)        // zero padding past Kd: fmaf(0, 0, p) == p
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * s + fh][wi + fr], Bs[2 * s + fh][wj + fr], acc, 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tot[e] += acc[e];
-        __syncthreads();
-    }
-    const int j = j0 + wj + fr;
+    const mm::Operand a = mm::make_operand<AK>(g.A + z * g.sab, g.sak, i0, g.I,
+                                               [&](int i) { return (int64_t)(i / g.adiv) * g.sah + (int64_t)(i % g.adiv) * g.sai; });
+    const mm::Operand b = mm::make_operand<BK>(g.B + z * g.sbb, g.sbk, j0, g.J, [&](int j) { return (int64_t)j * g.sbj; });
+    const mm::f32x16 tot = mm::tile_product<AK, BK>(a, b, 0, g.Kd, [](const auto&) {});
+    const int j = mm::out_col(j0);
     if (j >= g.J) return;
     const float bj = g.bias ? g.bias[z * g.sbias + j] : 0.0f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int i = i0 + wi + (e & 3) + 8 * (e >> 2) + 4 * fh;
-        if (i >= g.I) continue;
-        const int64_t at = z * g.scb + (int64_t)(i / g.cdiv) * g.sch + (int64_t)(i % g.cdiv) * g.sci + j;
-        float v = tot[e];
+    const int64_t at0 = z * g.scb + j;
+    mm::for_each_output(tot, i0, j0, g.I, g.J, [&](int i, int, float v) {
+        const int64_t at = at0 + (int64_t)(i / g.cdiv) * g.sch + (int64_t)(i % g.cdiv) * g.sci;
         if (g.bias) v += bj;
         if (g.res) v += g.res[at];
         g.C[at] = v;
-    }
+    });
 }
 
 template <bool AK, bool BK>
