@@ -1,5 +1,5 @@
 // The exact-fp32 product tile on v_mfma_f32_32x32x2_f32 that k_mfma_mm (xmh_grad_kernels.hip: every backward's NN / TN product, split reduction)
-// and k_umoed_bmm (xmh_umoed.hip: the batched soft-MoE products) wrap.  A block of kThreads threads owns 64 x 64 outputs C[i][j] = sum_k A(i, k)
+// and k_umoed_bmm (xmh_umoed_head.h: the batched soft-MoE products, forward and backward) wrap.  A block of kThreads threads owns 64 x 64 outputs C[i][j] = sum_k A(i, k)
 // B(j, k), one 32 x 32 MFMA tile per wave.  A wrapper is address set-up (make_operand), one call of tile_product, its epilogue (for_each_output).
 #pragma once
 #include <hip/hip_runtime.h>

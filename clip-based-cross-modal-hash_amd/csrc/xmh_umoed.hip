@@ -11,15 +11,16 @@
 //   embeds = classifier(x) [B, M, V];  code = linear-subspace bits of argmax_v, or tanh / pair softmax of the mean over M
 //
 //   launches per layer, MoE: 16 -- self-attention 4 (xmh_gemm_nt_f32 in_proj, xmh_attention_f32, xmh_gemm_nt_f32 out_proj + residual,
-//     xmh_layernorm_f32), cross-attention 5 (gemm q, gemm k|v of mem, k_umoed_cross_attn, gemm out_proj + residual, layernorm),
+//     xmh_layernorm_f32), cross-attention 5 (gemm q, gemm k|v of mem, k_umoed_attn, gemm out_proj + residual, layernorm),
 //     soft-MoE 7 (gemm linear + ReLU, k_umoed_bmm logits, k_umoed_route, k_umoed_bmm dispatch, k_umoed_bmm experts, k_umoed_bmm
 //     combine + residual, layernorm).  Plain: 12 (gemm linear + ReLU, gemm linear2 + residual, layernorm in place of the seven).
 //   per call: 1 (k_umoed_queries) + [1 first layer] + layers x 16 (12) + 1 (k_umoed_classify): 98 at the config's six MoE layers.
+//   The kernels and the layer chain (forward_chain) are in xmh_umoed_head.h, shared with the train-mode head of xmh_umoed_grad.hip.
 //
 //   k_umoed_bmm wraps the 64 x 64 tile core that k_mfma_mm wraps (xmh_mfma_mm.h: v_mfma_f32_32x32x2_f32, a 32-term chain per slab, slabs
 //   in order) with a batch on grid z, a two-level row stride for the A rows and the C rows (the experts' rows (b, p) of expert n lie
 //   S F apart in b and F apart in p) and bias / residual in the epilogue; the four soft-MoE products are its four argument sets.  The
-//   reduction is never split, so there is one summation order.  k_umoed_cross_attn: one block per (sample, head), K and V of the head
+//   reduction is never split, so there is one summation order.  k_umoed_attn: one block per (sample, head), K and V of the head
 //   in LDS, a thread per query row, scores in two passes (maximum, then sum and P V) so that no score table is kept; no mask.
 //
 // ---- the objective (xmh_umoed_loss / xmh_umoed_loss_grad), distance.mode pairwise, distance_mode cosine, triplet ---------------------
@@ -42,205 +43,21 @@
 #include "xmh_rows.h"
 #include "xmh_triplet.h"
 
+#include "xmh_umoed_head.h"
+
 namespace {
 
-namespace mm = xmh::mm;
 namespace trip = xmh::trip;
 using xmh::wave_max;
 using xmh::wave_sum;
+using umoed::kMaxM;
+using umoed::kMaxV;
 
 constexpr int kThreads = trip::kThreads, kWaves = trip::kWaves;
-constexpr int kMaxM = 128, kMaxT = 128, kMaxE = 2048, kMaxD = 1024, kMaxF = 4096, kMaxS = 256, kMaxV = 256;
-constexpr int64_t kMaxRows = 32768;            // B max(M, T), the row limit of the other heads
+static_assert(kThreads == umoed::kThreads, "one block size for the head and the objective");
 constexpr int kMaxLossB = trip::kMaxB, kMaxC = 127;
 constexpr float kEps = 1e-12f;                 // F.normalize's eps
 constexpr float kUnifT = 20.0f;                // batchwise_uniformity_loss's t
-
-// ---- batched exact-fp32 product -------------------------------------------------------------------------------------------------------
-using mm::kTile;
-static_assert(kThreads == mm::kThreads, "the tile core's block");
-
-struct BmmArgs {
-    const float* A;           // A(z; i, k) = A[z sab + (i / adiv) sah + (i % adiv) sai + k sak]
-    int64_t sai, sak, sab, sah;
-    int adiv;
-    const float* B;           // B(z; j, k) = B[z sbb + j sbj + k sbk]
-    int64_t sbj, sbk, sbb;
-    int I, J, Kd;
-    float* C;                 // C(z; i, j) = C[z scb + (i / cdiv) sch + (i % cdiv) sci + j]
-    int64_t sci, scb, sch;
-    int cdiv;
-    const float* bias;        // bias[z sbias + j], or NULL
-    int64_t sbias;
-    const float* res;         // residual, addressed as C, or NULL
-};
-
-// AK / BK: k is the unit-stride index of that operand (which index the lanes of a load walk; the arithmetic is the same).  Grid
-// (I tiles, J tiles, batch).  The reduction is the tile core's, whole: one chunk [0, Kd).
-template <bool AK, bool BK>
-__global__ __launch_bounds__(kThreads) void k_umoed_bmm(BmmArgs g) {
-    const int i0 = blockIdx.x * kTile, j0 = blockIdx.y * kTile;
-    const int64_t z = blockIdx.z;
-    const mm::Operand a = mm::make_operand<AK>(g.A + z * g.sab, g.sak, i0, g.I,
-                                               [&](int i) { return (int64_t)(i / g.adiv) * g.sah + (int64_t)(i % g.adiv) * g.sai; });
-    const mm::Operand b = mm::make_operand<BK>(g.B + z * g.sbb, g.sbk, j0, g.J, [&](int j) { return (int64_t)j * g.sbj; });
-    const mm::f32x16 tot = mm::tile_product<AK, BK>(a, b, 0, g.Kd, [](const auto&) {});
-    const int j = mm::out_col(j0);
-    if (j >= g.J) return;
-    const float bj = g.bias ? g.bias[z * g.sbias + j] : 0.0f;
-    const int64_t at0 = z * g.scb + j;
-    mm::for_each_output(tot, i0, j0, g.I, g.J, [&](int i, int, float v) {
-        const int64_t at = at0 + (int64_t)(i / g.cdiv) * g.sch + (int64_t)(i % g.cdiv) * g.sci;
-        if (g.bias) v += bj;
-        if (g.res) v += g.res[at];
-        g.C[at] = v;
-    });
-}
-
-template <bool AK, bool BK>
-void launch_bmm(hipStream_t st, const BmmArgs& g, int batch) {
-    const dim3 grid((unsigned)((g.I + kTile - 1) / kTile), (unsigned)((g.J + kTile - 1) / kTile), (unsigned)batch);
-    hipLaunchKernelGGL((k_umoed_bmm<AK, BK>), grid, dim3(kThreads), 0, st, g);
-}
-
-// ---- the learned queries, repeated over the batch --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_umoed_queries(const float* __restrict__ q, int64_t per, int64_t total, float* __restrict__ x) {
-    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (e < total) x[e] = q[e % per];
-}
-
-// ---- cross-attention: q [B M, d], kv [B T, 2 d] (k | v), out [B M, d]; block (sample, head), thread = query row, dh = 64 ---------------
-__global__ __launch_bounds__(128) void k_umoed_cross_attn(const float* __restrict__ q, const float* __restrict__ kv, int M, int T, int H,
-                                                          float* __restrict__ out) {
-    constexpr int DH = 64;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int b = blockIdx.x / H, h = blockIdx.x % H;
-    const int D = H * DH;
-    float4* sK = reinterpret_cast<float4*>(smem);                    // [T][DH / 4]; every lane reads the same address: a broadcast
-    float4* sV = sK + T * (DH / 4);                                  // [T][DH / 4]
-    const float* kvb = kv + (int64_t)b * T * 2 * D;
-    for (int e = threadIdx.x; e < T * (DH / 4); e += blockDim.x) {
-        const int j = e / (DH / 4), c4 = e % (DH / 4);
-        sK[e] = *reinterpret_cast<const float4*>(kvb + (int64_t)j * 2 * D + h * DH + c4 * 4);
-        sV[e] = *reinterpret_cast<const float4*>(kvb + (int64_t)j * 2 * D + D + h * DH + c4 * 4);
-    }
-    __syncthreads();
-    const int i = threadIdx.x;
-    if (i >= M) return;
-    const int64_t row = (int64_t)b * M + i;
-    float qr[DH];
-    const float scale = rsqrtf((float)DH);
-#pragma unroll
-    for (int c = 0; c < DH / 4; ++c) {                               // PyTorch scales q before Q K^T
-        const float4 v = *reinterpret_cast<const float4*>(q + row * D + h * DH + c * 4);
-        qr[4 * c + 0] = v.x * scale, qr[4 * c + 1] = v.y * scale, qr[4 * c + 2] = v.z * scale, qr[4 * c + 3] = v.w * scale;
-    }
-    auto score = [&](int j) {
-        float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-        for (int c = 0; c < DH / 4; ++c) {
-            const float4 kk = sK[j * (DH / 4) + c];
-            s0 = fmaf(qr[4 * c + 0], kk.x, s0);
-            s1 = fmaf(qr[4 * c + 1], kk.y, s1);
-            s0 = fmaf(qr[4 * c + 2], kk.z, s0);
-            s1 = fmaf(qr[4 * c + 3], kk.w, s1);
-        }
-        return s0 + s1;
-    };
-    float mx = -INFINITY;
-    for (int j = 0; j < T; ++j) mx = fmaxf(mx, score(j));
-    float o[DH];
-#pragma unroll
-    for (int c = 0; c < DH; ++c) o[c] = 0.0f;
-    float sum = 0.0f;
-    for (int j = 0; j < T; ++j) {
-        const float p = expf(score(j) - mx);                         // the same chain as in the first pass: the largest is exp(0)
-        sum += p;
-#pragma unroll
-        for (int c = 0; c < DH / 4; ++c) {
-            const float4 vv = sV[j * (DH / 4) + c];
-            o[4 * c + 0] = fmaf(p, vv.x, o[4 * c + 0]);
-            o[4 * c + 1] = fmaf(p, vv.y, o[4 * c + 1]);
-            o[4 * c + 2] = fmaf(p, vv.z, o[4 * c + 2]);
-            o[4 * c + 3] = fmaf(p, vv.w, o[4 * c + 3]);
-        }
-    }
-    const float inv = 1.0f / sum;
-#pragma unroll
-    for (int c = 0; c < DH / 4; ++c)
-        *reinterpret_cast<float4*>(out + row * D + h * DH + c * 4) = make_float4(o[4 * c + 0] * inv, o[4 * c + 1] * inv, o[4 * c + 2] * inv, o[4 * c + 3] * inv);
-}
-
-// ---- routing: block = sample; its logits [M, S] staged in LDS once; D = softmax down the columns, Cw = softmax along the rows -------------
-__global__ __launch_bounds__(kThreads) void k_umoed_route(const float* __restrict__ logits, int M, int S, float* __restrict__ Dw, float* __restrict__ Cw) {
-    extern __shared__ __attribute__((aligned(16))) float ls[];      // [M][S]: lanes walk s, consecutive banks in both phases
-    const int64_t base = (int64_t)blockIdx.x * M * S;
-    for (int e = threadIdx.x; e < M * S; e += kThreads) ls[e] = logits[base + e];
-    __syncthreads();
-    for (int s = threadIdx.x; s < S; s += kThreads) {                // a thread per slot: the M rows in order
-        float mx = -INFINITY;
-        for (int m = 0; m < M; ++m) mx = fmaxf(mx, ls[m * S + s]);
-        float sum = 0.0f;
-        for (int m = 0; m < M; ++m) sum += expf(ls[m * S + s] - mx);
-        for (int m = 0; m < M; ++m) Dw[base + (int64_t)m * S + s] = expf(ls[m * S + s] - mx) / sum;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int m = wave; m < M; m += kWaves) {                         // a wave per row
-        float mx = -INFINITY;
-        for (int s = lane; s < S; s += 64) mx = fmaxf(mx, ls[m * S + s]);
-        mx = wave_max(mx);
-        float sum = 0.0f;
-        for (int s = lane; s < S; s += 64) sum += expf(ls[m * S + s] - mx);
-        sum = wave_sum(sum);
-        for (int s = lane; s < S; s += 64) Cw[base + (int64_t)m * S + s] = expf(ls[m * S + s] - mx) / sum;
-    }
-}
-
-// ---- classifier and code: block = sample ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_umoed_classify(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                             int M, int d, int V, int hash_func, float* __restrict__ embeds, float* __restrict__ code) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t b = blockIdx.x;
-    const float* xb = x + b * M * d;
-    float* eb = embeds + b * M * V;
-    for (int pair = wave; pair < M * V; pair += kWaves) {            // a wave per logit
-        const int m = pair / V, v = pair % V;
-        float s = 0.0f;
-        for (int k = lane; k < d; k += 64) s = fmaf(xb[(int64_t)m * d + k], w[(int64_t)v * d + k], s);
-        s = wave_sum(s);
-        if (lane == 0) eb[pair] = s + bias[v];
-    }
-    __syncthreads();                                                 // the block's own global writes are visible to it behind the barrier
-    if (hash_func == XMH_UMOED_LINEAR_SUBSPACE) {
-        int bits = 0;
-        while ((1 << bits) < V) ++bits;
-        for (int m = threadIdx.x; m < M; m += kThreads) {
-            float best = eb[m * V];
-            int at = 0;
-            for (int v = 1; v < V; ++v) {
-                const float e = eb[m * V + v];
-                if (e > best) best = e, at = v;                      // the first index on a tie
-            }
-            for (int j = 0; j < bits; ++j) code[(b * M + m) * bits + j] = ((at >> (bits - 1 - j)) & 1) ? 1.0f : -1.0f;      // most significant first
-        }
-        return;
-    }
-    auto mean_of = [&](int v) {
-        float s = 0.0f;
-        for (int m = 0; m < M; ++m) s += eb[m * V + v];
-        return s / (float)M;
-    };
-    if (hash_func == XMH_UMOED_TANH) {
-        for (int v = threadIdx.x; v < V; v += kThreads) code[b * V + v] = tanhf(mean_of(v));
-        return;
-    }
-    for (int p = threadIdx.x; p < V / 2; p += kThreads) {             // pair softmax
-        const float a0 = mean_of(2 * p), a1 = mean_of(2 * p + 1);
-        const float mx = fmaxf(a0, a1), e0 = expf(a0 - mx), e1 = expf(a1 - mx);
-        code[b * V + 2 * p] = e0 / (e0 + e1);
-        code[b * V + 2 * p + 1] = e1 / (e0 + e1);
-    }
-}
 
 struct HeadWs {
     float *x, *y, *qkv, *att, *q, *kv, *mem, *h, *lg, *Dw, *Cw, *Xs, *Ys;
@@ -267,45 +84,10 @@ size_t head_layout(int64_t B, int T, const xmh_umoed_head* h, void* base, HeadWs
     return ar.used;
 }
 
-bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-// 0: fine; otherwise the status, with the text set when `who` is given
-int head_shape(const char* who, int64_t B, int T, const xmh_umoed_head* h) {
-#define UMOED_FAIL(code, ...) return who ? xmh::fail(code, __VA_ARGS__) : code
-    if (!h) UMOED_FAIL(XMH_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0 || h->E <= 0 || h->d <= 0 || h->heads <= 0 || h->F <= 0 || h->M <= 0 || h->V <= 0 || h->n_layers <= 0)
-        UMOED_FAIL(XMH_EINVAL, "%s: bad shape B=%lld T=%d E=%d d=%d heads=%d F=%d M=%d V=%d layers=%d", who, (long long)B, T, h->E, h->d, h->heads,
-                   h->F, h->M, h->V, h->n_layers);
-    if (h->moe && (h->n_experts <= 0 || h->slots <= 0)) UMOED_FAIL(XMH_EINVAL, "%s: bad shape experts=%d slots=%d", who, h->n_experts, h->slots);
-    if (h->hash_func < XMH_UMOED_LINEAR_SUBSPACE || h->hash_func > XMH_UMOED_SOFTMAX) UMOED_FAIL(XMH_EINVAL, "%s: hash_func %d", who, h->hash_func);
-    if ((h->hash_func == XMH_UMOED_LINEAR_SUBSPACE) != (h->merge == XMH_UMOED_CONCATENATE) || h->merge < XMH_UMOED_CONCATENATE || h->merge > XMH_UMOED_MEAN)
-        UMOED_FAIL(XMH_EINVAL, "%s: hash_func %d with merge %d (linear_subspace goes with concatenate, tanh and softmax with mean)", who, h->hash_func,
-                   h->merge);
-    if (!h->first_w && h->d != h->E) UMOED_FAIL(XMH_EINVAL, "%s: d=%d differs from E=%d and there is no first layer", who, h->d, h->E);
-    if (h->hash_func == XMH_UMOED_SOFTMAX && h->V % 2) UMOED_FAIL(XMH_EINVAL, "%s: the pair softmax needs an even V (V=%d)", who, h->V);
-    if (h->d % h->heads || h->d / h->heads != 64) UMOED_FAIL(XMH_ENOTSUP, "%s: head dim %d / %d (only 64, the attention kernels')", who, h->d, h->heads);
-    if (h->M > kMaxM || T > kMaxT) UMOED_FAIL(XMH_ENOTSUP, "%s: M=%d T=%d outside M <= %d, T <= %d", who, h->M, T, kMaxM, kMaxT);
-    if (h->E > kMaxE || h->d > kMaxD || h->F > kMaxF)
-        UMOED_FAIL(XMH_ENOTSUP, "%s: E=%d d=%d F=%d outside E <= %d, d <= %d (the LayerNorm kernel's width), F <= %d", who, h->E, h->d, h->F, kMaxE, kMaxD,
-                   kMaxF);
-    if (h->moe && (int64_t)h->n_experts * h->slots > kMaxS)
-        UMOED_FAIL(XMH_ENOTSUP, "%s: %d experts x %d slots outside S <= %d", who, h->n_experts, h->slots, kMaxS);
-    if (h->V > kMaxV || (h->hash_func == XMH_UMOED_LINEAR_SUBSPACE && !is_pow2(h->V)))
-        UMOED_FAIL(XMH_ENOTSUP, "%s: V=%d outside V <= %d (a power of two for linear_subspace)", who, h->V, kMaxV);
-    if (B > 65535 || B * (int64_t)(h->M > T ? h->M : T) > kMaxRows)
-        UMOED_FAIL(XMH_ENOTSUP, "%s: B=%lld with M=%d T=%d outside B max(M, T) <= %lld, B <= 65535", who, (long long)B, h->M, T, (long long)kMaxRows);
-#undef UMOED_FAIL
-    return XMH_OK;
-}
-
-int gemm(const float* A, int64_t K, const float* W, const float* bias, const float* res, float* Cm, int64_t rows, int64_t N, int act, xmh_stream_t s) {
-    return xmh_gemm_nt_f32(A, K, W, K, bias, res, N, Cm, N, rows, N, K, act, XMH_PREC_F32, s);
-}
-
 }  // namespace
 
 extern "C" size_t xmh_head_umoed_bytes(int64_t B, int T, const xmh_umoed_head* h) {
-    if (head_shape(nullptr, B, T, h)) return 0;
+    if (umoed::head_shape(nullptr, B, T, h)) return 0;
     return head_layout(B, T, h, nullptr, nullptr);
 }
 
@@ -313,88 +95,20 @@ extern "C" int xmh_head_umoed(const xmh_umoed_head* h, const float* tokens, int6
                               xmh_stream_t stream) {
     XMH_RANGE("xmh_head_umoed");
     const char* who = "xmh_head_umoed";
-    if (int rc = head_shape(who, B, T, h)) return rc;
-    if (!tokens || !embeds || !code || !ws || !h->layers || !h->queries || !h->cls_w || !h->cls_b || (h->first_w && !h->first_b))
-        return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
-    for (int l = 0; l < h->n_layers; ++l) {
-        const xmh_umoed_layer& y = h->layers[l];
-        const bool common = y.ln1_g && y.ln1_b && y.sa_in_w && y.sa_in_b && y.sa_out_w && y.sa_out_b && y.ln2_g && y.ln2_b && y.ca_in_w && y.ca_in_b &&
-                            y.ca_out_w && y.ca_out_b && y.ln3_g && y.ln3_b && y.lin_w && y.lin_b;
-        if (!common || (h->moe ? !(y.phi && y.exp_w && y.exp_b) : !(y.lin2_w && y.lin2_b)))
-            return xmh::fail(XMH_EINVAL, "%s: null pointer in layer %d", who, l);
-    }
+    if (int rc = umoed::head_shape(who, B, T, h)) return rc;
+    if (!tokens || !embeds || !code || !ws) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    XMH_TRY(umoed::head_pointers(who, h));
     XMH_TRY(xmh::check_workspace(who, ws, ws_bytes, head_layout(B, T, h, nullptr, nullptr), "xmh_head_umoed_bytes", XMH_ENOMEM));
     HeadWs w;
     head_layout(B, T, h, ws, &w);
-    hipStream_t st = xmh::as_stream(stream);
-    const int M = h->M, d = h->d, F = h->F, H = h->heads, P = h->slots, S = h->n_experts * h->slots;
-    const int64_t BM = B * M, BT = B * T;
-
     const float* mem = tokens;
     if (h->first_w) {
-        XMH_TRY(gemm(tokens, h->E, h->first_w, h->first_b, nullptr, w.mem, BT, d, XMH_ACT_RELU, stream));
+        XMH_TRY(umoed::gemm(tokens, h->E, h->first_w, h->first_b, nullptr, w.mem, B * T, h->d, XMH_ACT_RELU, stream));
         mem = w.mem;
     }
-    {
-        const int64_t per = (int64_t)M * d, total = BM * d;
-        hipLaunchKernelGGL(k_umoed_queries, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, h->queries, per, total, w.x);
-    }
-    const size_t attn_lds = (size_t)2 * T * 64 * sizeof(float), route_lds = (size_t)M * S * sizeof(float);
-    if (h->moe) XMH_TRY(xmh::raise_dynamic_lds(reinterpret_cast<const void*>(k_umoed_route), route_lds, who));
-    for (int l = 0; l < h->n_layers; ++l) {
-        const xmh_umoed_layer& y = h->layers[l];
-        // self-attention over the M rows
-        XMH_TRY(gemm(w.x, d, y.sa_in_w, y.sa_in_b, nullptr, w.qkv, BM, 3 * d, XMH_ACT_NONE, stream));
-        XMH_TRY(xmh_attention_f32(w.qkv, B, M, H, 64, 0, nullptr, w.att, stream));
-        XMH_TRY(gemm(w.att, d, y.sa_out_w, y.sa_out_b, w.x, w.y, BM, d, XMH_ACT_NONE, stream));
-        XMH_TRY(xmh_layernorm_f32(w.y, d, y.ln1_g, y.ln1_b, h->ln_eps, w.x, d, BM, d, stream));
-        // cross-attention: queries from x, keys and values from mem
-        XMH_TRY(gemm(w.x, d, y.ca_in_w, y.ca_in_b, nullptr, w.q, BM, d, XMH_ACT_NONE, stream));
-        XMH_TRY(gemm(mem, d, y.ca_in_w + (size_t)d * d, y.ca_in_b + d, nullptr, w.kv, BT, 2 * d, XMH_ACT_NONE, stream));
-        hipLaunchKernelGGL(k_umoed_cross_attn, dim3((unsigned)(B * H)), dim3(128), attn_lds, st, w.q, w.kv, M, T, H, w.att);
-        XMH_TRY(gemm(w.att, d, y.ca_out_w, y.ca_out_b, w.x, w.y, BM, d, XMH_ACT_NONE, stream));
-        XMH_TRY(xmh_layernorm_f32(w.y, d, y.ln2_g, y.ln2_b, h->ln_eps, w.x, d, BM, d, stream));
-        // feed-forward
-        XMH_TRY(gemm(w.x, d, y.lin_w, y.lin_b, nullptr, w.h, BM, F, XMH_ACT_RELU, stream));
-        if (!h->moe) {
-            XMH_TRY(gemm(w.h, F, y.lin2_w, y.lin2_b, w.x, w.y, BM, d, XMH_ACT_NONE, stream));
-        } else {
-            BmmArgs g = {};
-            g.adiv = g.cdiv = INT_MAX;
-            g.A = w.h, g.sai = F, g.sak = 1;                                     // logits [B M, S] = h phi
-            g.B = y.phi, g.sbj = 1, g.sbk = S;
-            g.I = (int)BM, g.J = S, g.Kd = F;
-            g.C = w.lg, g.sci = S;
-            launch_bmm<true, false>(st, g, 1);
-            hipLaunchKernelGGL(k_umoed_route, dim3((unsigned)B), dim3(kThreads), route_lds, st, w.lg, M, S, w.Dw, w.Cw);
-            g = BmmArgs{};
-            g.adiv = g.cdiv = INT_MAX;
-            g.A = w.Dw, g.sai = 1, g.sak = S, g.sab = (int64_t)M * S;            // Xs[b] [S, F] = D[b]^T h[b]
-            g.B = w.h, g.sbj = 1, g.sbk = F, g.sbb = (int64_t)M * F;
-            g.I = S, g.J = F, g.Kd = M;
-            g.C = w.Xs, g.sci = F, g.scb = (int64_t)S * F;
-            launch_bmm<false, false>(st, g, (int)B);
-            g = BmmArgs{};
-            g.A = w.Xs, g.sai = F, g.sak = 1, g.sab = (int64_t)P * F, g.adiv = P, g.sah = (int64_t)S * F;      // rows (b, p) of expert n
-            g.B = y.exp_w, g.sbj = 1, g.sbk = d, g.sbb = (int64_t)F * d;         // W_n [F, d], "in, out"
-            g.I = (int)(B * P), g.J = d, g.Kd = F;
-            g.C = w.Ys, g.sci = d, g.scb = (int64_t)P * d, g.cdiv = P, g.sch = (int64_t)S * d;
-            g.bias = y.exp_b, g.sbias = d;
-            launch_bmm<true, false>(st, g, h->n_experts);
-            g = BmmArgs{};
-            g.adiv = g.cdiv = INT_MAX;
-            g.A = w.Cw, g.sai = S, g.sak = 1, g.sab = (int64_t)M * S;            // y[b] = x[b] + Cw[b] Ys[b]
-            g.B = w.Ys, g.sbj = 1, g.sbk = d, g.sbb = (int64_t)S * d;
-            g.I = M, g.J = d, g.Kd = S;
-            g.C = w.y, g.sci = d, g.scb = (int64_t)M * d;
-            g.res = w.x;
-            launch_bmm<true, false>(st, g, (int)B);
-        }
-        XMH_TRY(xmh_layernorm_f32(w.y, d, y.ln3_g, y.ln3_b, h->ln_eps, w.x, d, BM, d, stream));
-    }
-    hipLaunchKernelGGL(k_umoed_classify, dim3((unsigned)B), dim3(kThreads), 0, st, w.x, h->cls_w, h->cls_b, M, d, h->V, h->hash_func, embeds, code);
-    XMH_LAUNCH_CHECK(who);
-    return XMH_OK;
+    // every layer works in the same buffers: x -> y -> x through each of the three post-norm sublayers
+    const umoed::LayerBufs bufs = {w.qkv, w.att, w.y, w.x, w.q, w.kv, w.att, w.y, w.x, w.h, w.lg, w.Dw, w.Cw, w.Xs, w.Ys, w.y, w.x, nullptr};
+    return umoed::forward_chain(who, h, mem, nullptr, 0.0f, B, T, w.x, [&](int) { return bufs; }, embeds, code, stream);
 }
 
 // =========================================================================================================================================

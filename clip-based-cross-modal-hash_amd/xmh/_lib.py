@@ -137,6 +137,15 @@ class UmoedHead(C.Structure):                  # xmh_umoed_head
                [(k, i32) for k in ("E", "d", "heads", "F", "M", "V", "n_experts", "slots", "moe", "hash_func", "merge")] + [("ln_eps", C.c_float)]
 
 
+class UmoedLayerGrads(C.Structure):            # xmh_umoed_layer_grads: the MoE layer's 19 parameters, in UmoedLayer's order
+    NAMES = UmoedLayer.NAMES[:19]
+    _fields_ = [(k, vp) for k in NAMES]
+
+
+class UmoedHeadGrads(C.Structure):             # xmh_umoed_head_grads
+    _fields_ = [("layers", C.POINTER(UmoedLayerGrads))] + [(k, vp) for k in ("d_queries", "d_cls_w", "d_cls_b", "d_tokens")]
+
+
 class UmoedConsts(C.Structure):                # xmh_umoed_consts
     _fields_ = [("extreme", i32)] + [(k, C.c_float) for k in ("extreme_T", "token_triplet_margin", "triplet_alpha", "unif_alpha")]
 
@@ -281,6 +290,10 @@ PROTOTYPES = {
     "xmh_head_dimch_backward": (i32, [C.POINTER(DimchHead), vp, i32, C.c_float, vp, vp, i64, vp, sz, C.POINTER(DimchHeadGrads), i32, vp, sz, vp]),
     "xmh_head_umoed_bytes": (sz, [i64, i32, C.POINTER(UmoedHead)]),
     "xmh_head_umoed": (i32, [C.POINTER(UmoedHead), vp, i64, i32, vp, vp, vp, sz, vp]),
+    "xmh_head_umoed_train_bytes": (sz, [i64, i32, C.POINTER(UmoedHead), C.POINTER(sz)]),
+    "xmh_umoed_keep_bytes": (sz, [i64, i32, C.POINTER(UmoedHead)]),
+    "xmh_head_umoed_train_forward": (i32, [C.POINTER(UmoedHead), vp, vp, C.c_float, i64, i32, vp, vp, vp, sz, vp, sz, vp]),
+    "xmh_head_umoed_backward": (i32, [C.POINTER(UmoedHead), vp, vp, C.c_float, vp, i64, i32, vp, sz, C.POINTER(UmoedHeadGrads), i32, vp, sz, vp]),
     "xmh_umoed_loss_ws_bytes": (sz, [i64, i32, i32, i32]),
     "xmh_umoed_loss": (i32, [vp, vp, i64, i32, i32, i32, vp, C.POINTER(UmoedConsts), vp, sz, vp, vp]),
     "xmh_umoed_loss_grad": (i32, [vp, vp, i64, i32, i32, i32, vp, C.POINTER(UmoedConsts), vp, vp, vp, i32, vp, sz, vp]),

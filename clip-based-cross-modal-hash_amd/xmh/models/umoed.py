@@ -2,8 +2,10 @@
 product a Soft-MoE, and the pairwise set objective -- through xmh_umoed.hip.
 
 ``UMoEDTokenHash`` / ``UMoEDHashLayer`` carry the reference's state-dict names (hash/hash_moe.py TokenHash, HashLayer), so a reference
-checkpoint loads strictly; one C call per modality and batch (xmh_head_umoed) runs the head in inference.  The head has no backward
-here: in train mode, or with a graph asked for, the forward raises.  ``UMoEDObjective`` is the reference's ``similarity_loss`` in the one
+checkpoint loads strictly; one C call per modality and batch (xmh_head_umoed) runs the head in inference.  ``forward`` / ``encode_img`` /
+``encode_txt`` stay inference only and raise in train mode or with a graph asked for; the train-mode head with its six dropout sites per
+layer and its backward (xmh_head_umoed_train_forward / xmh_head_umoed_backward) is ``forward_train`` / ``encode_img_train`` /
+``encode_txt_train``, one autograd.Function.  ``UMoEDObjective`` is the reference's ``similarity_loss`` in the one
 family its configuration uses (``distance.mode: pairwise``, ``distance_mode: cosine``, ``triplet: True``): one forward and one backward
 call (xmh_umoed_loss / xmh_umoed_loss_grad) behind one autograd.Function.  ``UMoED`` (registered as "UMoED") puts both behind the CLIP
 towers' token outputs.
@@ -22,7 +24,7 @@ from .. import retrieval as R
 from .._lib import check, current_stream, lib, ptr, workspace
 from ..common.register import registry
 from .base import BaseModel
-from .heads import _param
+from .heads import _DRAW, _param
 from .objective import Objective, Spec, need_cuda
 
 HASH_FUNCS = ("linear_subspace", "tanh", "softmax")          # XMH_UMOED_LINEAR_SUBSPACE, XMH_UMOED_TANH, XMH_UMOED_SOFTMAX
@@ -156,6 +158,43 @@ def _init_mha(m, g):
     nn.init.constant_(m.out_proj.bias, 0.0)
 
 
+class _UMoEDHeadTrain(torch.autograd.Function):
+    """forward = xmh_head_umoed_train_forward, backward = xmh_head_umoed_backward: one modality; only ``embeds`` carries a gradient"""
+
+    @staticmethod
+    def forward(ctx, mod, tokens, keep, *params):
+        embeds, code, x, saved = mod._run_train(tokens, keep)
+        ctx.mod, ctx.p, ctx.meta = mod, float(mod.dropout_p), (tokens.shape, tokens.dtype)
+        ctx.mark_non_differentiable(code)
+        ctx.save_for_backward(x, saved, keep, *params)   # saved parameters: autograd notices an in-place change before backward
+        return embeds, code
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the gradient kernels are not themselves differentiable
+    def backward(ctx, g_embeds, g_code):
+        x, saved, keep, *params = ctx.saved_tensors
+        mod, need = ctx.mod, ctx.needs_input_grad
+        B, T = x.shape[0], x.shape[1]
+        gx = torch.empty_like(x) if need[1] else None
+        gp = [torch.empty_like(_param(q)) if n else None for q, n in zip(params, need[3:])]
+        at = lambda t: None if t is None else t.data_ptr()                                   # noqa: E731
+        head, alive = mod._desc()
+        n = len(_lib.UmoedLayerGrads.NAMES)
+        layers = (_lib.UmoedLayerGrads * head.n_layers)(*[_lib.UmoedLayerGrads(*[at(t) for t in gp[1 + n * i:1 + n * (i + 1)]])
+                                                         for i in range(head.n_layers)])
+        grads = _lib.UmoedHeadGrads(layers, at(gp[0]), at(gp[-2]), at(gp[-1]), at(gx))
+        up = g_embeds.detach().float().contiguous()
+        wsb = C.c_size_t(0)
+        lib.xmh_head_umoed_train_bytes(B, T, C.byref(head), C.byref(wsb))
+        ws = workspace(wsb.value, x.device)
+        check(lib.xmh_head_umoed_backward(C.byref(head), ptr(x), ptr(keep), ctx.p, ptr(up), B, T, ptr(saved), saved.numel(),
+                                          C.byref(grads), 0, ptr(ws), ws.numel(), current_stream()), "xmh_head_umoed_backward")
+        del alive
+        if gx is not None:
+            gx = gx.reshape(ctx.meta[0]).to(ctx.meta[1])
+        return (None, gx, None, *gp)
+
+
 class UMoEDTokenHash(nn.Module):
     """reference TokenHash: ``decoder_learned_parameters`` [M, d], ``decoder.layers.{i}`` (a Soft-MoE decoder at the embedding width
     with ``MoE``, else nn.TransformerDecoder's layers at ``hidden_dim`` behind ``first_layer``), ``classifier`` Linear(d, V).
@@ -174,6 +213,8 @@ class UMoEDTokenHash(nn.Module):
             raise NotImplementedError("UMoED head: MoE: True with hidden_dim %d != embed_dim %d: the reference builds the Soft-MoE decoder at "
                                       "the embedding width and the learned rows at hidden_dim, and fails in its first forward" % (hidden_dim, embedDim))
         self.hash_func, self.merge_func, self.MoE = hash_func, merge_func, bool(MoE)
+        self.dropout_p = float(dropout)
+        self.generator = None                 # torch.Generator of the module's device for the dropout masks; None: the global one
         self.heads, self.num_experts, self.slots_per_expert = decoder_heads, num_experts, slots_per_expert
         if MoE:
             self.decoder = _Decoder([_SoftMoEDecoderLayer(embedDim, decoder_heads, num_experts, slots_per_expert, dim_feedforward, dropout)
@@ -242,7 +283,8 @@ class UMoEDTokenHash(nn.Module):
     def forward(self, tokens):
         """tokens [B, T, E] -> (embeds [B, M, V], code [B, M log2 V] or [B, V]); inference only"""
         if self.training or (torch.is_grad_enabled() and (tokens.requires_grad or any(p.requires_grad for p in self.parameters()))):
-            raise NotImplementedError("UMoED head: the backward of the decoder head is not built; run it in eval mode under torch.no_grad()")
+            raise NotImplementedError("UMoED head: the backward of the decoder head is not built behind forward(); run it in eval mode under "
+                                      "torch.no_grad(), or train through forward_train (encode_img_train / encode_txt_train)")
         head, keep = self._desc()
         if tokens.dim() != 3 or tokens.shape[2] != head.E:
             raise ValueError("a UMoED head takes [B, T, %d] tokens, got %s" % (head.E, tuple(tokens.shape)))
@@ -255,6 +297,80 @@ class UMoEDTokenHash(nn.Module):
         check(lib.xmh_head_umoed(C.byref(head), ptr(x), B, T, ptr(embeds), ptr(code), ptr(ws), nbytes, current_stream()), "xmh_head_umoed")
         del keep
         return embeds, code
+
+    # ---- train mode ------------------------------------------------------------------------------------------------------
+    def head_params(self):
+        """the parameters in the order of xmh_umoed_head_grads: the learned rows, each layer's nineteen (UmoedLayerGrads.NAMES), the
+        classifier's weight and bias"""
+        out = [self.decoder_learned_parameters]
+        for y in self.decoder.layers:
+            out += [y.norm1.weight, y.norm1.bias, y.self_attn.in_proj_weight, y.self_attn.in_proj_bias, y.self_attn.out_proj.weight,
+                    y.self_attn.out_proj.bias, y.norm2.weight, y.norm2.bias, y.multihead_attn.in_proj_weight, y.multihead_attn.in_proj_bias,
+                    y.multihead_attn.out_proj.weight, y.multihead_attn.out_proj.bias, y.norm3.weight, y.norm3.bias, y.linear.weight,
+                    y.linear.bias, y.moe.phi, y.moe.experts.weight, y.moe.experts.bias]
+        return out + [self.classifier.weight, self.classifier.bias]
+
+    def _check_trainable(self):
+        if not self.MoE:
+            raise NotImplementedError("UMoED head: MoE: False (the plain decoder) has no train mode; only the Soft-MoE decoder does")
+        if self.first_layer is not None:
+            raise NotImplementedError("UMoED head: a first_layer (hidden_dim != embed_dim) has no train mode")
+
+    def keep_sections(self, B: int, T: int):
+        """the element counts of the six keep-mask sections of one layer, in the library's order (drop1 .. drop6)"""
+        M, d = self.decoder_learned_parameters.shape
+        F = self.decoder.layers[0].linear.weight.shape[0]
+        return [B * self.heads * M * M, B * M * d, B * self.heads * M * T, B * M * d, B * M * F, B * M * d]
+
+    def draw_keep_mask(self, B: int, T: int, device):
+        """the keep bytes of one train-mode forward, uint8 [layers x sum(keep_sections)] on the device, or None when p == 0.  Drawn by
+        torch from ``self.generator`` as a byte Bernoulli(1 - p): the library draws no random numbers"""
+        self._check_trainable()
+        p = self.dropout_p
+        if p <= 0.0:
+            return None
+        if p >= 1.0:
+            raise ValueError("dropout p = %g: nothing would be kept" % p)
+        n = sum(self.keep_sections(B, T)) * len(self.decoder.layers)
+        return torch.empty(n, dtype=torch.uint8, device=device).bernoulli_(1.0 - p, generator=self.generator)
+
+    def _run_train(self, tokens, keep):
+        """one train-mode forward call -> (embeds, code, the tokens as the kernels read them, the record the call filled)"""
+        self._check_trainable()
+        head, alive = self._desc()
+        if tokens.dim() != 3 or tokens.shape[2] != head.E:
+            raise ValueError("a UMoED head takes [B, T, %d] tokens, got %s" % (head.E, tuple(tokens.shape)))
+        if not tokens.is_cuda:
+            raise RuntimeError("UMoED head in train mode needs CUDA/HIP tensors (got %s); there is no CPU fallback" % (tokens.device,))
+        x = ops._f32c(tokens.detach()).contiguous()
+        B, T = x.shape[0], x.shape[1]
+        want = lib.xmh_umoed_keep_bytes(B, T, C.byref(head))          # 0 outside the bounds: the call below then says which one
+        if keep is not None and want and (keep.dtype != torch.uint8 or keep.numel() != want):
+            raise ValueError("UMoED head: a keep mask of %d %s where B=%d T=%d take %d bytes (six sections per layer, keep_sections)"
+                             % (keep.numel(), keep.dtype, B, T, want))
+        wsb = C.c_size_t(0)
+        nbytes = lib.xmh_head_umoed_train_bytes(B, T, C.byref(head), C.byref(wsb))
+        saved, ws = workspace(nbytes, x.device), workspace(wsb.value, x.device)     # 0 outside the bounds: the call below then says which one
+        embeds = torch.empty(B, head.M, head.V, dtype=torch.float32, device=x.device)
+        code = torch.empty(B, self.code_width, dtype=torch.float32, device=x.device)
+        check(lib.xmh_head_umoed_train_forward(C.byref(head), ptr(x), ptr(keep), self.dropout_p, B, T, ptr(embeds), ptr(code), ptr(saved), nbytes,
+                                               ptr(ws), wsb.value, current_stream()), "xmh_head_umoed_train_forward")
+        del alive
+        return embeds, code, x, saved
+
+    def forward_train(self, tokens, keep=_DRAW):
+        """tokens [B, T, E] -> (embeds [B, M, V], code), the train-mode head whatever ``self.training`` says, behind torch.autograd when
+        anything requires grad.  `keep` overrides the drawn mask (uint8, draw_keep_mask's layout, or None for no dropout) -- tests replay
+        stored masks.  The code carries no gradient."""
+        if keep is _DRAW:
+            keep = self.draw_keep_mask(tokens.shape[0], tokens.shape[1], tokens.device)
+        elif keep is not None:
+            keep = keep.to(device=tokens.device, dtype=torch.uint8).contiguous().reshape(-1)
+        params = self.head_params()
+        if torch.is_grad_enabled() and (tokens.requires_grad or any(q.requires_grad for q in params)):
+            self._check_trainable()
+            return _UMoEDHeadTrain.apply(self, tokens, keep, *params)
+        return self._run_train(tokens, keep)[:2]
 
 
 class UMoEDHashLayer(nn.Module):
@@ -284,6 +400,14 @@ class UMoEDHashLayer(nn.Module):
     def encode_txt(self, token_embeds):
         # without fusion the reference's encode_txt still runs img_token_hash (hash_moe.py:130-138; txt_token_hash is never used): kept
         return (self.hash_module if self.fusion else self.img_token_hash)(token_embeds)
+
+    def encode_img_train(self, token_embeds, keep=_DRAW):
+        """the train-mode head (dropout, a graph when anything requires grad); `keep` replays a stored mask"""
+        return (self.hash_module if self.fusion else self.img_token_hash).forward_train(token_embeds, keep)
+
+    def encode_txt_train(self, token_embeds, keep=_DRAW):
+        # img_token_hash without fusion, as encode_txt: txt_token_hash never receives a gradient (reference hash_moe.py:130-138)
+        return (self.hash_module if self.fusion else self.img_token_hash).forward_train(token_embeds, keep)
 
     def encode_imgAndtxt(self, img_embeds, txt_embeds):
         """the tokens of both modalities stacked along T through ``hash_module`` (only there with fusion, as in the reference)"""
@@ -376,6 +500,19 @@ class UMoED(BaseModel):
             return self.object_function(img_embeds=img_embeds, img_hash=img_hash, txt_embeds=txt_embeds, txt_hash=txt_hash, fusion_embeds=None,
                                         fusion_hash=None, labels=labels, indexs=indexs)
         return img_embeds, img_hash, txt_embeds, txt_hash, None, None
+
+    def forward_train(self, image, text):
+        """the six outputs of ``forward`` with a graph through the head AND both towers (encode_*_train_tokens)"""
+        cls_token, seq_tokens = self.backbone.encode_image_train_tokens(image)
+        _, txt_tokens, _ = self.backbone.encode_text_train_tokens(text)
+        return (*self.hash.encode_img_train(self._image_tokens(cls_token, seq_tokens)), *self.hash.encode_txt_train(txt_tokens.permute(1, 0, 2)),
+                None, None)
+
+    def forward_train_heads(self, image, text):
+        """the same six with a graph through the head only: the towers run as in ``forward`` under no_grad (a frozen backbone)"""
+        with torch.no_grad():
+            img_tokens, txt_tokens = self.get_features(image, text)
+        return (*self.hash.encode_img_train(img_tokens), *self.hash.encode_txt_train(txt_tokens), None, None)
 
     def similarity_loss(self, img_embeds, img_hash, txt_embeds, txt_hash, fusion_embeds=None, fusion_hash=None, labels=None, indexs=None, **kwags):
         """-> (loss, loss_dict) from one forward call of the library; the dictionary is detached"""

@@ -406,11 +406,12 @@ class DIMCHTrainer(_MethodTrainer):
 class UMoEDTrainer(_MethodTrainer):
     """runners/UMoED/runner.py: the model's encoders return (token logits, code); evaluation reports four mAPs (i->t, t->i, i->i, t->t),
     keeps a best epoch for each and writes four .mat files with a fusion stream beside the usual keys.  The linear-subspace and tanh codes
-    are quantised by their sign, the pair softmax by its argmax.  The decoder head has no backward here, so ``train_epoch`` raises.
-    compute_loss (:126-134): the objective of xmh_umoed.hip behind torch.autograd, differentiable with respect to the two logit tensors."""
+    are quantised by their sign, the pair softmax by its argmax.  Training (:134-155) is ``train_epoch_decoder`` / ``train_decoder``, which
+    ``run()`` enters with ``is_train: true``: the decoder head in train mode with its backward and both towers; ``train_epoch``
+    and ``train()`` keep raising and name them.  compute_loss (:126-134): the objective of xmh_umoed.hip behind torch.autograd, differentiable with respect to the two logit tensors."""
 
     MODEL_ARCH = "UMoED"
-    # the six outputs of the model's forward; there is no train-forward yet (train_epoch raises), the names are what one would return
+    # the six outputs of the model's forward and of its forward_train
     LOSS_INPUTS = FORWARD_OUTPUTS = ("img_embeds", "img_hash", "txt_embeds", "txt_hash", "fusion_embeds", "fusion_hash")
     LOSS_OPTIONAL = ("fusion_embeds", "fusion_hash")
     BITS_FROM = "img_embeds"
@@ -432,12 +433,29 @@ class UMoEDTrainer(_MethodTrainer):
         return {"txt_token_size": self.cfg.dataset.get("max_word", 32)}
 
     def train_epoch(self, epoch: int):
-        raise NotImplementedError("UMoEDTrainer.train_epoch: the backward of the decoder head is not built (xmh_head_umoed is inference only: "
-                                  "self- and cross-attention, the Soft-MoE routing and the experts have no gradient kernels); the objective "
-                                  "and its gradient are (compute_loss), and valid() / test() evaluate a trained checkpoint")
+        raise NotImplementedError("UMoEDTrainer.train_epoch: the backward of the decoder head is not built behind this name (xmh_head_umoed is "
+                                  "inference only); the reference's epoch, through the train-mode head and both towers, is train_epoch_decoder "
+                                  "(train_decoder() and run() with is_train run it)")
+
+    def train_epoch_decoder(self, epoch: int):
+        """runners/UMoED/runner.py:134-155: the backbone at backbone_lr and the hash layer at lr through UMoED.forward_train"""
+        _train_epoch(self, epoch)
+
+    def train_decoder(self):
+        """the reference's train() with this epoch: every epoch followed by valid(), then the FINISHED line"""
+        for epoch in range(self.epochs):
+            self.train_epoch_decoder(epoch)
+            self.valid(epoch, k=self.top_k)
+        self._log_finished()
+
+    def run(self):
+        if self.is_train:
+            self.train_decoder()
+        else:
+            self.test()
 
     def _log_finished(self):
-        """runners/UMoED/runner.py:245-251: the line that ends train(), which with ``is_train: true`` raises at once in train_epoch"""
+        """runners/UMoED/runner.py:245-251: the line that ends train_decoder()"""
         self.logger.info(f">>>>>>> FINISHED >>>>>> Best epoch, I-T: {self.best_epoch_i2t}, mAP: {self.max_mapi2t}, T-I: {self.best_epoch_t2i}, "
                          f"mAP: {self.max_mapt2i}, I-I: {self.best_epoch_i2i}, MAP: {self.max_mapi2i}, T-T: {self.best_epoch_t2t}, MAP: {self.max_mapt2t}")
 

@@ -1078,6 +1078,48 @@ int xmh_head_umoed(const xmh_umoed_head* h, const float* tokens, int64_t B, int 
                    xmh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * UMoED decoder head in train mode and its backward (reference hash/block/transformer.py SoftMoEDecoderLayer with its dropouts;
+ * csrc/xmh_umoed_grad.hip).  One dropout probability p at six sites per layer, every kept entry scaled by 1 / (1 - p):
+ *   u1 = x  + drop2(out_proj(drop1(softmax(q k^T / 8)) v))   q, k, v from x                 x1 = LN1(u1)
+ *   u2 = x1 + drop4(out_proj(drop3(softmax(q k^T / 8)) v))   q from x1, k | v from tokens   x2 = LN2(u2)
+ *   h  = drop5(relu(linear(x2)));  the Soft-MoE of h as in inference -> Y;  u3 = x2 + drop6(Y);  x = LN3(u3)
+ * drop1 and drop3 act on the attention probabilities after the softmax and before P V.  No mask on the keys.
+ * The library draws no random numbers: `keep` is the caller's buffer of 0 / 1 bytes, xmh_umoed_keep_bytes(B, T, h) long; per layer, in
+ * this order, [B, heads, M, M] (drop1), [B M, d] (drop2), [B, heads, M, T] (drop3), [B M, d] (drop4), [B M, F] (drop5), [B M, d] (drop6),
+ * and the layers follow one another.  keep == NULL: no dropout (p is ignored), and embeds and code equal xmh_head_umoed's to the bit
+ * (the same launches in the same order).
+ * xmh_head_umoed_train_bytes -> the bytes of the record `saved` that the forward fills and the backward reads, and through
+ * workspace_bytes (may be NULL) the bytes of the workspace either call needs; both 0 outside the bounds.  Both buffers 256-byte aligned
+ * (XMH_ENOMEM when shorter).  The record keeps every layer's intermediate rows but not the attention probabilities, which the backward
+ * recomputes from q and k.
+ * xmh_head_umoed_backward: d_embeds [B, M, V] is the upstream of embeds (the code carries no gradient).  grads: one
+ * xmh_umoed_layer_grads per layer (host array, or NULL for none), d_queries [M, d], d_cls_w [V, d], d_cls_b [V], d_tokens [B, T, E].
+ * Every pointer may be NULL: that gradient is not formed, and nothing is written there.  Parameter gradients are written, or added to
+ * when accumulate != 0; d_tokens is always written.  ca_in_w's gradient: rows 0 : d from the queries' side, rows d : 3 d from the tokens'.
+ * Scope (XMH_ENOTSUP otherwise, the text names the cause): moe != 0 (the plain decoder has no train mode); first_w == NULL (nor has a
+ * first layer); ln_eps == 1e-5 (what the LayerNorm backward assumes); and the bounds of xmh_head_umoed: d / heads == 64; M, T <= 128
+ * (a thread per attention row); d <= 1024; F <= 4096; S <= 256; V <= 256; B max(M, T) <= 32768, B <= 65535.  p in [0, 1) with a mask.
+ * Exact fp32, no allocation, no host synchronisation, no float atomics, one fixed order per sum: two calls agree to the bit.  Argument and
+ * bound errors are reported before any launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_umoed_layer_grads {
+    float *ln1_g, *ln1_b, *sa_in_w, *sa_in_b, *sa_out_w, *sa_out_b;
+    float *ln2_g, *ln2_b, *ca_in_w, *ca_in_b, *ca_out_w, *ca_out_b;
+    float *ln3_g, *ln3_b, *lin_w, *lin_b, *phi, *exp_w, *exp_b;
+} xmh_umoed_layer_grads;
+typedef struct xmh_umoed_head_grads {
+    const xmh_umoed_layer_grads* layers; /* host array [n_layers], or NULL */
+    float *d_queries, *d_cls_w, *d_cls_b, *d_tokens;
+} xmh_umoed_head_grads;
+size_t xmh_head_umoed_train_bytes(int64_t B, int T, const xmh_umoed_head* h, size_t* workspace_bytes);
+size_t xmh_umoed_keep_bytes(int64_t B, int T, const xmh_umoed_head* h);
+int xmh_head_umoed_train_forward(const xmh_umoed_head* h, const float* tokens, const uint8_t* keep, float p, int64_t B, int T, float* embeds,
+                                 float* code, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, xmh_stream_t stream);
+int xmh_head_umoed_backward(const xmh_umoed_head* h, const float* tokens, const uint8_t* keep, float p, const float* d_embeds, int64_t B, int T,
+                            const void* saved, size_t saved_bytes, const xmh_umoed_head_grads* grads, int accumulate, void* ws, size_t ws_bytes,
+                            xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * UMoED: the objective of the pairwise / cosine / triplet family (reference models/UMoED/UMoED.py similarity_loss with
  * distance/__init__.py pairwise_distance) and its gradient.  e_img, e_txt [B, M, V] fp32, lab: xmh_pack_labels of the [B, C] labels.
  *   x, y = F.normalize (eps 1e-12) of the rows;  a, b = softmax(x / extreme_T), softmax(y / extreme_T) when extreme, else x, y
