@@ -556,6 +556,8 @@ Geom launch_geom(const Launch& l, const xmh_scan_plan& p, int64_t Q) {
         g.lds = nb * (64 / l.S) * 8; g.nqt = (int)p.nqtile * l.S;
     } else if (l.kern == Kern::kHistB) {                 // (grid and LDS are launch_scan_hist_bits' own: xmh_scan_bits.hip)
         g.nqt = (int)(p.qpad / (16 * kMfmaWaves));
+    } else if (l.kern == Kern::kHistR2 || l.kern == Kern::kHistR2w) {      // tables of bucket rows x 512 B, two query groups of every wave each (xmh_scan_mfma.h, r2_cell)
+        g.lds = r2_lds_bytes(l.S, (int)nb); g.nqt = (int)(p.qpad / (l.NW * l.S * 16));
     } else {
         g.lds = (size_t)l.NW * l.S * nb * 16 * (ap ? 8 : 4); g.nqt = (int)(p.qpad / (l.NW * l.S * 16));
     }
@@ -954,12 +956,26 @@ bool r2_selfcheck_ok() {
     std::lock_guard<std::mutex> lock(mu);
     if (state[dev]) return state[dev] == 1;
     state[dev] = 1;                                       // the evaluations below pin Overrides::mfma and do not ask again
-    const int64_t Q = 200, R = 9000;
+    const int64_t Q = 272, R = 9000;                      // one whole block of k_scan_hist_r2 (256 queries) and a ragged one
     bool same = true, ran = true;
+    // k_scan_hist_r2 / r2w take their counter addresses as offsets from LDS address 0 (xmh_scan_mfma.h, r2_cell): the dynamic array has to
+    // start there, so none of their instances may have static LDS
+    {
+        const void* const r2_kernels[] = {reinterpret_cast<const void*>(k_scan_hist_r2<1, 4, 4, true>), reinterpret_cast<const void*>(k_scan_hist_r2<1, 4, 4, false>),
+                                          reinterpret_cast<const void*>(k_scan_hist_r2<2, 4, 4, true>), reinterpret_cast<const void*>(k_scan_hist_r2<2, 4, 4, false>),
+                                          reinterpret_cast<const void*>(k_scan_hist_r2w<1, 4, 2, true>), reinterpret_cast<const void*>(k_scan_hist_r2w<1, 4, 2, false>),
+                                          reinterpret_cast<const void*>(k_scan_hist_r2w<2, 4, 2, true>), reinterpret_cast<const void*>(k_scan_hist_r2w<2, 4, 2, false>)};
+        for (const void* k : r2_kernels) {
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, k) != hipSuccess) ran = false;
+            else if (fa.sharedSizeBytes != 0) same = false;
+        }
+    }
     // two code words, one + a partial one, <= 32 bits (all k_scan_hist_r2), 65..128 bits (k_scan_hist_r2w), with 80 classes; then both
     // kernels with 128 classes and labels made for the FP4 label tile (below)
     const int cases[6][2] = {{64, 80}, {40, 80}, {16, 80}, {100, 80}, {64, 128}, {100, 128}};
     for (const auto& kc : cases) {
+        if (!ran || !same) break;
         const int K = kc[0], C = kc[1], LW = (C + 31) / 32;
         const int W = (K + 31) / 32;
         std::vector<uint32_t> qb(Q * W), ql(Q * LW), rb(R * W), rl(R * LW);
@@ -988,6 +1004,22 @@ bool r2_selfcheck_ok() {
                 else if (i % 3 == 1) for (int w = 0; w < LW; ++w) rl[i * LW + w] = 0u;
             }
             for (int w = 0; w < LW; ++w) ql[1 * LW + w] = rl[2 * LW + w] = rl[5000 * LW + w] = 0xffffffffu;
+        }
+        // the highest counter addresses of both kernels -- the last wave's last query group of a block: queries 240..255 of k_scan_hist_r2's 256,
+        // 112..127 of k_scan_hist_r2w's 128 -- at both ends of the bucket range: items equal to the query (distance 0) and to its complement
+        // (distance K), each once sharing a class with the query and once without a label, in whole batches and in the ragged last one
+        {
+            const int64_t q0 = K <= 64 ? 240 : 112;
+            for (int64_t t = 0; t < 16; ++t) {
+                const int64_t q = q0 + t;
+                ql[q * LW] |= 1u;
+                for (int set = 0; set < 2; ++set)
+                    for (int v = 0; v < 4; ++v) {
+                        const int64_t i = (set ? R - 64 : 128) + 4 * t + v;
+                        for (int w = 0; w < W; ++w) rb[i * W + w] = (v & 2) ? ~qb[q * W + w] & (w == W - 1 ? last : 0xffffffffu) : qb[q * W + w];
+                        for (int w = 0; w < LW; ++w) rl[i * LW + w] = (v & 1) ? 0u : ql[q * LW + w];
+                    }
+            }
         }
         std::vector<uint32_t> h1, h0;
         std::vector<double> a1, a0;

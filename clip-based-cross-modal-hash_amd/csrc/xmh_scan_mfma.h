@@ -6,6 +6,7 @@
 #include "xmh_common.h"
 #include "xmh_scan_map.h"
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -38,11 +39,11 @@ __device__ __forceinline__ bool map_block(const ScanArgs& a, int& chunk_id, int&
 // Hamming distance and label overlap of 16 gallery items x 16 queries are i8 dot-product tiles -- literally what the
 // reference computes, B1 @ B2^T and query_L @ retrieval_L^T (common/calc_utils.py:51-56, :72) -- so they go to
 // v_mfma_i32_16x16x64_i8 instead of 8 VALU instructions per pair:
-//   * address chain: item bytes 0 / 1 (2 in the odd registers of a tile), query bytes +-SCALE (SCALE = bytes of one bucket row of the LDS
-//     counters, halved against the item bytes worth 2); started from the lane's counter base + SCALE * popcount(query), the accumulator
+//   * address chain: item bytes 0 / w (pass 1: w = 8, 16, 32, 64 in the four registers of a tile; k_scan_ap_r2: 2 and 4), query bytes +-SCALE / w
+//     (SCALE = bytes of one bucket row of the LDS counters); started from the lane's counter base + SCALE * popcount(query), the accumulator
 //     IS the LDS byte address of counter [distance][query], since distance = popcount(q) + sum x_i (1 - 2 q_i);
-//   * 2 * distance chain (pass 1 with a pair cache): the same item bytes against query bytes +-2; its low byte is the distance half of the
-//     cache entry (distance << 1 | relevant);
+//   * pass 1 with a pair cache: SCALE = 512 and a register part of the address below 256 put 2 * distance into byte 1 of that address --
+//     the distance half of the cache entry (distance << 1 | relevant) with no chain of its own (round 9; scan_hist_r2_body);
 //   * label chain: item and query label bits as bytes 0 / 1.  Pass 1 starts it at 0x10000, so that min(acc, 0x10001) is the add operand of
 //     (all << 16 | relevant) counters and its low byte the relevance bit (a chunk has at most kMaxChunk items: the 16-bit halves hold).
 //     Pass 2 (k_scan_ap_r2) has query label bytes 0 / -1 and takes max(acc, -1) as the mask 0 / ~0.  65-128 classes (three or four label
@@ -99,16 +100,27 @@ __device__ __forceinline__ v4i label_item_f4(uint32_t w) {
 //     an MFMA result is asm volatile in program order, software-pipelined one (item group, query group) behind its MFMAs, so
 //     the MFMA -> VALU / DS read hazard (8 wait states, hipcc inserts them only for its own instructions) is covered by the 12
 //     consumer instructions of the previous group that sit in between.
-//   * the pair-cache byte comes out of the matrix pipe too: a second code chain with query bytes -+2 IS 2 * distance, and the label
-//     chain counts into (all << 16 | relevant) counters -- started at 0x10000, min(acc, 0x10001) is the add operand and its low byte the
-//     relevance bit -- so one SDWA OR per pair (byte0(2d) | byte0(inc) written to byte j of the cache word) assembles the entry.
+//   * the pair-cache byte comes out of the matrix pipe too, and out of the SAME chain (round 9): counter rows are 512 bytes and the
+//     register part of the address stays below 256, so byte 1 of the address IS 2 * distance.  The label chain counts into
+//     (all << 16 | relevant) counters -- started at 0x10000, min(acc, 0x10001) is the add operand and its low byte the relevance bit --
+//     so one SDWA OR per pair (byte1(address) | byte0(inc) written to byte j of the cache word) assembles the entry.  (Rounds 3-8 ran a
+//     third chain with query bytes -+2 for it: 0.75 MFMA per 64 pairs, now 0.5.)
 //   * the A operands are built in registers from the packed gallery words (round 4): no operand image, no LDS-DMA, no ring, no
-//     barrier.  Lane (row, slot) loads the word of its item that holds its 16 bits (fetched one batch ahead) and spreads it with 5-6
+//     barrier.  Lane (row, slot) loads the word of its item that holds its 16 bits (fetched one batch ahead) and spreads it with 5
 //     VALU operations per tile; waves are independent, LDS holds the counters only.
 //   * NQ query groups of 16 per wave: every tile built feeds NQ MFMA groups.
-// Counter rows are 64 bytes (16 queries x u32); chunks hold up to 32768 items (16-bit halves).  Round 3's form of the same statements
-// (k_scan_hist_m2: operand images through a 3-deep LDS ring) and round 2's k_scan_hist_m were removed in round 5 (DESIGN 3.1 keeps their
-// measurements).
+// THE COUNTER LAYOUT (r2_cell below).  A table is 65 bucket rows of 512 bytes = 128 u32 counters: columns 64 (h & 1) + 16 wave + query for
+// query groups h = 2 t and 2 t + 1 of table t, so NQ = 4 groups take two tables and the block (65 + nb) x 512 bytes.  The VGPR address a
+// chain produces is table-relative, 512 d + 64 wave + 4 query; which half of a row and which table is the `offset:` immediate of the
+// ds_add_u32 -- 256 (h & 1) + 65 x 512 (h >> 1), a constant of each statement, the table distance therefore 65 rows whatever K is.  All of
+// it is an LDS address only because the dynamic array starts at LDS address 0: THESE KERNELS MUST NOT HAVE STATIC LDS (the self-check of
+// xmh_scan.hip asks the runtime for their static size and refuses them if it is not 0).  The two lane groups of a ds_add_u32 that hit one
+// row now always share banks (rows are a multiple of the 256-byte bank span): priced in profiles/r09_scan_addr_byte.txt.
+// THE SCALING.  The products of the chain have to be exactly +-512 in i8: the item bits stand at byte bits 3..6, worth 8, 16, 32 and 64
+// (one rotate of the packed word and four masks), the query bytes of the four registers are +-64, +-32, +-16 and +-8, and the chain
+// starts at 64 wave + 4 query + 512 popcount(query).  Chunks hold up to 32768 items (16-bit halves).  Round 3's form of the same
+// statements (k_scan_hist_m2: operand images through a 3-deep LDS ring) and round 2's k_scan_hist_m were removed in round 5 (DESIGN 3.1
+// keeps their measurements).
 //
 // THE HAZARD LIST of the hand-written MFMA statements (this body, scan_hist_r2w_body, k_scan_ap_r2).  One asm statement = the MFMAs of one
 // (16-item group, 16-query group) with the consumer instructions of the PREVIOUS group between them.  hipcc sees none of the following,
@@ -126,27 +138,44 @@ __device__ __forceinline__ v4i label_item_f4(uint32_t w) {
 //         stages per statement.  MFMA -> MFMA srcC dependencies are interlocked in hardware.
 // tools/isa_hazards.py (tests/test_isa_hazards.py) checks the emitted ISA of every build for the wait states of (i) and (iii).
 // ---------------------------------------------------------------------------------------------------
+constexpr int kR2TableRows = 65, kR2RowBytes = 512;                 // an instruction immediate holds the table distance: 65 rows for every K
+// u32 index of counter [query group h][distance d][query ql] of a wave in the block's LDS: the one place that knows the layout (zeroing,
+// padding fix-up and epilogue go through it; the statements' `offset:` immediates are r2_imm, the byte offset of its (h, 0, 0) part)
+__device__ __forceinline__ int r2_cell(int wave, int h, int d, int ql) {
+    return ((h >> 1) * kR2TableRows + d) * (kR2RowBytes / 4) + (h & 1) * 64 + wave * 16 + ql;
+}
+constexpr int r2_imm(int h) { return (h & 1) * 256 + (h >> 1) * (kR2TableRows * kR2RowBytes); }
+// dynamic LDS of a block of k_scan_hist_r2 with NQ query groups per wave: full tables but the last, which ends with bucket row nb - 1
+constexpr size_t r2_lds_bytes(int nq, int nb) { return (size_t)(((nq + 1) / 2 - 1) * kR2TableRows + nb) * kR2RowBytes; }
+template <typename F, int... I>
+__device__ __forceinline__ void r2_each(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+
 template <int NML, int NW, int NQ, bool CACHE>
 __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* __restrict__ chunk_hist, uint4* __restrict__ pair_cache) {
     static_assert(NML == 1 || NML == 2, "one i8 label tile (at most 64 classes) or one FP4 label tile (65-128 classes)");
+    static_assert(NW <= 4, "the register part of a counter address, 64 wave + 4 query, stays below 256: byte 1 of the address is 2 * distance");
+    static_assert(r2_imm(NQ - 1) < 65536, "the offset: immediate of ds_add_u32 has 16 bits");
     constexpr bool F4 = NML == 2;                                    // the label tile is FP4 (E2M1) with K = 128: see label_query_f4 / label_item_f4
-    constexpr int NMI = 2, NMQ = 3;                                  // operand tiles per item group (code, label) and per query group (address, 2 * distance, label)
+    constexpr int NMI = 2, NMQ = 2;                                  // operand tiles per item group (code, label) and per query group (address, label)
     constexpr bool REGS = true;                                      // (the operands come from the packed words; kept as a name in the expressions below)
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters
+    // (NQ + 1) / 2 tables x [65 (the last: nb)][128] u32 counters, at LDS address 0: no static LDS in this kernel (layout: above this function)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     int chunk_id, qtile;
     if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts tiles of NW * NQ * 16 queries here
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ql = lane & 15, slot = lane >> 4;
     const int t16 = (qtile * NW + wave) * NQ;                        // first 16-query tile of this wave
     const int ncell = a.nb * 16;
-    uint32_t* cnt = lds + (wave * NQ) * ncell;
-    for (int e = lane; e < NQ * ncell; e += 64) cnt[e] = 0u;
-    v4i bq[NQ][NMQ], cq[NQ], kqv[REGS ? NQ : 1];                    // the image kernels start every 2 * distance chain at K: one quad
+#pragma unroll
+    for (int h = 0; h < NQ; ++h)                                     // a wave clears, counts into and writes out its own columns only: no barrier
+        for (int e = lane; e < ncell; e += 64) lds[r2_cell(wave, h, e >> 4, e & 15)] = 0u;
+    v4i bq[NQ][NMQ], cq[NQ];
     bool valid[NQ];
     // REGS: byte b of operand register j of lane (row, slot) stands for bit 4 (slot & 1) + j + 8 b of word slot >> 1 (of the code, or of the
-    // 64 label bits of a tile): (word >> (4 (slot & 1) + j)) & 0x01010101 leaves those four bits each alone in its byte, worth 1.  Item bytes
-    // are therefore 0 / 1 (not -+1): distance = popcount(q) + sum x_i (1 - 2 q_i), so the query bytes are +-64 (counter rows of 64 bytes) for
-    // the address chain, +-2 for the 2 * distance chain, and the chains start at 64 popcount(q) / 2 popcount(q) more.
+    // 64 label bits of a tile).  On the query side (word >> (4 (slot & 1) + j)) & 0x01010101 leaves those four bits each alone in its byte;
+    // the item side leaves bit j at byte bit 3 + j, worth 8 << j (build()).  Item bytes are 0 / positive (not -+1): distance = popcount(q) +
+    // sum x_i (1 - 2 q_i), so the query bytes of register j are +-(64 >> j) -- every product +-512, one counter row -- and the chain starts
+    // at 512 popcount(q) more.
     const int rsh = 4 * (slot & 1), rwi = slot >> 1;
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
@@ -164,36 +193,29 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
             for (int j = 0; j < 4; ++j) {
                 const uint32_t t = (qw >> j) & 0x01010101u;
                 const bool on = valid[h] && rwi < a.W;                 // no such code word (codes of at most 32 bits): zero operand, whatever the item lane holds
-                // registers 1 and 3 of an item tile hold their bits worth 2 (see build()): their query bytes are halved, the products stay +-64 / +-2
-                if (j & 1) {
-                    bq[h][0][j] = on ? (int)(0x20202020u ^ (t * 0xc0u)) : 0;     // +32 / -32 (0xe0)
-                    bq[h][1][j] = on ? (int)(0x01010101u ^ (t * 0xfeu)) : 0;     // +1 / -1
-                } else {
-                    bq[h][0][j] = on ? (int)(0x40404040u ^ (t << 7)) : 0;        // +64 / -64 (0xc0)
-                    bq[h][1][j] = on ? (int)(0x02020202u ^ (t * 0xfcu)) : 0;     // +2 / -2 (0xfe)
-                }
+                // register j of an item tile holds its bits worth 8 << j (see build()): +(64 >> j) = 0x40, 0x20, 0x10, 0x08 for a query bit
+                // of 0, -(64 >> j) = 0xc0, 0xe0, 0xf0, 0xf8 for a query bit of 1 (t has 0x01 in the bytes whose bit is set: no carries)
+                const uint32_t pos = 0x40u >> j, flip = pos ^ ((0x100u - pos) & 0xffu);
+                bq[h][0][j] = on ? (int)((0x01010101u * pos) ^ (t * flip)) : 0;
             }
             if constexpr (F4) {
-                bq[h][2] = label_query_f4(valid[h] && slot < a.LW ? a.qlab[q * a.LW + slot] : 0u, 0x2u);
+                bq[h][1] = label_query_f4(valid[h] && slot < a.LW ? a.qlab[q * a.LW + slot] : 0u, 0x2u);
             } else {
                 uint32_t lw = 0u;
                 if (valid[h] && rwi < a.LW) lw = a.qlab[q * a.LW + rwi];
                 lw >>= rsh;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bq[h][2][j] = (int)((lw >> j) & 0x01010101u);
+                for (int j = 0; j < 4; ++j) bq[h][1][j] = (int)((lw >> j) & 0x01010101u);
             }
-            const int k2 = 2 * pcq;
-            kqv[h] = v4i{k2, k2, k2, k2};
         }
-        const int c0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(cnt + h * ncell) + ql * 4 + (valid[h] ? 64 * pcq : 0);
+        // table-relative (the statement's offset: immediate is r2_imm(h)); the register part 64 wave + 4 ql < 256 leaves byte 1 to 2 * distance
+        const int c0 = 64 * wave + ql * 4 + (valid[h] ? kR2RowBytes * pcq : 0);
         cq[h] = v4i{c0, c0, c0, c0};
     }
     v4i lab0 = {0x10000, 0x10000, 0x10000, 0x10000};
     asm volatile("" : "+v"(lab0));                                  // opaque: kept in VGPRs, not re-materialised from SGPRs inside the loop
 #pragma unroll
     for (int h = 0; h < NQ; ++h) asm volatile("" : "+v"(cq[h]));
-#pragma unroll
-    for (int h = 0; h < (REGS ? NQ : 1); ++h) asm volatile("" : "+v"(kqv[h]));
     const int64_t lo = (int64_t)chunk_id * a.chunk;
     const int64_t hi = (lo + a.chunk < a.R) ? lo + a.chunk : a.R;
     const int nbat = (int)((hi - lo + 63) >> 6);
@@ -234,18 +256,18 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
             }
         }
     };
-    // 6 operations per code tile: two shifts bring bits 0, 1 and bits 2, 3 of the lane's nibble to the bottom of their bytes, four masks
-    // pick them -- the odd ones worth 2 where they stand, which the halved query bytes above make up for (the products of both chains have
-    // to be exact: they are an address and a cache byte).  The label tiles only have to tell an overlap from none, so their bits stay where
+    // 5 operations per code tile: one rotate (v_alignbit_b32 w, w, s: right by 29 for the low nibble of a byte, by 1 for the high one)
+    // brings the lane's nibble to bits 3..6 of its byte, four masks pick the bits where they stand, worth 8, 16, 32 and 64 -- the query
+    // bytes above make every product +-512 (exact: the chain is an address and a cache byte); what the rotate wraps in from the neighbouring
+    // byte lies under none of the masks.  The label tiles only have to tell an overlap from none, so their bits stay where
     // one shift leaves them: y & (0x01010101 << j) is worth 2^j (1, 2, 4, 8) in its byte, the sum over the common labels is positive
     // exactly when there is one, and min(0x10000 + sum, 0x10001) is the add operand as before -- 5 operations.  The FP4 tile of 65-128
     // classes: label_item_f4, 5 operations as well (the two i8 tiles it replaces took 10).
+    const uint32_t rot = rsh ? 1u : 29u;
     auto build = [&](v4i (&At)[NMI], const uint32_t (&w)[NMI]) {
-        const uint32_t xa = w[0] >> rsh, xb = w[0] >> (rsh + 2);
-        At[0][0] = (int)(xa & 0x01010101u);
-        At[0][1] = (int)(xa & 0x02020202u);
-        At[0][2] = (int)(xb & 0x01010101u);
-        At[0][3] = (int)(xb & 0x02020202u);
+        const uint32_t x = __builtin_rotateright32(w[0], rot);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) At[0][j] = (int)(x & (0x08080808u << j));
         if constexpr (F4) {
             At[1] = label_item_f4(w[1]);
         } else {
@@ -271,13 +293,14 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
         v4i A[REGS ? 4 : 2][NMI];                                    // REGS: one set per group, each kept alive one statement past its last MFMA
 #endif
         uint32_t cw[NQ][4];
-        v4i addr_p, d2_p, lab_p;                                     // results of the previous (group, query group), consumed by the next statement
-        // One asm statement = the MFMAs of (group g, query group h) with the consumer instructions of the PREVIOUS pair between them:
-        // an MFMA occupies the matrix pipe for 16 cycles, the three VALU / DS instructions behind it issue meanwhile, so a wave
+        v4i addr_p, lab_p;                                           // results of the previous (group, query group), consumed by the next statement
+        // One asm statement = the two MFMAs of (group g, query group h) with the consumer instructions of the PREVIOUS pair between them:
+        // an MFMA occupies the matrix pipe for 16 cycles, the VALU / DS instructions behind it issue meanwhile, so a wave
         // keeps the pipe busy by itself (four MFMAs then twelve consumers left it idle half the time: 1830 cycles per batch measured
         // against 512 of MFMA work per wave).  Inside a statement the hazards are handled by hand (hipcc does not see them): hazards
         // (i)-(v) of the list above this function.
-        // The consumers: inc = min(label overlap chain, 0x10001) in place; cache byte j = byte0(2 * distance) | byte0(inc); the add.
+        // The consumers: inc = min(label overlap chain, 0x10001) in place; cache byte j = byte1(address) | byte0(inc); the add, whose
+        // offset: immediate (r2_imm of the PREVIOUS pair's query group) picks the half row and the table.
 // ablation switches of tools/proto_scan_ablate.hip (-DXMH_ABL_NOADD: the LDS adds become s_nop; -DXMH_ABL_NOMFMA: the MFMAs do; results are
 // wrong then, only the time means something): never set in the library build
 // wait states the statements carry by hand (XMH_R2_NOPS: tools/proto_scan_ablate.hip prices the alternatives; tools/isa_hazards.py R1-R3 gates them)
@@ -314,10 +337,13 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
 #undef XMH_VMIN
 #define XMH_VMIN "v_and_b32 "                                        // (ablation: a full-rate instruction of the same shape)
 #endif
+#if defined(XMH_ABL_NOMFMA) && !defined(XMH_ABL_NOADD)
+#define XMH_ABL_NOADD                                                // nothing writes the adds' addresses then: they would go wherever the registers point (a GPU memory fault)
+#endif
 #ifdef XMH_ABL_NOADD
-#define XMH_ADD(A, D) "s_nop 0\n\t"
+#define XMH_ADD(A, D, O) "s_nop 0\n\t"
 #else
-#define XMH_ADD(A, D) "ds_add_u32 " A ", " D "\n\t"
+#define XMH_ADD(A, D, O) "ds_add_u32 " A ", " D " offset:" O "\n\t"
 #endif
 #ifdef XMH_ABL_NOMFMA
 #define XMH_MFMA(D, A, B, C) "s_nop 0\n\t"
@@ -326,41 +352,44 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
 #define XMH_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 " D ", " A ", " B ", " C "\n\t"
 #define XMH_MFMA_F4(D, A, B, C) "v_mfma_f32_16x16x128_f8f6f4 " D ", " A ", " B ", " C " cbsz:4 blgp:4\n\t"
 #endif
-#define XMH_SDWA(J) "dst_sel:BYTE_" #J " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
+#define XMH_SDWA(J) "dst_sel:BYTE_" #J " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
 // The statements, once per label instruction (LAB = XMH_MFMA: the i8 tile of at most 64 classes; XMH_MFMA_F4: the FP4 tile of 65-128).
 // Both take four passes of the matrix pipe and need the same wait states in front of a VALU read, and both leave the bits the v_min reads.
+// Six consumers behind each MFMA; the SDWA inserts into the cache word alternate with the adds (hazard (ii)).
 #define XMH_R2_FUSED_CACHE(LAB)                                                                                                                   \
-    asm volatile(XMH_R2_OPEN LAB("%0", "%8", "%9", "%10")                                                                                         \
-                 XMH_VMIN "%4, 0x10001, %24\n\t" XMH_VMIN "%5, 0x10001, %25\n\t" XMH_VMIN "%6, 0x10001, %26\n\t" XMH_VMIN "%7, 0x10001, %27\n\t" \
-                 "v_or_b32_sdwa %3, %16, %4 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"                            \
-                 XMH_ADD("%20", "%4")                                                                                                             \
-                 XMH_MFMA("%1", "%11", "%12", "%13")                                                                                              \
-                 "v_or_b32_sdwa %3, %17, %5 " XMH_SDWA(1) XMH_ADD("%21", "%5") "v_or_b32_sdwa %3, %18, %6 " XMH_SDWA(2)                           \
-                 XMH_MFMA("%2", "%11", "%14", "%15")                                                                                              \
-                 XMH_ADD("%22", "%6") "v_or_b32_sdwa %3, %19, %7 " XMH_SDWA(3) XMH_ADD("%23", "%7")                                               \
-                 : "=&v"(lab), "=&v"(addr), "=&v"(d2), "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)                                        \
-                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]),             \
-                   "v"(d2_p[0]), "v"(d2_p[1]), "v"(d2_p[2]), "v"(d2_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]),         \
-                   "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])                                                                      \
+    asm volatile(XMH_R2_OPEN LAB("%0", "%7", "%8", "%9")                                                                                          \
+                 XMH_VMIN "%3, 0x10001, %17\n\t" XMH_VMIN "%4, 0x10001, %18\n\t" XMH_VMIN "%5, 0x10001, %19\n\t" XMH_VMIN "%6, 0x10001, %20\n\t" \
+                 "v_or_b32_sdwa %2, %13, %3 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                            \
+                 XMH_ADD("%13", "%3", "%21")                                                                                                      \
+                 XMH_MFMA("%1", "%10", "%11", "%12")                                                                                              \
+                 "v_or_b32_sdwa %2, %14, %4 " XMH_SDWA(1) XMH_ADD("%14", "%4", "%21") "v_or_b32_sdwa %2, %15, %5 " XMH_SDWA(2)                    \
+                 XMH_ADD("%15", "%5", "%21") "v_or_b32_sdwa %2, %16, %6 " XMH_SDWA(3) XMH_ADD("%16", "%6", "%21")                                 \
+                 : "=&v"(lab), "=&v"(addr), "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)                                                   \
+                 : "v"(At[1]), "v"(bql), "v"(lab0), "v"(At[0]), "v"(bqa), "v"(cqh),                                                                \
+                   "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3]),     \
+                   "n"(r2_imm(HP))                                                                                                                 \
                  : "memory")
+// (round 9: two adds in front of the address MFMA, or one, measured the same as all four behind it: 33.3 / 33.3 / 33.2 clocks in the harness)
 #define XMH_R2_FUSED_PLAIN(LAB)                                                                                                                   \
     asm volatile(XMH_R2_OPEN LAB("%0", "%6", "%7", "%8")                                                                                          \
                  XMH_VMIN "%2, 0x10001, %16\n\t" XMH_VMIN "%3, 0x10001, %17\n\t" XMH_VMIN "%4, 0x10001, %18\n\t" XMH_VMIN "%5, 0x10001, %19\n\t" \
                  XMH_MFMA("%1", "%9", "%10", "%11")                                                                                               \
-                 XMH_ADD("%12", "%2") XMH_ADD("%13", "%3") XMH_ADD("%14", "%4") XMH_ADD("%15", "%5")                                              \
+                 XMH_ADD("%12", "%2", "%20") XMH_ADD("%13", "%3", "%20") XMH_ADD("%14", "%4", "%20") XMH_ADD("%15", "%5", "%20")                  \
                  : "=&v"(lab), "=&v"(addr), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)                                                             \
-                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]),                                                    \
-                   "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3])      \
+                 : "v"(At[1]), "v"(bql), "v"(lab0), "v"(At[0]), "v"(bqa), "v"(cqh),                                                                \
+                   "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3]),     \
+                   "n"(r2_imm(HP))                                                                                                                 \
                  : "memory")
-#define XMH_R2_EVAL_CACHE(LAB)                                                                                                                    \
-    asm volatile(XMH_R2_OPEN LAB("%0", "%3", "%4", "%5") XMH_MFMA("%1", "%6", "%7", "%8") XMH_MFMA("%2", "%6", "%9", "%10") XMH_R2_EVAL_CLOSE     \
-                 : "=&v"(lab), "=&v"(addr), "=&v"(d2)                                                                                             \
-                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]), "v"(bq[h][1]), "v"(kqv[REGS ? h : 0]))
-#define XMH_R2_EVAL_PLAIN(LAB)                                                                                                                    \
+#define XMH_R2_EVAL(LAB)                                                                                                                          \
     asm volatile(XMH_R2_OPEN LAB("%0", "%2", "%3", "%4") XMH_MFMA("%1", "%5", "%6", "%7") XMH_R2_EVAL_CLOSE                                       \
                  : "=&v"(lab), "=&v"(addr)                                                                                                        \
-                 : "v"(At[1]), "v"(bq[h][2]), "v"(lab0), "v"(At[0]), "v"(bq[h][0]), "v"(cq[h]))
-        auto fused = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab, uint32_t& w) {
+                 : "v"(At[1]), "v"(bql), "v"(lab0), "v"(At[0]), "v"(bqa), "v"(cqh))
+        // H, the query group, is a constant of the statement: its predecessor's (HP) is the immediate of the adds.  Everything a statement
+        // names is a parameter (bqa, bql, cqh: the address and label operands and the chain start of group H): clang does not capture
+        // what only the asm operands of a generic lambda name
+        auto fused = [](auto hc, const v4i (&At)[NMI], const v4i& bqa, const v4i& bql, const v4i& cqh, const v4i& lab0, const v4i& addr_p, const v4i& lab_p,
+                        v4i& addr, v4i& lab, uint32_t& w) {
+            constexpr int HP = (decltype(hc)::value + NQ - 1) % NQ;
             uint32_t i0, i1, i2, i3;                                  // min results: fresh registers (in-place on the MFMA's result tuple made hipcc copy them)
             if constexpr (F4 && CACHE) XMH_R2_FUSED_CACHE(XMH_MFMA_F4);
             else if constexpr (F4) XMH_R2_FUSED_PLAIN(XMH_MFMA_F4);
@@ -369,37 +398,34 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
         };
         // the first statement of a batch: nothing to consume yet.  Closed by 8 wait states: the next statement's consumers (and any
         // copy hipcc places in front of it) read these results, and its own MFMA is only one slot away
-        auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab) {
-            if constexpr (F4 && CACHE) XMH_R2_EVAL_CACHE(XMH_MFMA_F4);
-            else if constexpr (F4) XMH_R2_EVAL_PLAIN(XMH_MFMA_F4);
-            else if constexpr (CACHE) XMH_R2_EVAL_CACHE(XMH_MFMA);
-            else XMH_R2_EVAL_PLAIN(XMH_MFMA);
+        auto evaluate = [](const v4i (&At)[NMI], const v4i& bqa, const v4i& bql, const v4i& cqh, const v4i& lab0, v4i& addr, v4i& lab) {
+            if constexpr (F4) XMH_R2_EVAL(XMH_MFMA_F4);
+            else XMH_R2_EVAL(XMH_MFMA);
         };
         auto consume = [&](uint32_t& w, const v4i (&live)[NMI]) {        // the last pair of a batch (live: hazard (iv) of the list above this function)
             uint32_t i0, i1, i2, i3;
             if (CACHE) {
                 asm volatile(
                     XMH_VMIN "%1, 0x10001, %5\n\t" XMH_VMIN "%2, 0x10001, %6\n\t" XMH_VMIN "%3, 0x10001, %7\n\t" XMH_VMIN "%4, 0x10001, %8\n\t"
-                    "v_or_b32_sdwa %0, %9, %1 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-                    XMH_ADD("%13", "%1")
-                    "v_or_b32_sdwa %0, %10, %2 " XMH_SDWA(1) XMH_ADD("%14", "%2") "v_or_b32_sdwa %0, %11, %3 " XMH_SDWA(2)
-                    XMH_ADD("%15", "%3") "v_or_b32_sdwa %0, %12, %4 " XMH_SDWA(3) XMH_ADD("%16", "%4")
+                    "v_or_b32_sdwa %0, %9, %1 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
+                    XMH_ADD("%9", "%1", "%16")
+                    "v_or_b32_sdwa %0, %10, %2 " XMH_SDWA(1) XMH_ADD("%10", "%2", "%16") "v_or_b32_sdwa %0, %11, %3 " XMH_SDWA(2)
+                    XMH_ADD("%11", "%3", "%16") "v_or_b32_sdwa %0, %12, %4 " XMH_SDWA(3) XMH_ADD("%12", "%4", "%16")
                     : "=&v"(w), "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
-                    : "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3]), "v"(d2_p[0]), "v"(d2_p[1]), "v"(d2_p[2]), "v"(d2_p[3]), "v"(addr_p[0]),
-                      "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[NMI - 1])
+                    : "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]),
+                      "v"(live[0]), "v"(live[1]), "v"(live[NMI - 1]), "n"(r2_imm(NQ - 1))
                     : "memory");
             } else {
                 asm volatile(
                     XMH_VMIN "%0, 0x10001, %4\n\t" XMH_VMIN "%1, 0x10001, %5\n\t" XMH_VMIN "%2, 0x10001, %6\n\t" XMH_VMIN "%3, 0x10001, %7\n\t"
-                    XMH_ADD("%8", "%0") XMH_ADD("%9", "%1") XMH_ADD("%10", "%2") XMH_ADD("%11", "%3")
+                    XMH_ADD("%8", "%0", "%15") XMH_ADD("%9", "%1", "%15") XMH_ADD("%10", "%2", "%15") XMH_ADD("%11", "%3", "%15")
                     : "=&v"(i0), "=&v"(i1), "=&v"(i2), "=&v"(i3)
                     : "v"(lab_p[0]), "v"(lab_p[1]), "v"(lab_p[2]), "v"(lab_p[3]), "v"(addr_p[0]), "v"(addr_p[1]), "v"(addr_p[2]), "v"(addr_p[3]), "v"(live[0]),
-                      "v"(live[1]), "v"(live[NMI - 1])
+                      "v"(live[1]), "v"(live[NMI - 1]), "n"(r2_imm(NQ - 1))
                     : "memory");
             }
         };
-#undef XMH_R2_EVAL_PLAIN
-#undef XMH_R2_EVAL_CACHE
+#undef XMH_R2_EVAL
 #undef XMH_R2_FUSED_PLAIN
 #undef XMH_R2_FUSED_CACHE
 #undef XMH_SDWA
@@ -409,17 +435,17 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
         auto group = [&](auto gc) {
             constexpr int G = decltype(gc)::value;
             constexpr int SET = REGS ? G : (G & 1);
-#pragma unroll
-            for (int h = 0; h < NQ; ++h) {
-                v4i addr, d2, lab;
-                if (G == 0 && h == 0) evaluate(A[SET], h, addr, d2, lab);
-                else fused(A[SET], h, addr, d2, lab, cw[(h + NQ - 1) % NQ][h == 0 ? G - 1 : G]);
-                addr_p = addr; d2_p = d2; lab_p = lab;
+            r2_each([&](auto hc) {
+                constexpr int h = decltype(hc)::value;
+                v4i addr, lab;
+                if constexpr (G == 0 && h == 0) evaluate(A[SET], bq[h][0], bq[h][1], cq[h], lab0, addr, lab);
+                else fused(hc, A[SET], bq[h][0], bq[h][1], cq[h], lab0, addr_p, lab_p, addr, lab, cw[(h + NQ - 1) % NQ][h == 0 ? G - 1 : G]);
+                addr_p = addr; lab_p = lab;
                 if (REGS && G > 0 && h == 0) {                         // the previous group's tiles may be reused from here on, not earlier
                     if constexpr (NMI == 2) asm volatile("" ::"v"(A[REGS ? G - 1 : 0][0]), "v"(A[REGS ? G - 1 : 0][1]));
                     else asm volatile("" ::"v"(A[REGS ? G - 1 : 0][0]), "v"(A[REGS ? G - 1 : 0][1]), "v"(A[REGS ? G - 1 : 0][NMI - 1]));
                 }
-            }
+            }, std::make_integer_sequence<int, NQ>{});
         };
 #ifdef XMH_ABL_NOBUILD
         if (i == 0) {
@@ -466,7 +492,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
             const int64_t q = (int64_t)(t16 + h) * 16 + ql;
             int dpad = 0;
             for (int w = 0; w < a.W; ++w) dpad += __popc(a.qbits[q * a.W + w]);
-            cnt[h * ncell + dpad * 16 + ql] -= (uint32_t)npad << 16;
+            lds[r2_cell(wave, h, dpad, ql)] -= (uint32_t)npad << 16;
         }
     }
     // (round 8: one bucket row of the wave's 64 consecutive queries per instruction -- 256 contiguous bytes instead of four pieces of 64,
@@ -474,7 +500,7 @@ __device__ __forceinline__ void scan_hist_r2_body(const MfmaArgs& a, uint32_t* _
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
         uint32_t* __restrict__ out = chunk_hist + ((int64_t)chunk_id * a.nb) * a.qpad + (t16 + h) * 16;
-        for (int e = lane; e < ncell; e += 64) out[(int64_t)(e >> 4) * a.qpad + (e & 15)] = cnt[h * ncell + e];
+        for (int e = lane; e < ncell; e += 64) out[(int64_t)(e >> 4) * a.qpad + (e & 15)] = lds[r2_cell(wave, h, e >> 4, e & 15)];
     }
 }
 
@@ -518,58 +544,53 @@ __global__ __launch_bounds__(64 * NW) XMH_R2_ATTR void k_scan_hist_r2(MfmaArgs a
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_scan_hist_r2w (round 4): k_scan_hist_r2 for codes of 65..128 bits -- TWO code tiles per chain (five MFMAs per (16 items x 16 queries):
-// label, address, address, 2 * distance, 2 * distance), 129 bucket rows, 2 query groups per wave (66 KB of counters per block of four
-// waves, two blocks per CU), one-byte pair-cache entries in the layout of the shorter codes.  Same operand construction, same pipeline of
-// statements one (item group, query group) behind their MFMAs, same hazards (the list above scan_hist_r2_body).  Two differences in form: the operands
-// are named (a statement has 28 of the 30 an asm may take), and the cache word is assembled by a second, small statement -- byte j of the
-// word = byte0(2 * distance) | byte0(increment), the even bytes into one register and the odd ones into another so that no two SDWA
-// inserts into one register follow each other (the dst_sel hazard), OR-ed at the end.  A distance of 128 makes 2 * distance = 256, whose
-// byte wraps to 0: the same statement keeps the largest 2 * distance seen, and the kernel raises *ovf (kGateWrapped: pass 2 then evaluates the pairs from the codes).
+// k_scan_hist_r2w (round 4): k_scan_hist_r2 for codes of 65..128 bits -- TWO code tiles per chain (three MFMAs per (16 items x 16 queries):
+// label, address, address; rounds 4-8 had two more for a 2 * distance chain), 2 query groups per wave, one-byte pair-cache entries in the
+// layout of the shorter codes.  Same operand construction and scaling (products of +-512), same pipeline of statements one (item group,
+// query group) behind their MFMAs, same hazards (the list above scan_hist_r2_body), and the same counter layout (r2_cell) with ONE table
+// of 129 bucket rows x 512 bytes for the block's 128 queries -- 66 KB per block, two blocks per CU: the register part of an address is
+// 512 d + 64 wave + 4 query, the `offset:` immediate of the adds 256 h, and the dynamic array has to start at LDS address 0 (no static LDS,
+// held by the self-check of xmh_scan.hip).  Two differences in form: the operands are named, and the cache word is assembled by a second,
+// small statement -- byte j of the word = byte1(address) | byte0(increment), the even bytes into one register and the odd ones into
+// another so that no two SDWA inserts into one register follow each other (the dst_sel hazard), OR-ed at the end.  A distance of 128 makes
+// byte 1 of the address wrap to 0: the same statement keeps the largest address seen, 65536 or more exactly when a distance was 128, and
+// the kernel raises *ovf (kGateWrapped: pass 2 then evaluates the pairs from the codes).
 // ---------------------------------------------------------------------------------------------------
 #define XMH_W_MFMA(D, A, B, C) "v_mfma_i32_16x16x64_i8 %[" D "], %[" A "], %[" B "], %[" C "]\n\t"
 #define XMH_W_MFMA_F4(D, A, B, C) "v_mfma_f32_16x16x128_f8f6f4 %[" D "], %[" A "], %[" B "], %[" C "] cbsz:4 blgp:4\n\t"
 #define XMH_W_MIN(I, L) "v_min_u32 %[" I "], 0x10001, %[" L "]\n\t"
-#define XMH_W_ADD(A, D) "ds_add_u32 %[" A "], %[" D "]\n\t"
-// the statements of k_scan_hist_r2w, once per label instruction (LAB = XMH_W_MFMA: the i8 tile of at most 64 classes; XMH_W_MFMA_F4: the FP4
-// tile of 65-128 classes -- same passes, same wait states, same bits for the v_min)
-#define XMH_W_FUSED_CACHE(LAB) \
-    asm volatile("s_nop 3\n\t" LAB("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")                \
-                 XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap1", "i1")                         \
-                 XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_ADD("ap2", "i2") XMH_W_MFMA("d2", "a0", "bd0", "kq") XMH_W_ADD("ap3", "i3")          \
-                 XMH_W_MFMA("d2", "a1", "bd1", "d2")                                                                                                \
-                 : [lab] "=&v"(lab), [addr] "=&v"(addr), [d2] "=&v"(d2), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)             \
-                 : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bd0] "v"(bD[h][0]),               \
-                   [bd1] "v"(bD[h][1]), [bl0] "v"(bL[h]), [lab0] "v"(lab0), [cq] "v"(cq[h]), [kq] "v"(kq[h]), [lp0] "v"(lab_p[0]),                  \
-                   [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), \
-                   [ap3] "v"(addr_p[3])                                                                                                             \
-                 : "memory")
-#define XMH_W_FUSED_PLAIN(LAB) \
+#define XMH_W_ADD(A, D) "ds_add_u32 %[" A "], %[" D "] offset:%[off]\n\t"
+// the statement of k_scan_hist_r2w, once per label instruction (LAB = XMH_W_MFMA: the i8 tile of at most 64 classes; XMH_W_MFMA_F4: the FP4
+// tile of 65-128 classes -- same passes, same wait states, same bits for the v_min).  With and without a pair cache: the cache word is
+// pack()'s.  off: r2_imm of the PREVIOUS pair's query group, whose adds these are
+#define XMH_W_FUSED(LAB) \
     asm volatile("s_nop 3\n\t" LAB("lab", "al0", "bl0", "lab0") XMH_W_MIN("i0", "lp0") XMH_W_MIN("i1", "lp1") XMH_W_MIN("i2", "lp2")                 \
                  XMH_W_MIN("i3", "lp3") XMH_W_ADD("ap0", "i0") XMH_W_ADD("ap1", "i1") XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_ADD("ap2", "i2")   \
                  XMH_W_ADD("ap3", "i3") XMH_W_MFMA("addr", "a1", "ba1", "addr")                                                                      \
                  : [lab] "=&v"(lab), [addr] "=&v"(addr), [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)                              \
-                 : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bl0] "v"(bL[h]), [lab0] "v"(lab0), \
-                   [cq] "v"(cq[h]), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]),        \
-                   [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3])                                                                  \
+                 : [a0] "v"(At[0]), [a1] "v"(At[1]), [al0] "v"(At[2]), [ba0] "v"(bAh[0]), [ba1] "v"(bAh[1]), [bl0] "v"(bLh), [lab0] "v"(lab0),       \
+                   [cq] "v"(cqh), [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]),        \
+                   [ap1] "v"(addr_p[1]), [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), [off] "n"(r2_imm(HP))                                           \
                  : "memory")
 template <int NML, int NW, int NQ, bool CACHE>
 __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t* __restrict__ chunk_hist, uint4* __restrict__ pair_cache,
                                                            uint32_t* __restrict__ ovf) {
     static_assert(NML == 1 || NML == 2, "one i8 label tile (at most 64 classes) or one FP4 label tile (65-128 classes)");
     constexpr bool F4 = NML == 2;                                    // the label tile is FP4 with K = 128 (label_query_f4 / label_item_f4)
+    static_assert(NW <= 4 && NQ <= 2, "one table of 129 rows: the register part of an address, 64 wave + 4 query, stays below 256, the immediate is 256 h");
     constexpr int NMC = 2, NMI = NMC + 1;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // NW x NQ x [nb][16] u32 counters (all << 16 | relevant)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [nb][128] u32 counters (all << 16 | relevant) at LDS address 0: no static LDS in this kernel
     int chunk_id, qtile;
     if (!map_block(a, chunk_id, qtile)) return;                      // a.nqt counts tiles of NW * NQ * 16 queries here
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ql = lane & 15, slot = lane >> 4;
     const int t16 = (qtile * NW + wave) * NQ;
     const int ncell = a.nb * 16;
-    uint32_t* cnt = lds + (wave * NQ) * ncell;
-    for (int e = lane; e < NQ * ncell; e += 64) cnt[e] = 0u;
+#pragma unroll
+    for (int h = 0; h < NQ; ++h)                                     // a wave clears, counts into and writes out its own columns only: no barrier
+        for (int e = lane; e < ncell; e += 64) lds[r2_cell(wave, h, e >> 4, e & 15)] = 0u;
     const int rsh = 4 * (slot & 1), rwi = slot >> 1;                 // this lane's nibble of the 16 bits it owns; its word inside a 64-bit tile
-    v4i bA[NQ][NMC], bD[NQ][NMC], bL[NQ], cq[NQ], kq[NQ];
+    v4i bA[NQ][NMC], bL[NQ], cq[NQ];
     bool valid[NQ];
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
@@ -586,13 +607,8 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t t = (qw >> j) & 0x01010101u;
-                if (j & 1) {                                         // registers 1 and 3 of an item tile hold their bits worth 2: halved query bytes
-                    bA[h][c][j] = on ? (int)(0x20202020u ^ (t * 0xc0u)) : 0;
-                    bD[h][c][j] = on ? (int)(0x01010101u ^ (t * 0xfeu)) : 0;
-                } else {
-                    bA[h][c][j] = on ? (int)(0x40404040u ^ (t << 7)) : 0;
-                    bD[h][c][j] = on ? (int)(0x02020202u ^ (t * 0xfcu)) : 0;
-                }
+                const uint32_t pos = 0x40u >> j, flip = pos ^ ((0x100u - pos) & 0xffu);      // +-(64 >> j): see scan_hist_r2_body
+                bA[h][c][j] = on ? (int)((0x01010101u * pos) ^ (t * flip)) : 0;
             }
         }
         if constexpr (F4) {
@@ -604,15 +620,13 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
 #pragma unroll
             for (int j = 0; j < 4; ++j) bL[h][j] = (int)((lw >> j) & 0x01010101u);
         }
-        const int c0 = (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(cnt + h * ncell) + ql * 4 + (valid[h] ? 64 * pcq : 0);
-        const int k2 = valid[h] ? 2 * pcq : 0;
+        const int c0 = 64 * wave + ql * 4 + (valid[h] ? kR2RowBytes * pcq : 0);      // table-relative; the statement's immediate is r2_imm(h)
         cq[h] = v4i{c0, c0, c0, c0};
-        kq[h] = v4i{k2, k2, k2, k2};
     }
     v4i lab0 = {0x10000, 0x10000, 0x10000, 0x10000};
     asm volatile("" : "+v"(lab0));                                  // opaque: kept in VGPRs, not re-materialised in front of an MFMA
 #pragma unroll
-    for (int h = 0; h < NQ; ++h) asm volatile("" : "+v"(cq[h]), "+v"(kq[h]));
+    for (int h = 0; h < NQ; ++h) asm volatile("" : "+v"(cq[h]));
     const int64_t lo = (int64_t)chunk_id * a.chunk;
     const int64_t hi = (lo + a.chunk < a.R) ? lo + a.chunk : a.R;
     const int nbat = (int)((hi - lo + 63) >> 6);
@@ -651,14 +665,13 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
             }
         }
     };
-    auto build = [&](v4i (&At)[NMI], const uint32_t (&w)[NMI]) {     // see k_scan_hist_r2: 6 operations per code tile, 5 per label tile
+    const uint32_t rot = rsh ? 1u : 29u;
+    auto build = [&](v4i (&At)[NMI], const uint32_t (&w)[NMI]) {     // see k_scan_hist_r2: 5 operations per code tile, 5 per label tile
 #pragma unroll
         for (int c = 0; c < NMC; ++c) {
-            const uint32_t xa = w[c] >> rsh, xb = w[c] >> (rsh + 2);
-            At[c][0] = (int)(xa & 0x01010101u);
-            At[c][1] = (int)(xa & 0x02020202u);
-            At[c][2] = (int)(xb & 0x01010101u);
-            At[c][3] = (int)(xb & 0x02020202u);
+            const uint32_t x = __builtin_rotateright32(w[c], rot);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) At[c][j] = (int)(x & (0x08080808u << j));
         }
         if constexpr (F4) {
             At[NMC] = label_item_f4(w[NMC]);
@@ -668,51 +681,44 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
             for (int j = 0; j < 4; ++j) At[NMC][j] = (int)(y & (0x01010101u << j));
         }
     };
-    uint32_t dmax = 0u;                                              // largest 2 * distance this lane packed
+    uint32_t dmax = 0u;                                              // largest counter address this lane packed: >= 65536 = a distance of 128
     load_words(bat0, wcur);
     for (int i = 0; i < nbat; ++i) {
         load_words(bat0 + (i + 1 < nbat ? i + 1 : i), wnxt);
         v4i A[4][NMI];
         uint32_t cw[NQ][4];
-        v4i addr_p = {0, 0, 0, 0}, d2_p = {0, 0, 0, 0}, lab_p = {0, 0, 0, 0};
-        // the MFMAs of (group g, query group h) with the increments and adds of the PREVIOUS pair between them
-        auto fused = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab, uint32_t& i0, uint32_t& i1, uint32_t& i2, uint32_t& i3) {
-            if constexpr (F4 && CACHE) XMH_W_FUSED_CACHE(XMH_W_MFMA_F4);
-            else if constexpr (F4) XMH_W_FUSED_PLAIN(XMH_W_MFMA_F4);
-            else if constexpr (CACHE) XMH_W_FUSED_CACHE(XMH_W_MFMA);
-            else XMH_W_FUSED_PLAIN(XMH_W_MFMA);
+        v4i addr_p = {0, 0, 0, 0}, lab_p = {0, 0, 0, 0};
+        // the MFMAs of (group g, query group H) with the increments and adds of the PREVIOUS pair (query group HP) between them
+        // (everything the statement names is a parameter -- bAh, bLh, cqh: the operands and the chain start of group H -- as in scan_hist_r2_body)
+        auto fused = [](auto hc, const v4i (&At)[NMI], const v4i (&bAh)[NMC], const v4i& bLh, const v4i& cqh, const v4i& lab0, const v4i& addr_p, const v4i& lab_p,
+                        v4i& addr, v4i& lab, uint32_t& i0, uint32_t& i1, uint32_t& i2, uint32_t& i3) {
+            constexpr int HP = (decltype(hc)::value + NQ - 1) % NQ;
+            if constexpr (F4) XMH_W_FUSED(XMH_W_MFMA_F4);
+            else XMH_W_FUSED(XMH_W_MFMA);
         };
-        // the cache word of the pair whose increments the statement above just made (d: that pair's 2 * distance results, a statement old)
+        // the cache word of the pair whose increments the statement above just made (d: that pair's addresses, a statement old)
         auto pack = [&](uint32_t& w, const v4i& d, uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3) {
             uint32_t wb;
-            asm volatile("v_or_b32_sdwa %[wa], %[d0], %[i0] dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-                         "v_or_b32_sdwa %[wb], %[d1], %[i1] dst_sel:BYTE_1 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
+            asm volatile("v_or_b32_sdwa %[wa], %[d0], %[i0] dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
+                         "v_or_b32_sdwa %[wb], %[d1], %[i1] dst_sel:BYTE_1 dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
                          "v_max3_u32 %[mx], %[d0], %[d1], %[mx]\n\t"
-                         "v_or_b32_sdwa %[wa], %[d2], %[i2] dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-                         "v_or_b32_sdwa %[wb], %[d3], %[i3] dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
+                         "v_or_b32_sdwa %[wa], %[d2], %[i2] dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
+                         "v_or_b32_sdwa %[wb], %[d3], %[i3] dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
                          "v_max3_u32 %[mx], %[d2], %[d3], %[mx]\n\t"
                          "v_or_b32 %[wa], %[wa], %[wb]"
                          : [wa] "=&v"(w), [wb] "=&v"(wb), [mx] "+v"(dmax)
                          : [d0] "v"(d[0]), [d1] "v"(d[1]), [d2] "v"(d[2]), [d3] "v"(d[3]), [i0] "v"(i0), [i1] "v"(i1), [i2] "v"(i2), [i3] "v"(i3));
         };
         // the first statement of a batch: nothing to consume yet; closed by 8 wait states (the next statement's consumers read these results)
-        auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& d2, v4i& lab) {
+        auto evaluate = [&](const v4i (&At)[NMI], int h, v4i& addr, v4i& lab) {
             if constexpr (F4) {
                 asm volatile("s_nop 3\n\t" XMH_W_MFMA_F4("lab", "al0", "bl0", "lab0") : [lab] "=&v"(lab) : [al0] "v"(At[2]), [bl0] "v"(bL[h]), [lab0] "v"(lab0));
             } else {
                 asm volatile("s_nop 3\n\t" XMH_W_MFMA("lab", "al0", "bl0", "lab0") : [lab] "=&v"(lab) : [al0] "v"(At[2]), [bl0] "v"(bL[h]), [lab0] "v"(lab0));
             }
-            if (CACHE) {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_MFMA("addr", "a1", "ba1", "addr") XMH_W_MFMA("d2", "a0", "bd0", "kq")
-                             XMH_W_MFMA("d2", "a1", "bd1", "d2") "s_nop 7"
-                             : [addr] "=&v"(addr), [d2] "=&v"(d2)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [bd0] "v"(bD[h][0]), [bd1] "v"(bD[h][1]), [cq] "v"(cq[h]),
-                               [kq] "v"(kq[h]));
-            } else {
-                asm volatile("s_nop 3\n\t" XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_MFMA("addr", "a1", "ba1", "addr") "s_nop 7"
-                             : [addr] "=&v"(addr)
-                             : [a0] "v"(At[0]), [a1] "v"(At[1]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [cq] "v"(cq[h]));
-            }
+            asm volatile("s_nop 3\n\t" XMH_W_MFMA("addr", "a0", "ba0", "cq") XMH_W_MFMA("addr", "a1", "ba1", "addr") "s_nop 7"
+                         : [addr] "=&v"(addr)
+                         : [a0] "v"(At[0]), [a1] "v"(At[1]), [ba0] "v"(bA[h][0]), [ba1] "v"(bA[h][1]), [cq] "v"(cq[h]));
         };
         // the last pair of a batch: its increments and adds (live: the tiles of the last statements stay untouched until here)
         auto consume = [&](uint32_t& i0, uint32_t& i1, uint32_t& i2, uint32_t& i3, const v4i (&live)[NMI]) {
@@ -720,26 +726,26 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
                          XMH_W_ADD("ap1", "i1") XMH_W_ADD("ap2", "i2") XMH_W_ADD("ap3", "i3")
                          : [i0] "=&v"(i0), [i1] "=&v"(i1), [i2] "=&v"(i2), [i3] "=&v"(i3)
                          : [lp0] "v"(lab_p[0]), [lp1] "v"(lab_p[1]), [lp2] "v"(lab_p[2]), [lp3] "v"(lab_p[3]), [ap0] "v"(addr_p[0]), [ap1] "v"(addr_p[1]),
-                           [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[2])
+                           [ap2] "v"(addr_p[2]), [ap3] "v"(addr_p[3]), "v"(live[0]), "v"(live[1]), "v"(live[2]), [off] "n"(r2_imm(NQ - 1))
                          : "memory");
         };
         auto group = [&](auto gc) {
             constexpr int G = decltype(gc)::value;
-#pragma unroll
-            for (int h = 0; h < NQ; ++h) {
-                v4i addr, d2 = d2_p, lab;
-                if (G == 0 && h == 0) {
-                    evaluate(A[G], h, addr, d2, lab);
+            r2_each([&](auto hc) {
+                constexpr int h = decltype(hc)::value;
+                v4i addr, lab;
+                if constexpr (G == 0 && h == 0) {
+                    evaluate(A[G], h, addr, lab);
                 } else {
                     uint32_t i0, i1, i2, i3;
-                    fused(A[G], h, addr, d2, lab, i0, i1, i2, i3);
-                    if (CACHE) pack(cw[(h + NQ - 1) % NQ][h == 0 ? G - 1 : G], d2_p, i0, i1, i2, i3);
+                    fused(hc, A[G], bA[h], bL[h], cq[h], lab0, addr_p, lab_p, addr, lab, i0, i1, i2, i3);
+                    if (CACHE) pack(cw[(h + NQ - 1) % NQ][h == 0 ? G - 1 : G], addr_p, i0, i1, i2, i3);
                 }
-                addr_p = addr; d2_p = d2; lab_p = lab;
+                addr_p = addr; lab_p = lab;
                 if (G > 0 && h == 0) {                                 // the previous group's tiles may be reused from here on, not earlier
                     asm volatile("" ::"v"(A[G > 0 ? G - 1 : 0][0]), "v"(A[G > 0 ? G - 1 : 0][1]), "v"(A[G > 0 ? G - 1 : 0][2]));
                 }
-            }
+            }, std::make_integer_sequence<int, NQ>{});
         };
         build(A[0], wcur[0]);
         build(A[1], wcur[1]);
@@ -753,7 +759,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
         {
             uint32_t i0, i1, i2, i3;
             consume(i0, i1, i2, i3, A[3]);
-            if (CACHE) pack(cw[NQ - 1][3], d2_p, i0, i1, i2, i3);
+            if (CACHE) pack(cw[NQ - 1][3], addr_p, i0, i1, i2, i3);
         }
 #ifdef XMH_ABL_NOSTORE
         if (CACHE && a.Q < 0) {
@@ -784,18 +790,17 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
             const int64_t q = (int64_t)(t16 + h) * 16 + ql;
             int dpad = 0;
             for (int w = 0; w < a.W; ++w) dpad += __popc(a.qbits[q * a.W + w]);
-            cnt[h * ncell + dpad * 16 + ql] -= (uint32_t)npad << 16;
+            lds[r2_cell(wave, h, dpad, ql)] -= (uint32_t)npad << 16;
         }
     }
 #pragma unroll
     for (int h = 0; h < NQ; ++h) {
         uint32_t* __restrict__ out = chunk_hist + ((int64_t)chunk_id * a.nb) * a.qpad + (t16 + h) * 16;
-        for (int e = lane; e < ncell; e += 64) out[(int64_t)(e >> 4) * a.qpad + (e & 15)] = cnt[h * ncell + e];
+        for (int e = lane; e < ncell; e += 64) out[(int64_t)(e >> 4) * a.qpad + (e & 15)] = lds[r2_cell(wave, h, e >> 4, e & 15)];
     }
-    if (CACHE && dmax >= 256u) *ovf = 1u;                            // every writer stores the same 1; read by the next launch
+    if (CACHE && dmax >= 65536u) *ovf = 1u;                            // every writer stores the same 1; read by the next launch
 }
-#undef XMH_W_FUSED_PLAIN
-#undef XMH_W_FUSED_CACHE
+#undef XMH_W_FUSED
 #undef XMH_W_MFMA_F4
 #undef XMH_W_MFMA
 #undef XMH_W_MIN
@@ -1172,7 +1177,7 @@ __global__ __launch_bounds__(64 * NW) void k_scan_ap_r2(MfmaArgs a, const uint2*
             c[cell(e)] = pack(pb[at], pd[at]);
         }
     }
-    // query operands: the address chain with k_scan_hist_r2's query bytes (+-64 even registers, +-32 odd ones; the item bytes are doubled, see
+    // query operands: the address chain with the query bytes k_scan_hist_r2 had up to round 8 (+-64 even registers, +-32 odd ones; the item bytes are doubled, see
     // build), started 128 popcount(q) above the lane's counter; the label tile 0 / -1 (FP4: nibbles 0xA = -1.0, the chain starts at +0.0, so the
     // result is +0.0 or a negative float, whose bits are an int below -1: max(bits, -1) is the mask either way)
     v4i bq[NQ], bl[NQ], cq[NQ];

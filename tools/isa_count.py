@@ -25,7 +25,8 @@ SRC = os.path.join(ROOT, "clip-based-cross-modal-hash_amd", "csrc", "xmh_scan.hi
 #   k_scan_hist_s<W, LW, TERN, S, NW, CACHE>;  k_scan_ap_s<W, LW, TERN, CAPPED, S, P32, MASKED, NW, CACHE>;
 #   k_scan_hist_m<NMC, NML, NW, CACHE, BYTE>;  k_scan_hist_m2<NML, NW, NQ, CACHE, STAMP>;  k_scan_ap_c<CAPPED>
 KERNELS = [
-    "k_scan_hist_r2<2, 4, 4, true>", "k_scan_hist_r2<2, 4, 4, false>", "k_scan_hist_r2w<2, 4, 2, true>", "k_scan_ap_c<false, 8, false>", "k_scan_ap_c<false, 8, true>",
+    "k_scan_hist_r2<2, 4, 4, true>", "k_scan_hist_r2<1, 4, 4, true>", "k_scan_hist_r2<2, 4, 4, false>", "k_scan_hist_r2w<2, 4, 2, true>", "k_scan_hist_r2w<1, 4, 2, true>",
+    "k_scan_ap_c<false, 8, false>", "k_scan_ap_c<false, 8, true>",
     "k_scan_ap_r2<2, 4, 2, false>",
     "k_scan_hist_s<2, 3, false, 4, 1, true>", "k_scan_hist_s<2, 3, false, 4, 1, false>", "k_scan_hist_s<1, 3, false, 2, 1, false>",
     "k_scan_ap_s<2, 1, false, false, 4, false, false, 1, true>", "k_scan_ap_s<2, 3, false, true, 4, false, false, 1, false>",
@@ -122,6 +123,7 @@ def main():
                         "-o", os.path.join(tmp, "x.o")], cwd=tmp, check=True, stderr=subprocess.DEVNULL)
         asm = open([os.path.join(tmp, f) for f in os.listdir(tmp) if f.endswith("gfx950.s")][0]).read()
     bodies = kernel_bodies(asm)
+    vgprs = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(?:(?!\.end_amdhsa_kernel).*\n)*?\s+\.amdhsa_next_free_vgpr (\d+)", asm)}
     result, text = {}, []
     for inst in KERNELS:
         key = re.sub(r"\s+", "", inst)
@@ -144,13 +146,15 @@ def main():
         text.append("=== %s  %s\n    loop: %d instructions, %d LDS atomics (= steps of 64 pairs); VALU per step %.2f, DS per step %.2f, SALU per step %.2f\n"
                     % (key, names[0], sum(ops.values()), natom, sum(valu.values()) / natom,
                        sum(v for k, v in ops.items() if k.startswith("ds_")) / natom, sum(v for k, v in ops.items() if k.startswith("s_")) / natom))
-        text.append("    per step: " + ", ".join("%s %.2f" % kv for kv in per_step.items()) + (", MFMA %.3f" % (mfma / natom) if mfma else "") + "\n")
+        text.append("    per step: " + ", ".join("%s %.2f" % kv for kv in per_step.items()) + (", MFMA %.3f" % (mfma / natom) if mfma else "")
+                    + (", VGPRs %d" % vgprs[names[0]] if names[0] in vgprs else "") + "\n")
         text.extend(l + "\n" for l in body if l.strip() and not l.strip().startswith(";"))
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     json.dump(result, open(os.path.join(ROOT, "profiles", "%s_scan_isa.json" % tag), "w"), indent=1, sort_keys=True)
     open(os.path.join(ROOT, "profiles", "%s_scan_isa.txt" % tag), "w").writelines(text)
     for k, v in result.items():
         print("%-64s VALU per 64 pairs: %.2f" % (k, sum(v.values())))
+    sys.stdout.write("".join(l for l in text if l.startswith(("===", "    loop:", "    per step:"))))
 
 
 if __name__ == "__main__":

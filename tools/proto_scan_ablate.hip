@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
     MfmaArgs a{dq, Q, R, K, W, chunk, nchunk, qpad / (PNW * PNQ * 16), nb, qpad};
     a.rbits = dr; a.rlab = drl; a.qlab = dql; a.LW = LW;
     constexpr int NW = PNW, NQ = PNQ;
-    const size_t lds1 = (size_t)NW * NQ * nb * 16 * 4;
+    const size_t lds1 = r2_lds_bytes(NQ, nb);
     auto k1 = k_scan_hist_r2<2, NW, NQ, true>;
     auto k1n = k_scan_hist_r2<2, NW, NQ, false>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
@@ -121,8 +121,8 @@ int main(int argc, char** argv) {
         hipFuncAttributes fa, fan;
         CK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k1)));
         CK(hipFuncGetAttributes(&fan, reinterpret_cast<const void*>(k1n)));
-        printf("pass 1: %d waves x %d query groups, LDS %zu B per block; with cache: %d VGPRs, %d blocks per CU; without: %d VGPRs, %d blocks per CU\n", NW, NQ, lds1,
-               fa.numRegs, occ, fan.numRegs, occn);
+        printf("pass 1: %d waves x %d query groups, LDS %zu B per block (static: %zu, must be 0); with cache: %d VGPRs, %d blocks per CU; without: %d VGPRs, %d blocks per CU\n",
+               NW, NQ, lds1, fa.sharedSizeBytes + fan.sharedSizeBytes, fa.numRegs, occ, fan.numRegs, occn);
     }
     printf("plan: %d chunks of %d items, grid pass 1 %u blocks, pass 2 %u blocks\n", nchunk, chunk, grid1.x, grid2.x);
     timed("pass 1 with pair cache", [&]() { touch(); hipLaunchKernelGGL(k1, grid1, dim3(64 * NW), lds1, 0, a, chunk_hist, cache); });
