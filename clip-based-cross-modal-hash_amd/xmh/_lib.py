@@ -247,6 +247,10 @@ PROTOTYPES = {
     "xmh_twdh_loss_grad": (i32, [C.POINTER(TwdhStreams), vp, vp, vp, i64, C.c_double, C.c_double, vp, vp, vp, vp]),
     "xmh_twdh_short_forward": (i32, [vp, vp, i64, i32, i32, vp, vp]),
     "xmh_twdh_short_backward": (i32, [vp, vp, vp, i64, i32, i32, vp, i32, vp, sz, vp]),
+    "xmh_twdh_trans_ws_bytes": (sz, [i64, i32, i32]),
+    "xmh_twdh_trans_loss": (i32, [vp, vp, i64, i32, i32, C.c_double, vp, sz, vp, vp]),
+    "xmh_twdh_trans_grad": (i32, [vp, vp, i64, i32, i32, C.c_double, vp, vp, i32, vp, sz, vp]),
+    "xmh_twdh_trans_check": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "xmh_hyp_loss_ws_bytes": (sz, [i64, i32, i32]),
     "xmh_hyp_loss": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, sz, vp, vp]),
     "xmh_hyp_loss_grad": (i32, [vp, vp, vp, i64, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, i32, vp, sz, vp]),

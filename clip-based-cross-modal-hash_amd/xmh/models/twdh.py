@@ -211,6 +211,14 @@ class TwDH(BaseModel):
             raise ValueError("TwDH loss: short_center has the code lengths %s and trans_matrix %s; the two config keys must name the same lengths"
                              % (sorted(self.short_center), sorted(self.trans)))
 
+    def transform_fidelity(self):
+        """{key: (n_wrong, wrong [C, short] bool)} of every loaded transform against the loaded centres: the class / bit pairs at
+        which the transform does not turn the long centre into the short one (twdh_transform.transform_fidelity; a lossless
+        transform has n_wrong == 0).  A query: nothing is checked at load time."""
+        from .twdh_transform import transform_fidelity
+        self._require_centres()
+        return {k: transform_fidelity(self.long_center, self.short_center[k], v) for k, v in self.trans.items()}
+
     def compute_loss(self, long_img_hash, long_txt_hash, short_img_hash, short_txt_hash, labels, indexs, ties=None, **kwags):
         """reference :132-184 -- (loss, loss_dict).  `loss` is a 0-dim fp32 device tensor, differentiable with respect to the two
         long codes and every short code; loss_dict has the reference's nested keys, its values detached 0-dim slices of the kernel's

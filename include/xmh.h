@@ -705,6 +705,27 @@ int xmh_twdh_short_forward(const float* long_probs, const float* trans_t, int64_
  * trans [2L, 2S] is T_cat itself.  Workspace: 4 * B * 2S bytes (g_z), 8-byte aligned (XMH_ENOMEM when shorter).  2 launches. */
 int xmh_twdh_short_backward(const float* g_short, const float* p_short, const float* trans, int64_t B, int L2, int S2, float* g_long,
                             int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* The stage that makes a transform (runners/TwDH/transform_matrix_generation).  M [2L, 2S] fp32 is the matrix being
+ * trained; targets [B][ceil((L + S) / 32)] are xmh_twdh_targets' words for the two streams bit = {0, L}, K = {L, S}.  With
+ * x = hash_convert(t_long) (one-hot pairs, never written), z = x . M is the gather z[b][j] = sum_l M[2 l + bit_l(b)][j] and
+ * p = pair_softmax(z).  B <= 4096, L + S <= 4096, C <= 1024 (XMH_ENOTSUP beyond); workspace of xmh_twdh_trans_ws_bytes(B, L, S)
+ * bytes (0: out of range), 8-byte aligned (XMH_ENOMEM when shorter).  Elements are computed in double and rounded once.
+ * out4 (device doubles): total = hash + bce + lasso, hash = 1 - mean_{b,s}((p[b,2s] - p[b,2s+1])^2), bce = nn.BCELoss()(p,
+ * hash_convert(t_short)) (mean over B 2S, each log clamped at -100), lasso = alpha |M|_1.  A NaN in M makes the terms it reaches, and
+ * the total, NaN (the gather reads only the selected row of a pair: the logits of the rows that select the entry).  2 launches. */
+size_t xmh_twdh_trans_ws_bytes(int64_t B, int L, int S);
+int xmh_twdh_trans_loss(const float* M, const uint32_t* targets, int64_t B, int L, int S, double alpha, void* workspace,
+                        size_t workspace_bytes, double* out4, xmh_stream_t stream);
+/* dM [2L, 2S] = upstream[0] (device float, NULL = 1) times (x^T g_z + alpha sign(M)), sign(0) = 0: g = (p - t) / max(p (1 - p), 1e-12)
+ * / (B 2S) -+ 2 (p0 - p1) / (B S), g_z = p (g - (g0 p0 + g1 p1)), dM[2 l + c][j] = the sum of g_z[b][j] over the rows b whose long bit
+ * l is c, b ascending.  Written, or added to dM when accumulate != 0.  2 launches. */
+int xmh_twdh_trans_grad(const float* M, const uint32_t* targets, int64_t B, int L, int S, double alpha, const float* upstream, float* dM,
+                        int accumulate, void* workspace, size_t workspace_bytes, xmh_stream_t stream);
+/* The generator's stopping criterion (train.py:87-96): argmax over each pair of hash_convert(long_centre) . M against short_centre > 0,
+ * equal logits (and a NaN) giving bit 0.  centres [C][L + S] int8 +-1, long then short.  wrong (device int32): wrong[0] the number of
+ * class / bit pairs that disagree, then a [C][ceil(S/32)] bitmap of them (bit s of class c: word c * ceil(S/32) + s / 32, bit s % 32).
+ * Logits are summed in double.  A memset of the count and 1 launch; no host synchronisation. */
+int xmh_twdh_trans_check(const float* M, const int8_t* centres, int C, int L, int S, int32_t* wrong, xmh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * HyP loss of DSPH (models/DSPH/loss/HyP.py:18-70): forward, and its gradient with respect to the two code matrices and the
