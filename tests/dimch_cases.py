@@ -84,6 +84,13 @@ def consts(c):
 
 
 # ---- restatement -------------------------------------------------------------------------------------------------------------------
+def _trace(probe, key, value):
+    """a probe that holds a dict under "trace" receives, per key, the list of every array behind the probe's minima (float64 numpy, in
+    call order; NaN where a triplet is not live): tests/dimch_train_step_cases.py compares them between two dtypes"""
+    if probe.get("trace") is not None:
+        probe["trace"].setdefault(key, []).append(value.double().numpy().copy())
+
+
 def set_similarity(u, v, M, cst, probe=None):
     """u, v [N, K] normalised -> s(u, v) [B, B].  probe: a dict that receives the smallest top-2 gap behind a maximum"""
     N = u.shape[0]
@@ -101,6 +108,7 @@ def set_similarity(u, v, M, cst, probe=None):
             for d in (3, 1):
                 top = torch.topk(G.detach(), 2, dim=d).values
                 probe["gap"] = min(probe.get("gap", np.inf), float((top.select(d, 0) - top.select(d, 1)).min()))
+                _trace(probe, "gap", top.select(d, 0) - top.select(d, 1))
         return (G.max(dim=3).values.sum(1) / M + G.max(dim=1).values.sum(2) / M) / den
     flat = G.permute(0, 2, 1, 3).reshape(B, B, M * M)
     if "max" in mode:
@@ -129,7 +137,10 @@ def triplet_term(D, labels, margin, probe=None):
         live = (mask > 0) & (weight.detach() != 0)
         if live.any():
             probe["hinge"] = min(probe.get("hinge", np.inf), float(t.detach()[live].abs().min()))
+        _trace(probe, "hinge", torch.where(live, t.detach(), torch.full_like(t.detach(), float("nan"))))
     t = (weight * mask * t).clamp(0)
+    if probe is not None:
+        _trace(probe, "live", t.detach().gt(1e-16).sum())
     return t.sum() / (t.gt(1e-16).to(D.dtype).sum() + 1e-16)
 
 
@@ -143,6 +154,7 @@ def objective_terms(e_img, e_txt, h_img, h_txt, labels, cst, probe=None):
     s_xy, s_yx = set_similarity(x, y, M, cst, probe), set_similarity(y, x, M, cst, probe)
     if probe is not None:
         probe["one_minus_s"] = min(float((1 - s_xy.detach()).abs().min()), float((1 - s_yx.detach()).abs().min()))
+        _trace(probe, "one_minus_s", torch.stack([1 - s_xy.detach(), 1 - s_yx.detach()]))
     T_i2t = triplet_term(torch.clamp(1 - s_xy, 0), lab, cst["token_triplet_margin"], probe)
     T_t2i = triplet_term(torch.clamp(1 - s_yx, 0), lab, cst["token_triplet_margin"], probe)
     g = cst["mmd_gamma"]
@@ -284,19 +296,26 @@ HEAD_CASES = {
 }
 
 
+def head_forward(x, P, keep, p, hash_func):
+    """the head on torch tensors of one dtype, with a graph: x [B, T, E], P the six parameters, keep [B M, E / 2] 0 / 1 of that dtype or
+    None -> (embeds [B, M, K], code [B, K], the pre-activations of the two relus [B, M, E] and [B, M, E / 2])"""
+    c_pre = F.conv1d(x, P["conv_w"], P["conv_b"], padding=1)                              # [B, M, E]
+    a_pre = F.linear(F.relu(c_pre), P["w1"], P["b1"])                                     # [B, M, H]
+    a = F.relu(a_pre)
+    if keep is not None:
+        a = a * keep.reshape(a.shape) / (1.0 - p)
+    embeds = F.linear(a, P["w2"], P["b2"])                                                # [B, M, K]
+    pooled = embeds.mean(1)
+    code = torch.tanh(pooled) if hash_func == "tanh" else torch.softmax(pooled.reshape(pooled.shape[0], -1, 2), dim=-1).reshape(pooled.shape)
+    return embeds, code, c_pre, a_pre
+
+
 def head(x, P, keep, p, hash_func, dtype, g_embeds=None, g_hash=None, probe=None):
     """the head of one modality in torch on the CPU: x [B, T, E], P the six parameters (HEAD_PARAMS), keep [B M, E / 2] 0 / 1 or None
     -> {"embeds", "hash"} and, with upstreams, the gradients of sum(embeds g_embeds) + sum(hash g_hash): "g_x" and "g_<parameter>";
     float64 numpy, computed in `dtype`.  probe: receives "relu", the smallest |pre-activation| / max |pre-activation| of both relus"""
     leaves = {k: torch.tensor(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in dict(P, x=x).items()}
-    c_pre = F.conv1d(leaves["x"], leaves["conv_w"], leaves["conv_b"], padding=1)          # [B, M, E]
-    a_pre = F.linear(F.relu(c_pre), leaves["w1"], leaves["b1"])                           # [B, M, H]
-    a = F.relu(a_pre)
-    if keep is not None:
-        a = a * torch.tensor(np.asarray(keep)).to(dtype).reshape(a.shape) / (1.0 - p)
-    embeds = F.linear(a, leaves["w2"], leaves["b2"])                                      # [B, M, K]
-    pooled = embeds.mean(1)
-    code = torch.tanh(pooled) if hash_func == "tanh" else torch.softmax(pooled.reshape(pooled.shape[0], -1, 2), dim=-1).reshape(pooled.shape)
+    embeds, code, c_pre, a_pre = head_forward(leaves["x"], leaves, None if keep is None else torch.tensor(np.asarray(keep)).to(dtype), p, hash_func)
     if probe is not None:
         probe["relu"] = min(float((z.detach().abs() / z.detach().abs().max()).min()) for z in (c_pre, a_pre))
     out = {"embeds": embeds.detach().double().numpy(), "hash": code.detach().double().numpy()}
