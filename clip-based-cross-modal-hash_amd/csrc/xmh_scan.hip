@@ -47,6 +47,7 @@
 
 #include <stdlib.h>
 #include <type_traits>
+#include <unordered_set>
 
 namespace {
 
@@ -411,7 +412,40 @@ struct ScanRoute {
     int rank_bits = 0;              // rank field of the packed pass-2 counters handed to the launches (0: 64-bit counters only)
     Launch p2[3];                   // pass 2 in launch order
     int n2 = 0;
+    bool tables32 = false;          // k_scan_below leaves the packed `below` table (xmh_scan_kernels.h) and k_scan_ap_c reads it: tables_packed
 };
+
+// THE RULE FOR THE PACKED `below` TABLE (one uint32 per cell, all << 16 | relevant, instead of a uint2): k_scan_below writes it and pass 2 reads
+// it exactly when (1) the call is Mode::kUnsharded, (2) the pass 2 behind this xmh_hamming_hist is k_scan_ap_c ALONE -- one launch, no device
+// word that hands the call to another kernel: in practice k_scan_ap_c<., 8, false>, codes of at most 64 bits with a pair cache -- and (3) the
+// host expects every bucket total of the shard to fit 16 bits.  Everything else keeps the 64-bit table: the caller-offsets, totals and
+// all-to-all modes, every route that launches k_scan_ap_s or k_scan_ap_r2, the routes where a device word picks one of two launches.
+// (3) is an estimate, the device decides (kGateWide): the fullest bucket of uniformly random K-bit codes holds R * C(K, K / 2) / 2^K items of
+// a query -- a tenth of the shard at 64 bits, a fifth at 16 -- and the table is packed while TWICE that fits, so that codes whose distances
+// are twice as concentrated as random ones still take the fast path; R / nbuckets > 65 535, where no shard can fit, is implied.  Headline
+// (117 218 x 64 bit): 11 645 -> packed.  16-bit codes on a shard of a million rows: 196 381 -> 64-bit table, not a fallback on every call.
+// The factor of two is a margin chosen by reasoning, not a measured one: no gallery of real codes was profiled for it.
+// WHO SAYS WHICH PASS 2 FOLLOWS.  xmh_hamming_hist cannot see it, so the caller says it: xmh_hamming_hist_for(..., pass2_sharded), and plain
+// xmh_hamming_hist takes a call that exports its histograms (what a sharded evaluation gathers) for a sharded one.  A sharded pass 1 leaves
+// the 64-bit table, so the sharded step has the launches and the table it had.  A caller that says one thing and does the other is still
+// served: the host remembers per workspace which form the last pass 1 left (g_packed_ws below; calls on one workspace are in stream order,
+// one stream at a time), and a pass 2 that finds the other form than its route reads either takes the 64-bit table as it is (k_scan_ap_c
+// reads both) or, for the kernels that read only the 64-bit one, writes it again first (hamming_ap_impl: one launch more, on that mismatch
+// only -- a pass 2 under another XMH_SCAN_* setting than its pass 1, a sharded pass 2 behind a pass 1 that was not told).
+std::mutex g_packed_mu;
+std::unordered_set<const void*> g_packed_ws;              // workspaces whose `below` table is in the packed form
+bool ws_packed(const void* ws) { std::lock_guard<std::mutex> lock(g_packed_mu); return g_packed_ws.count(ws) != 0; }
+void ws_set_packed(const void* ws, bool on) {
+    std::lock_guard<std::mutex> lock(g_packed_mu);
+    if (on) g_packed_ws.insert(ws); else g_packed_ws.erase(ws);
+}
+bool counts_fit16(int K, int64_t R) {
+    double peak = 1.0;                                    // C(K, K / 2) / 2^K
+    for (int i = 1; i <= K / 2; ++i) peak *= (double)(K - K / 2 + i) / (double)i;
+    peak = ldexp(peak, -K);
+    return 2.0 * peak * (double)R <= 65535.0;
+}
+bool tables_packed(bool apc_alone, Mode mode, int K, int64_t R) { return apc_alone && mode == Mode::kUnsharded && counts_fit16(K, R); }
 
 ScanRoute scan_route(const xmh_scan_plan& p, const ScanCall& c, Mode mode, const Overrides& ov, hipStream_t st) {
     ScanRoute r;
@@ -472,7 +506,10 @@ ScanRoute scan_route(const xmh_scan_plan& p, const ScanCall& c, Mode mode, const
         Launch& l = add(Kern::kApC, kByWidth);
         l.eb = 16; l.S = 8;
     }
-    if ((apc || apr2) && !size_gate && !byte128) return r;                  // k_scan_ap_c / k_scan_ap_r2 alone takes the call
+    if ((apc || apr2) && !size_gate && !byte128) {                          // k_scan_ap_c / k_scan_ap_r2 alone takes the call
+        r.tables32 = tables_packed(apc, mode, K, R);
+        return r;
+    }
     Launch s;                                                               // k_scan_ap_s: both counter widths where packed ones apply
     s.kern = Kern::kApS; s.W = tb ? 8 : W; s.LW = LW; s.tern = tern && !tb; s.masked = masked;
     s.cache = cache && !byte128 && !masked && pair_cache_shape(s.W, s.tern);
@@ -595,6 +632,7 @@ struct ScanCtx {
     bool capped = false;
     template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<char*>(c.ws) + off); }
     uint32_t* chunk_hist() const { return at<uint32_t>(L.chunk_hist); }
+    uint32_t rel_scale() const { return r.p1.kern != Kern::kHistS ? kRelHi16 : 0u; }      // the format of pass 1's counter words (chunk_counts)
     const uint2* below() const { return at<uint2>(L.below); }
     uint2* tot() const { return at<uint2>(L.tot); }
     uint2* dpre() const { return at<uint2>(L.dpre); }
@@ -670,20 +708,22 @@ int mfma_hist(const ScanCtx& x) {
                       : (h.cache ? go(k_scan_hist_r2<2, 4, 4, true>, 4, 4, true) : go(k_scan_hist_r2<2, 4, 4, false>, 4, 4, false));
 }
 
-int hamming_hist_impl(const ScanCall& c, uint32_t* hist_all, uint32_t* hist_rel, xmh_stream_t stream, const Overrides& ov) {
+int hamming_hist_impl(const ScanCall& c, uint32_t* hist_all, uint32_t* hist_rel, xmh_stream_t stream, const Overrides& ov, bool pass2_sharded = false) {
     ScanCtx x{c, xmh::as_stream(stream)};
     if (const int rc = plan_call("xmh_hamming_hist", x, ov)) return rc;
     route_call(x, Mode::kUnsharded, ov);
     const xmh_scan_plan& p = x.p;
     const Kern kern = x.r.p1.kern;
+    const bool packed = x.r.tables32 && !pass2_sharded;              // the rule above scan_route
     // k_scan_below's tile tickets, the nrel_max gate word, the finalize ticket (k_scan_hist_r2 / r2w: k_scan_touch in front of them clears them)
     if (kern == Kern::kHistS || kern == Kern::kHistB) XMH_HIP(hipMemsetAsync(x.at<char>(x.L.tick), 0, x.L.gate + 256 - x.L.tick, x.st));
     if (const int rc = kern == Kern::kHistS ? valu_hist(x) : mfma_hist(x)) return rc;
     XMH_LAUNCH_CHECK("xmh_hamming_hist");
     hipLaunchKernelGGL(k_scan_below, dim3((unsigned)p.nqtile, (unsigned)xmh::ceil_div(p.nbuckets, 4)), dim3(256), 0, x.st, x.chunk_hist(), (int)p.qpad,
-                       (int)p.nbuckets, (int)p.nchunk, kern != Kern::kHistS ? kRelHi16 : 0u, x.at<uint2>(x.L.below), x.tot(), x.at<uint32_t>(x.L.tick), (int)c.Q, x.dpre(),
-                       x.cap_ws(), x.gate(), hist_all, hist_rel);
+                       (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), x.at<uint32_t>(x.L.tick), (int)c.Q, x.dpre(),
+                       x.cap_ws(), x.gate(), hist_all, hist_rel, packed, x.gate(kGateWide));
     XMH_LAUNCH_CHECK("xmh_hamming_hist below");
+    ws_set_packed(c.ws, packed);
     return XMH_OK;
 }
 
@@ -740,13 +780,44 @@ extern "C" int xmh_scan_describe(int64_t Q, int64_t R, int K, int C, int ternary
     return XMH_OK;
 }
 
+// FOR TESTS ONLY -- the layout is no promise.  Where the control words of a call lie in its workspace (u32 words: kGateWide is word 4): what a test reads to see which form of the
+// `below` table the device settled on.
+extern "C" size_t xmh_scan_gate_offset(int64_t Q, int64_t R, int K, int ternary) {
+    xmh_scan_plan p;
+    if (make_plan(Q, R, K, ternary, &p)) return (size_t)-1;
+    return ws_layout(p, 0).gate;                                        // (the cache is the last region: its size moves nothing)
+}
+
+// Does an evaluation of this shape run on the packed `below` table (tables_packed)?  1 / 0, or a negative error code.  mode: 0 unsharded
+// (xmh_hamming_map, xmh_hamming_ap without offsets), 1 caller's offsets (xmh_hamming_ap), 2 gathered totals (xmh_hamming_map_sharded), 3
+// all-to-all slices (xmh_hamming_map_sharded_offsets); R is the shard's row count.  The launches' own route, like xmh_scan_describe.
+extern "C" int xmh_scan_tables_packed(int64_t Q, int64_t R, int K, int C, int ternary, int mode) {
+    if (mode < 0 || mode > 3) return xmh::fail(XMH_EINVAL, "xmh_scan_tables_packed: mode=%d", mode);
+    xmh_scan_plan p;
+    if (const int rc = make_plan(Q, R, K, ternary, &p)) return rc;
+    Overrides ov;
+    ov.describe = true;
+    const ScanCall c{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, Q, R, K, C, nullptr, (size_t)p.ws_bytes, ternary != 0};
+    static const Mode modes[4] = {Mode::kUnsharded, Mode::kBaseAll, Mode::kTotals, Mode::kAllToAll};
+    return scan_route(p, c, modes[mode], ov, nullptr).tables32 ? 1 : 0;
+}
+
 extern "C" int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
                                 const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R,
                                 int K, int C, void* ws, size_t ws_bytes, uint32_t* hist_all, uint32_t* hist_rel,
                                 xmh_stream_t stream) {
     XMH_RANGE("xmh_hamming_hist (pass 1)");
     const ScanCall c{qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, qzero != nullptr};
-    return hamming_hist_impl(c, hist_all, hist_rel, stream, {});
+    return hamming_hist_impl(c, hist_all, hist_rel, stream, {}, hist_all != nullptr || hist_rel != nullptr);
+}
+
+extern "C" int xmh_hamming_hist_for(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
+                                    const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab, int64_t Q, int64_t R,
+                                    int K, int C, void* ws, size_t ws_bytes, uint32_t* hist_all, uint32_t* hist_rel, int pass2_sharded,
+                                    xmh_stream_t stream) {
+    XMH_RANGE("xmh_hamming_hist (pass 1)");
+    const ScanCall c{qbits, qzero, qlab, rbits, rzero, rlab, Q, R, K, C, ws, ws_bytes, qzero != nullptr};
+    return hamming_hist_impl(c, hist_all, hist_rel, stream, {}, pass2_sharded != 0);
 }
 
 namespace {
@@ -775,10 +846,12 @@ int ap_offsets(const ScanCtx& x, const Pass2& o) {
 int ap_launch_c(const ScanCtx& x, const Launch& l) {
     const Geom g = launch_geom(l, x.p, x.c.Q);
     const ScanArgs as = x.args(g, true);
+    const uint32_t* wide = x.r.tables32 ? x.gate(kGateWide) : nullptr;      // the packed `below` table and its gate word (tables_packed)
     xmh::ProfScope prof("scan_ap", x.st);
     auto go = [&](auto kc, int S) {                                  // S: the slots of the instance (64 / S queries per wave)
         return start("xmh_hamming_ap", l, g, x.st, kc, S, 1, l.cache, as, x.below(), (const uint2*)x.dpre(), (const uint32_t*)x.cap_ws(), x.ap_part(),
-                     x.gate_if(l, kBySize, 2), x.kcap, x.gate_if(l, kByWrap, kGateWrapped), x.gate_if(l, kByWidth, 0), l.gate & kByWidth ? x.r.rank_bits : 0);
+                     x.gate_if(l, kBySize, 2), x.kcap, x.gate_if(l, kByWrap, kGateWrapped), x.gate_if(l, kByWidth, 0), l.gate & kByWidth ? x.r.rank_bits : 0, wide,
+                     (const uint32_t*)x.chunk_hist(), x.rel_scale());
     };
     if (l.eb == 16) return x.capped ? go(k_scan_ap_c<true, 16>, 8) : go(k_scan_ap_c<false, 16>, 8);
     if (l.half) return x.capped ? go(k_scan_ap_c<true, 8, true>, 8) : go(k_scan_ap_c<false, 8, true>, 8);
@@ -911,8 +984,21 @@ int hamming_ap_impl(const ScanCall& c, const Pass2& o, xmh_stream_t stream, cons
     const int ext = (o.base_all != nullptr) + (o.base_rel != nullptr) + (o.nrel_total != nullptr);
     if (ext != 0 && ext != 3) return xmh::fail(XMH_EINVAL, "xmh_hamming_ap: base_all, base_rel and nrel_total go together");
     route_call(x, o.mode, ov);
+    // the form of `below` the last pass 1 left in this workspace against the form this route reads (the rule above scan_route)
+    const bool have_packed = ws_packed(c.ws);
+    if (x.r.tables32 && !have_packed) x.r.tables32 = false;          // k_scan_ap_c reads the 64-bit table as it is
     x.kcap = o.k > 0 && o.k < (int64_t)0xffffffffll ? (uint32_t)o.k : 0xffffffffu;
     x.capped = o.k > 0;
+    if (!x.r.tables32 && have_packed) {
+        // pass 1 was taken for an unsharded k_scan_ap_c call and left the packed table, which no kernel of this route reads: the 64-bit table
+        // again, from pass 1's counters (no tickets: `below` and the totals only, the same values)
+        const xmh_scan_plan& p = x.p;
+        hipLaunchKernelGGL(k_scan_below, dim3((unsigned)p.nqtile, (unsigned)xmh::ceil_div(p.nbuckets, 4)), dim3(256), 0, x.st, x.chunk_hist(), (int)p.qpad,
+                           (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), (uint32_t*)nullptr, (int)x.c.Q, (uint2*)nullptr,
+                           (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, false, (uint32_t*)nullptr);
+        XMH_LAUNCH_CHECK("xmh_hamming_ap below");
+        ws_set_packed(c.ws, false);
+    }
     if (const int rc = ap_offsets(x, o)) return rc;
     for (int i = 0; i < x.r.n2; ++i) {
         const Launch& l = x.r.p2[i];

@@ -59,27 +59,62 @@ __device__ __forceinline__ void rec_eval01(const QueryRegs<W, LW, TERN>& qr, con
 // bucket tables between the passes (tiny, latency-bound -> spread over many waves, loads independent)
 //   below[c][d][q] = (#all, #relevant) items of bucket d in chunks < c of this shard
 //   tot[d][q]      = (#all, #relevant) items of bucket d in this shard
+// `below` has two forms.  The 64-bit one is a uint2 {all, relevant} per cell.  The PACKED one (k_scan_below's `packed`; the host's rule is
+// tables_packed in xmh_scan.hip) is one uint32 per cell, all << 16 | relevant -- the word pass 1 counts a chunk in, kept through the prefix --
+// at the same index of the same region, of which it fills the first half: half the bytes k_scan_below writes, half of what every block of
+// k_scan_ap_c reads before its first pair.  A prefix is bounded by the shard total of its (bucket, query).  A thread whose total does not
+// fit 16 bits raises the gate word kGateWide; its cells may then hold anything, and every block of k_scan_ap_c sums its start values from
+// chunk_hist itself, which nothing overwrites between the passes: correct, slower, no launch more.  Only k_scan_ap_c reads this form.
 // ---------------------------------------------------------------------------------------------------
-// rel_scale = 0: pass-1 counters are (all | relevant << 16) (k_scan_hist_s); kRelHi16: (all << 16 | relevant) (k_scan_hist_r2 / r2w / b).  Any
-// other value reads them as all + relevant * rel_scale, the form of a kernel that round 5 removed: no caller passes one today.
-constexpr uint32_t kRelHi16 = 0xffffffffu;
+// rel_scale: the format of the pass-1 counter words (chunk_counts, xmh_scan_mfma.h)
 // words of the gate block of the workspace (cleared at the start of every xmh_hamming_hist): 0 = nrel_max, 1 = finalize ticket,
-// 2 = gallery items over all shards, 3 = "a distance wrapped in the one-byte pair cache of 65..128-bit codes"
+// 2 = gallery items over all shards, 3 = "a distance wrapped in the one-byte pair cache of 65..128-bit codes", 4 = "a bucket total does
+// not fit the 16 bits of the packed `below` table"
 constexpr int kGateWrapped = 3;
+constexpr int kGateWide = 4;
 // The block that finishes a 64-query tile LAST (ticket per tile, zeroed ahead of the launch) also writes what the unsharded pass 2
 // needs from the totals -- dpre[d][q] = exclusive prefix of tot over d, nrel[q], the nrel_max gate word -- which used to be a
 // launch of its own between the passes (k_scan_dpre: 9 us + a launch gap; kept for the sharded call and the histogram export).
 __global__ __launch_bounds__(256) void k_scan_below(const uint32_t* __restrict__ chunk_hist, int qpad, int nb, int nchunk, uint32_t rel_scale,
                                                     uint2* __restrict__ below, uint2* __restrict__ tot, uint32_t* __restrict__ tickets, int Q,
                                                     uint2* __restrict__ dpre, uint32_t* __restrict__ nrel_ws, uint32_t* __restrict__ nrel_max,
-                                                    uint32_t* __restrict__ hist_all, uint32_t* __restrict__ hist_rel) {
+                                                    uint32_t* __restrict__ hist_all, uint32_t* __restrict__ hist_rel, bool packed,
+                                                    uint32_t* __restrict__ wide) {
     __shared__ uint2 part[4][64];
     __shared__ int last;
     const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
     const int d = blockIdx.y * 4 + wq;
     const int q = blockIdx.x * 64 + lane;
     const bool hi16 = rel_scale == kRelHi16;
-    if (d < nb) {
+    if (d < nb && packed) {
+        // the packed table (see the header): a thread loads the words of 16 chunks before the first store of the group -- two round trips at
+        // the headline's 24 chunks, where the 64-bit form below makes six dependent ones -- and a cell is one 4-byte store.  (Groups of 32, all of
+        // a thread's chunks in one trip, took 173 VGPRs for the 64 addresses: two waves per SIMD, and the kernel was 2 us slower than the 64-bit
+        // form.)  Source and destination walk by one chunk's stride, so that an address is dead once its instruction has issued.
+        const int64_t cell = (int64_t)d * qpad + q, step = (int64_t)nb * qpad;
+        const uint32_t* __restrict__ src = chunk_hist + cell;
+        uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(below) + cell;
+        uint32_t ra = 0, rr = 0;
+        for (int c0 = 0; c0 < nchunk; c0 += 16) {
+            uint32_t h[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j, src += step) h[j] = c0 + j < nchunk ? *src : 0u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j, dst += step) {
+                if (c0 + j < nchunk) {
+                    *dst = (ra << 16) | rr;
+                    const uint2 n = chunk_counts(h[j], rel_scale);
+                    ra += n.x;
+                    rr += n.y;
+                }
+            }
+        }
+        // relevant <= all: the total of all items decides for both halves.  (The columns of the padding queries count for nothing: pass 1 may
+        // have counted the padding items of the last batch in them, and no sum of theirs is read.)
+        if (ra > 0xffffu && q < Q) *wide = 1u;
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(tot + (int64_t)d * qpad + q), (unsigned long long)ra | ((unsigned long long)rr << 32),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (d < nb) {
         uint32_t ra = 0, rr = 0;
         int c = 0;
         for (; c + 4 <= nchunk; c += 4) {

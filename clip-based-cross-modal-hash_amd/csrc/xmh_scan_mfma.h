@@ -14,6 +14,15 @@ constexpr int kMaxChunk = 32768;   // u16 halves of the packed pass-1 counters m
 constexpr uint32_t kF23 = 0x4B000000u;                  // bits of 2^23 as a float (k_scan_ap_c)
 constexpr int64_t kFloatBitsMaxItems = (1ll << 23) - 3;   // largest gallery (all shards) whose ranks k_scan_ap_c's float-bit counters hold
 constexpr int kMinChunk = 256;
+// The pass-1 counter word of a (chunk, bucket, query).  rel_scale = 0: (all | relevant << 16) (k_scan_hist_s); kRelHi16: (all << 16 | relevant)
+// (k_scan_hist_r2 / r2w / b).  Any other value reads it as all + relevant * rel_scale, the form of a kernel that round 5 removed: no caller
+// passes one today.
+constexpr uint32_t kRelHi16 = 0xffffffffu;
+__device__ __forceinline__ uint2 chunk_counts(uint32_t h, uint32_t rel_scale) {      // {all, relevant}
+    if (rel_scale == kRelHi16) return make_uint2(h >> 16, h & 0xffffu);
+    if (rel_scale == 0u) return make_uint2(h & 0xffffu, h >> 16);
+    return make_uint2(h % rel_scale, h / rel_scale);
+}
 
 struct ScanArgs {
     const uint32_t* qbits;
@@ -831,11 +840,16 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
 // 4-query tiles of a record row are different blocks and each fetched the row's lines -- configs[4]'s shard 2.56 -> 5.65 ms.  That pass is
 // bound by the stream of its pair cache; fetching the words four batches ahead instead of two is worth 4 % there, below.  A batch-major record order -- the records
 // of one batch of all query tiles contiguous, so that the blocks running side by side stream one region -- changed nothing at any shape.)
+// wide (null: `below` is the 64-bit table): the table is the packed one of k_scan_below (xmh_scan_kernels.h) and this is its gate word, "a
+// bucket total did not fit 16 bits"; chunk_hist / rel_scale are what a block then sums its start values from.  Plain pointer arguments on
+// purpose: the same two pointers as members of a struct argument make the accesses through them "indirect" for hipcc's performance hints,
+// the kernel counts as memory bound, and the loop is scheduled for three waves per SIMD instead of five (142 VGPRs instead of 88).
 template <bool CAPPED, int EB, bool HALF = false>
 __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __restrict__ below, const uint2* __restrict__ dpre,
                                                   const uint32_t* __restrict__ cap_ws, float* __restrict__ ap_part,
                                                   const uint32_t* __restrict__ items_total, uint32_t kcap, const uint32_t* __restrict__ skip_if = nullptr,
-                                                  const uint32_t* __restrict__ nrel_max = nullptr, int rank_bits = 0) {
+                                                  const uint32_t* __restrict__ nrel_max = nullptr, int rank_bits = 0, const uint32_t* __restrict__ wide = nullptr,
+                                                  const uint32_t* __restrict__ chunk_hist = nullptr, uint32_t rel_scale = 0) {
     static_assert(!HALF || EB == 8, "the 8 x 8 geometry on one-byte entries");
     constexpr int QW = HALF ? 8 : 128 / EB, LOG_QW = QW == 16 ? 4 : 3, S = 64 / QW, EPW = HALF ? 2 : 32 / EB;      // queries per tile, slots, entries a lane takes from a cache word
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [nb][QW] 64-bit counters
@@ -858,23 +872,65 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
             return (unsigned long long)(kF23 + x.x + y.x + 1u) | ((unsigned long long)(kF23 + (0x7fffffu - (x.y + y.y + 1u))) << 32);
         };
         int e = lane;
-        for (; e + 7 * 64 < ncell; e += 8 * 64) {
-            uint2 x[8], y[8];
+        if (wide == nullptr) {
+            for (; e + 7 * 64 < ncell; e += 8 * 64) {
+                uint2 x[8], y[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int ee = e + j * 64;
-                const int64_t at = (int64_t)(ee >> LOG_QW) * a.qpad + (ee & (QW - 1));
-                x[j] = pb[at];
-                y[j] = pd[at];
+                for (int j = 0; j < 8; ++j) {
+                    const int ee = e + j * 64;
+                    const int64_t at = (int64_t)(ee >> LOG_QW) * a.qpad + (ee & (QW - 1));
+                    x[j] = pb[at];
+                    y[j] = pd[at];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) cnt[e + j * 64] = pack(x[j], y[j]);
             }
+            for (; e < ncell; e += 64) {
+                const int64_t at = (int64_t)(e >> LOG_QW) * a.qpad + (e & (QW - 1));
+                cnt[e] = pack(pb[at], pd[at]);
+            }
+        } else if (*wide == 0u) {
+            // the packed table (k_scan_below): one word per cell, all << 16 | relevant, at the cell's index of the same region
+            const uint32_t* __restrict__ pw = reinterpret_cast<const uint32_t*>(below) + ((int64_t)chunk_id * a.nb) * a.qpad + q0;
+            auto unpack = [](uint32_t w) { return make_uint2(w >> 16, w & 0xffffu); };
+            for (; e + 7 * 64 < ncell; e += 8 * 64) {
+                uint32_t w[8];
+                uint2 y[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) cnt[e + j * 64] = pack(x[j], y[j]);
-        }
-        for (; e < ncell; e += 64) {
-            const int64_t at = (int64_t)(e >> LOG_QW) * a.qpad + (e & (QW - 1));
-            cnt[e] = pack(pb[at], pd[at]);
+                for (int j = 0; j < 8; ++j) {
+                    const int ee = e + j * 64;
+                    const int64_t at = (int64_t)(ee >> LOG_QW) * a.qpad + (ee & (QW - 1));
+                    w[j] = pw[at];
+                    y[j] = pd[at];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) cnt[e + j * 64] = pack(unpack(w[j]), y[j]);
+            }
+            for (; e < ncell; e += 64) {
+                const int64_t at = (int64_t)(e >> LOG_QW) * a.qpad + (e & (QW - 1));
+                cnt[e] = pack(unpack(pw[at]), pd[at]);
+            }
+        } else {
+            // a bucket total of this shard did not fit the packed table (65 536 items or more of one query at one distance): the same sums
+            // from pass 1's own words, chunk by chunk.  Slow and rare; the values are the 64-bit table's, so the results are too.
+            const uint32_t* __restrict__ ph = chunk_hist + q0;
+            for (; e < ncell; e += 64) {
+                const int64_t at = (int64_t)(e >> LOG_QW) * a.qpad + (e & (QW - 1));
+                uint2 x = make_uint2(0u, 0u);
+#pragma unroll 4
+                for (int c = 0; c < chunk_id; ++c) {
+                    const uint2 n = chunk_counts(ph[((int64_t)c * a.nb) * a.qpad + at], rel_scale);
+                    x.x += n.x;
+                    x.y += n.y;
+                }
+                cnt[e] = pack(x, pd[at]);
+            }
         }
     }
+    // the argument the tail stores through, in SGPRs from here on: behind the three-way prologue hipcc otherwise loads it between the first
+    // returning adds and their counted lgkmcnt wait, which a scalar load in flight makes inexact (tools/isa_hazards.py, rule R5).  This pins
+    // what one hipcc does: whoever removes or moves the line, or changes compilers, re-runs tests/test_isa_hazards.py on the rebuilt library.
+    asm volatile("" : "+s"(ap_part));
     const uint32_t cntbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)lds + ql * 8;
     const float capf = CAPPED ? (float)min(cap_ws[q], kcap) : 0.0f;   // exact: below 2^23
     const int64_t lo = (int64_t)chunk_id * a.chunk;

@@ -170,7 +170,10 @@ PROTOTYPES = {
     "xmh_scan_pair_cache_offset": (sz, [i64, i64, i32, i32]),
     "xmh_scan_ws_bytes_nocache": (sz, [i64, i64, i32, i32]),
     "xmh_scan_describe": (i32, [i64, i64, i32, i32, i32, C.c_char_p, sz]),
+    "xmh_scan_tables_packed": (i32, [i64, i64, i32, i32, i32, i32]),
+    "xmh_scan_gate_offset": (sz, [i64, i64, i32, i32]),
     "xmh_hamming_hist": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, sz, vp, vp, vp]),
+    "xmh_hamming_hist_for": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, sz, vp, vp, i32, vp]),
     "xmh_hamming_ap": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, sz, vp, vp, vp, i64, vp, vp, vp]),
     "xmh_hamming_map": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, sz, i64, vp, vp, vp, vp]),
     "xmh_scan_totals_offset": (sz, [i64, i64, i32, i32, C.POINTER(C.c_size_t)]),

@@ -274,13 +274,17 @@ class RankingScan:
         return (ptr(self.q.bits), ptr(self.qz), ptr(self.qlab), ptr(self.r.bits), ptr(self.rz), ptr(self.rlab),
                 self.q.n, self.r.n, self.q.K, self.C, ptr(self.ws), self.ws.numel())      # the size decides: a buffer without room for the pair cache runs uncached
 
-    def histograms(self, want_totals: bool = True):
-        """pass 1.  Returns (hist_all, hist_rel) int32 [Q, nbuckets] shard totals (or (None, None))."""
+    def histograms(self, want_totals: bool = True, sharded: Optional[bool] = None):
+        """pass 1.  Returns (hist_all, hist_rel) int32 [Q, nbuckets] shard totals (or (None, None)).
+        ``sharded``: the pass 2 that follows takes offsets from outside this shard (ap_sums with offsets, map_sharded,
+        map_sharded_offsets) -- it decides the form of the chunk-offset table pass 1 leaves; a wrong word costs a launch
+        in pass 2, never a result.  None: sharded exactly when the totals are exported."""
         ha = hr = None
         if want_totals:
             pair = torch.empty(2, self.q.n, self.plan.nbuckets, dtype=torch.int32, device=self.ws.device)
             ha, hr = pair[0], pair[1]                  # one buffer: the sharded driver all-gathers both planes at once
-        check(lib.xmh_hamming_hist(*self._common(), ptr(ha), ptr(hr), current_stream()), "xmh_hamming_hist")
+        sharded = want_totals if sharded is None else bool(sharded)
+        check(lib.xmh_hamming_hist_for(*self._common(), ptr(ha), ptr(hr), int(sharded), current_stream()), "xmh_hamming_hist")
         return ha, hr
 
     def ap_sums(self, k: Optional[int] = None, base_all=None, base_rel=None, nrel_total=None):

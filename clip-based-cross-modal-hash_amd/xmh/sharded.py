@@ -70,7 +70,7 @@ class HipShardOps:
         if self.empty:
             p = self._R.scan_plan(self.q.n, 1, self.q.K, self._ternary)
             return torch.zeros(p.nbuckets, p.qpad, 2, dtype=torch.int32, device=self.q.bits.device)
-        self.scan.histograms(False)
+        self.scan.histograms(False, sharded=True)
         return self.scan.totals()
 
     def map_partial(self, k, totals_gathered, rank):

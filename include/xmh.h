@@ -147,6 +147,15 @@ size_t xmh_scan_ws_bytes_nocache(int64_t Q, int64_t R, int K, int ternary);
  * an unsharded mAP@all evaluation of this shape launches, spelled as rocprofv3 prints them -- so that a profile row is matched by
  * its exact name.  out_bytes >= 64. */
 int xmh_scan_describe(int64_t Q, int64_t R, int K, int C, int ternary, char* out, size_t out_bytes);
+/* Diagnostics, the same route: does an evaluation of this shape keep the chunk-offset table between the passes in its packed form (one
+ * 32-bit word per cell)?  Returns 1 / 0, or a negative error code.  R: the rows of the shard.  mode: 0 unsharded
+ * (xmh_hamming_map, xmh_hamming_ap without offsets), 1 xmh_hamming_ap with the caller's offsets, 2 xmh_hamming_map_sharded,
+ * 3 xmh_hamming_map_sharded_offsets. */
+int xmh_scan_tables_packed(int64_t Q, int64_t R, int K, int C, int ternary, int mode);
+/* FOR TESTS ONLY; the layout of the workspace is no part of the interface and may change.  Byte offset of the call's control words (u32)
+ * in the workspace; word 4 is raised by xmh_hamming_hist when a bucket total did not fit
+ * the packed table and pass 2 sums its start values itself.  (size_t)-1 on a bad shape. */
+size_t xmh_scan_gate_offset(int64_t Q, int64_t R, int K, int ternary);
 
 /* pass 1.  hist_all / hist_rel: [Q][nbuckets] u32 totals over this shard (either may be NULL).
  * qzero / rzero NULL => binary codes.
@@ -159,6 +168,14 @@ int xmh_hamming_hist(const uint32_t* qbits, const uint32_t* qzero, const uint32_
                      const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab,
                      int64_t Q, int64_t R, int K, int C, void* ws, size_t ws_bytes,
                      uint32_t* hist_all, uint32_t* hist_rel, xmh_stream_t stream);
+/* The same, told which pass 2 follows: pass2_sharded != 0 = one with offsets from outside the shard (xmh_hamming_ap with offsets,
+ * xmh_hamming_map_sharded, xmh_hamming_map_sharded_offsets), 0 = xmh_hamming_map / xmh_hamming_ap without offsets.  It decides the form of
+ * the chunk-offset table left between the passes; a wrong word costs one launch in pass 2, never a result.  Plain
+ * xmh_hamming_hist takes a call that asks for hist_all or hist_rel for a sharded one. */
+int xmh_hamming_hist_for(const uint32_t* qbits, const uint32_t* qzero, const uint32_t* qlab,
+                         const uint32_t* rbits, const uint32_t* rzero, const uint32_t* rlab,
+                         int64_t Q, int64_t R, int K, int C, void* ws, size_t ws_bytes,
+                         uint32_t* hist_all, uint32_t* hist_rel, int pass2_sharded, xmh_stream_t stream);
 
 /* pass 2 (needs the workspace pass 1 filled for the same inputs).
  *   base_all / base_rel [Q][nbuckets] u32 and nrel_total [Q] u32: rank offsets contributed by items
