@@ -47,7 +47,7 @@
 
 #include <stdlib.h>
 #include <type_traits>
-#include <unordered_set>
+#include <unordered_map>
 
 namespace {
 
@@ -432,12 +432,22 @@ struct ScanRoute {
 // one stream at a time), and a pass 2 that finds the other form than its route reads either takes the 64-bit table as it is (k_scan_ap_c
 // reads both) or, for the kernels that read only the 64-bit one, writes it again first (hamming_ap_impl: one launch more, on that mismatch
 // only -- a pass 2 under another XMH_SCAN_* setting than its pass 1, a sharded pass 2 behind a pass 1 that was not told).
+// ROUND 11, THE PACKED TABLE WITHOUT k_scan_below's TAIL.  Where the packed rule holds and the call exports no histograms, k_scan_below runs
+// without tickets and leaves `below` (packed) and the totals only: no dpre, no nrel row, no nrel_max word.  k_scan_ap_c makes the first two from
+// the totals in its prologue (nrel_out, xmh_scan_mfma.h) and nothing on that route reads the third.  The host remembers that as well, and a
+// pass 2 of any other kind on such a workspace first gets the table kernels in their full form: the ticket words cleared, then k_scan_below
+// with tickets, the 64-bit table and its tail (hamming_ap_impl) -- on that mismatch only, and the same values as if pass 1 had been told.
+enum class Tables { k64, kPacked, kPackedNoTail };        // what the last pass 1 left: 64-bit `below` + tail; packed `below` + tail; packed, no tail
 std::mutex g_packed_mu;
-std::unordered_set<const void*> g_packed_ws;              // workspaces whose `below` table is in the packed form
-bool ws_packed(const void* ws) { std::lock_guard<std::mutex> lock(g_packed_mu); return g_packed_ws.count(ws) != 0; }
-void ws_set_packed(const void* ws, bool on) {
+std::unordered_map<const void*, Tables> g_packed_ws;      // workspaces whose `below` table is in the packed form
+Tables ws_tables(const void* ws) {
     std::lock_guard<std::mutex> lock(g_packed_mu);
-    if (on) g_packed_ws.insert(ws); else g_packed_ws.erase(ws);
+    const auto it = g_packed_ws.find(ws);
+    return it == g_packed_ws.end() ? Tables::k64 : it->second;
+}
+void ws_set_tables(const void* ws, Tables t) {
+    std::lock_guard<std::mutex> lock(g_packed_mu);
+    if (t == Tables::k64) g_packed_ws.erase(ws); else g_packed_ws[ws] = t;
 }
 bool counts_fit16(int K, int64_t R) {
     double peak = 1.0;                                    // C(K, K / 2) / 2^K
@@ -630,6 +640,7 @@ struct ScanCtx {
     ScanArgs a;                                          // on the plan's tiles of 64 queries; args(): with a launch's own nqt and the pair cache
     uint32_t kcap = 0xffffffffu;                         // pass 2: k as the kernels take it (none: no ordinal exceeds it) and whether the call has one
     bool capped = false;
+    bool no_tail = false;                                // pass 2 on a workspace without dpre / nrel (Tables::kPackedNoTail): k_scan_ap_c makes them from the totals
     template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<char*>(c.ws) + off); }
     uint32_t* chunk_hist() const { return at<uint32_t>(L.chunk_hist); }
     uint32_t rel_scale() const { return r.p1.kern != Kern::kHistS ? kRelHi16 : 0u; }      // the format of pass 1's counter words (chunk_counts)
@@ -715,15 +726,16 @@ int hamming_hist_impl(const ScanCall& c, uint32_t* hist_all, uint32_t* hist_rel,
     const xmh_scan_plan& p = x.p;
     const Kern kern = x.r.p1.kern;
     const bool packed = x.r.tables32 && !pass2_sharded;              // the rule above scan_route
+    const bool no_tail = packed && !hist_all && !hist_rel;           // k_scan_ap_c prefixes the totals itself (Tables::kPackedNoTail); the export keeps the tail
     // k_scan_below's tile tickets, the nrel_max gate word, the finalize ticket (k_scan_hist_r2 / r2w: k_scan_touch in front of them clears them)
     if (kern == Kern::kHistS || kern == Kern::kHistB) XMH_HIP(hipMemsetAsync(x.at<char>(x.L.tick), 0, x.L.gate + 256 - x.L.tick, x.st));
     if (const int rc = kern == Kern::kHistS ? valu_hist(x) : mfma_hist(x)) return rc;
     XMH_LAUNCH_CHECK("xmh_hamming_hist");
     hipLaunchKernelGGL(k_scan_below, dim3((unsigned)p.nqtile, (unsigned)xmh::ceil_div(p.nbuckets, 4)), dim3(256), 0, x.st, x.chunk_hist(), (int)p.qpad,
-                       (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), x.at<uint32_t>(x.L.tick), (int)c.Q, x.dpre(),
-                       x.cap_ws(), x.gate(), hist_all, hist_rel, packed, x.gate(kGateWide));
+                       (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), no_tail ? (uint32_t*)nullptr : x.at<uint32_t>(x.L.tick), (int)c.Q,
+                       x.dpre(), x.cap_ws(), x.gate(), hist_all, hist_rel, packed, x.gate(kGateWide));
     XMH_LAUNCH_CHECK("xmh_hamming_hist below");
-    ws_set_packed(c.ws, packed);
+    ws_set_tables(c.ws, no_tail ? Tables::kPackedNoTail : (packed ? Tables::kPacked : Tables::k64));
     return XMH_OK;
 }
 
@@ -849,9 +861,9 @@ int ap_launch_c(const ScanCtx& x, const Launch& l) {
     const uint32_t* wide = x.r.tables32 ? x.gate(kGateWide) : nullptr;      // the packed `below` table and its gate word (tables_packed)
     xmh::ProfScope prof("scan_ap", x.st);
     auto go = [&](auto kc, int S) {                                  // S: the slots of the instance (64 / S queries per wave)
-        return start("xmh_hamming_ap", l, g, x.st, kc, S, 1, l.cache, as, x.below(), (const uint2*)x.dpre(), (const uint32_t*)x.cap_ws(), x.ap_part(),
+        return start("xmh_hamming_ap", l, g, x.st, kc, S, 1, l.cache, as, x.below(), (const uint2*)(x.no_tail ? x.tot() : x.dpre()), (const uint32_t*)x.cap_ws(), x.ap_part(),
                      x.gate_if(l, kBySize, 2), x.kcap, x.gate_if(l, kByWrap, kGateWrapped), x.gate_if(l, kByWidth, 0), l.gate & kByWidth ? x.r.rank_bits : 0, wide,
-                     (const uint32_t*)x.chunk_hist(), x.rel_scale());
+                     (const uint32_t*)x.chunk_hist(), x.rel_scale(), x.no_tail ? x.cap_ws() : (uint32_t*)nullptr);
     };
     if (l.eb == 16) return x.capped ? go(k_scan_ap_c<true, 16>, 8) : go(k_scan_ap_c<false, 16>, 8);
     if (l.half) return x.capped ? go(k_scan_ap_c<true, 8, true>, 8) : go(k_scan_ap_c<false, 8, true>, 8);
@@ -985,19 +997,25 @@ int hamming_ap_impl(const ScanCall& c, const Pass2& o, xmh_stream_t stream, cons
     if (ext != 0 && ext != 3) return xmh::fail(XMH_EINVAL, "xmh_hamming_ap: base_all, base_rel and nrel_total go together");
     route_call(x, o.mode, ov);
     // the form of `below` the last pass 1 left in this workspace against the form this route reads (the rule above scan_route)
-    const bool have_packed = ws_packed(c.ws);
+    const Tables have = ws_tables(c.ws);
+    const bool have_packed = have != Tables::k64;
     if (x.r.tables32 && !have_packed) x.r.tables32 = false;          // k_scan_ap_c reads the 64-bit table as it is
+    x.no_tail = x.r.tables32 && have == Tables::kPackedNoTail;       // ... and prefixes the totals itself where pass 1 left no dpre / nrel
     x.kcap = o.k > 0 && o.k < (int64_t)0xffffffffll ? (uint32_t)o.k : 0xffffffffu;
     x.capped = o.k > 0;
     if (!x.r.tables32 && have_packed) {
         // pass 1 was taken for an unsharded k_scan_ap_c call and left the packed table, which no kernel of this route reads: the 64-bit table
-        // again, from pass 1's counters (no tickets: `below` and the totals only, the same values)
+        // again, from pass 1's counters, the same values.  Behind a pass 1 that ran the tail (dpre, nrel, nrel_max are there): no tickets,
+        // `below` and the totals only.  Behind one that did not: the whole kernel, its ticket words cleared first.
         const xmh_scan_plan& p = x.p;
+        const bool tail = have == Tables::kPackedNoTail;
+        if (tail) XMH_HIP(hipMemsetAsync(x.at<char>(x.L.tick), 0, x.L.gate - x.L.tick, x.st));
         hipLaunchKernelGGL(k_scan_below, dim3((unsigned)p.nqtile, (unsigned)xmh::ceil_div(p.nbuckets, 4)), dim3(256), 0, x.st, x.chunk_hist(), (int)p.qpad,
-                           (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), (uint32_t*)nullptr, (int)x.c.Q, (uint2*)nullptr,
-                           (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, false, (uint32_t*)nullptr);
+                           (int)p.nbuckets, (int)p.nchunk, x.rel_scale(), x.at<uint2>(x.L.below), x.tot(), tail ? x.at<uint32_t>(x.L.tick) : (uint32_t*)nullptr, (int)x.c.Q,
+                           tail ? x.dpre() : (uint2*)nullptr, tail ? x.cap_ws() : (uint32_t*)nullptr, tail ? x.gate() : (uint32_t*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, false, (uint32_t*)nullptr);
         XMH_LAUNCH_CHECK("xmh_hamming_ap below");
-        ws_set_packed(c.ws, false);
+        ws_set_tables(c.ws, Tables::k64);
     }
     if (const int rc = ap_offsets(x, o)) return rc;
     for (int i = 0; i < x.r.n2; ++i) {

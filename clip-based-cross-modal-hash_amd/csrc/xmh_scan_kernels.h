@@ -75,6 +75,10 @@ constexpr int kGateWide = 4;
 // The block that finishes a 64-query tile LAST (ticket per tile, zeroed ahead of the launch) also writes what the unsharded pass 2
 // needs from the totals -- dpre[d][q] = exclusive prefix of tot over d, nrel[q], the nrel_max gate word -- which used to be a
 // launch of its own between the passes (k_scan_dpre: 9 us + a launch gap; kept for the sharded call and the histogram export).
+// tickets == nullptr: none of that -- `below` and the totals only, no ticket, no wait for the stores, and the kernel is a stream of two
+// load groups and their stores.  Round 11: the unsharded step on the packed table runs it so (no histogram export), and every block of
+// k_scan_ap_c prefixes the 65 x 16 totals of its query tile over the buckets itself, in registers (xmh_scan_mfma.h); the host remembers that
+// the workspace then holds no dpre / nrel (xmh_scan.hip, the rule for the packed table) and runs this kernel in full for a pass 2 that needs them.
 __global__ __launch_bounds__(256) void k_scan_below(const uint32_t* __restrict__ chunk_hist, int qpad, int nb, int nchunk, uint32_t rel_scale,
                                                     uint2* __restrict__ below, uint2* __restrict__ tot, uint32_t* __restrict__ tickets, int Q,
                                                     uint2* __restrict__ dpre, uint32_t* __restrict__ nrel_ws, uint32_t* __restrict__ nrel_max,
@@ -112,8 +116,11 @@ __global__ __launch_bounds__(256) void k_scan_below(const uint32_t* __restrict__
         // relevant <= all: the total of all items decides for both halves.  (The columns of the padding queries count for nothing: pass 1 may
         // have counted the padding items of the last batch in them, and no sum of theirs is read.)
         if (ra > 0xffffu && q < Q) *wide = 1u;
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(tot + (int64_t)d * qpad + q), (unsigned long long)ra | ((unsigned long long)rr << 32),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // no tickets: no block of this launch reads the totals (their readers are a kernel boundary away), a plain store will do
+        if (!tickets) tot[(int64_t)d * qpad + q] = make_uint2(ra, rr);
+        else
+            __hip_atomic_store(reinterpret_cast<unsigned long long*>(tot + (int64_t)d * qpad + q), (unsigned long long)ra | ((unsigned long long)rr << 32),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (d < nb) {
         uint32_t ra = 0, rr = 0;
         int c = 0;

@@ -844,12 +844,16 @@ __global__ __launch_bounds__(64 * NW) void k_scan_hist_r2w(MfmaArgs a, uint32_t*
 // bucket total did not fit 16 bits"; chunk_hist / rel_scale are what a block then sums its start values from.  Plain pointer arguments on
 // purpose: the same two pointers as members of a struct argument make the accesses through them "indirect" for hipcc's performance hints,
 // the kernel counts as memory bound, and the loop is scheduled for three waves per SIMD instead of five (142 VGPRs instead of 88).
+// nrel_out (round 11; null: dpre and cap_ws are what k_scan_below's tail or the offsets stage left): the packed table without that tail.
+// `dpre` then points at the TOTALS tot[d][q], the prologue prefixes them over the buckets in registers, the cap comes from the row sum it
+// makes on the way, and the blocks of chunk 0 store that sum here (the workspace's nrel row) for the reduce launch.  `wide` is not null then.
 template <bool CAPPED, int EB, bool HALF = false>
 __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __restrict__ below, const uint2* __restrict__ dpre,
                                                   const uint32_t* __restrict__ cap_ws, float* __restrict__ ap_part,
                                                   const uint32_t* __restrict__ items_total, uint32_t kcap, const uint32_t* __restrict__ skip_if = nullptr,
                                                   const uint32_t* __restrict__ nrel_max = nullptr, int rank_bits = 0, const uint32_t* __restrict__ wide = nullptr,
-                                                  const uint32_t* __restrict__ chunk_hist = nullptr, uint32_t rel_scale = 0) {
+                                                  const uint32_t* __restrict__ chunk_hist = nullptr, uint32_t rel_scale = 0,
+                                                  uint32_t* __restrict__ nrel_out = nullptr) {
     static_assert(!HALF || EB == 8, "the 8 x 8 geometry on one-byte entries");
     constexpr int QW = HALF ? 8 : 128 / EB, LOG_QW = QW == 16 ? 4 : 3, S = 64 / QW, EPW = HALF ? 2 : 32 / EB;      // queries per tile, slots, entries a lane takes from a cache word
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [nb][QW] 64-bit counters
@@ -865,6 +869,7 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
     const int q0 = qtile * QW, q = q0 + ql;
     const int ncell = a.nb * QW;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(lds);
+    uint32_t nrel_q = 0u;                                            // nrel_out: the relevant items of query q, summed in the prologue
     {
         const uint2* __restrict__ pb = below + ((int64_t)chunk_id * a.nb) * a.qpad + q0;
         const uint2* __restrict__ pd = dpre + q0;
@@ -872,7 +877,66 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
             return (unsigned long long)(kF23 + x.x + y.x + 1u) | ((unsigned long long)(kF23 + (0x7fffffu - (x.y + y.y + 1u))) << 32);
         };
         int e = lane;
-        if (wide == nullptr) {
+        if (nrel_out != nullptr) {
+            // Round 11: `dpre` is the TOTALS table tot[d][q] and the prefix over the buckets is made here.  Lane (query ql, part `slot`)
+            // owns a contiguous run of ceil(nb / S) bucket rows: it sums its run, takes the sums of the parts in front of it (and all of them:
+            // the query's relevant count) from their lanes, and walks the run again writing each cell's start value, below + prefix, as the
+            // other branches do.  Integers throughout: every counter starts at the bits it started at when k_scan_below wrote dpre.
+            const int rpp = (a.nb + S - 1) / S;
+            const int d0 = slot * rpp < a.nb ? slot * rpp : a.nb, d1 = d0 + rpp < a.nb ? d0 + rpp : a.nb;
+            const uint2* __restrict__ pt = dpre + q;
+            uint32_t sa = 0u, sr = 0u;
+            for (int d = d0; d < d1; d += 8) {
+                uint2 t[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) t[j] = d + j < d1 ? pt[(int64_t)(d + j) * a.qpad] : make_uint2(0u, 0u);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { sa += t[j].x; sr += t[j].y; }
+            }
+            uint32_t ra = 0u, rr = 0u;
+#pragma unroll
+            for (int j = 0; j < S; ++j) {
+                const uint32_t pa = (uint32_t)__shfl((int)sa, j * QW + ql), pr = (uint32_t)__shfl((int)sr, j * QW + ql);
+                if (j < slot) { ra += pa; rr += pr; }
+                nrel_q += pr;
+            }
+            if (chunk_id == 0 && slot == 0 && q < a.Q) nrel_out[q] = nrel_q;      // k_ap_reduce / k_ap_reduce_map read it, a launch later
+            if (*wide == 0u) {                                        // the packed table holds
+                const uint32_t* __restrict__ pw = reinterpret_cast<const uint32_t*>(below) + ((int64_t)chunk_id * a.nb) * a.qpad + q;
+                for (int d = d0; d < d1; d += 8) {
+                    uint2 t[8];
+                    uint32_t w[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int64_t at = (int64_t)(d + j) * a.qpad;
+                        t[j] = d + j < d1 ? pt[at] : make_uint2(0u, 0u);
+                        w[j] = d + j < d1 ? pw[at] : 0u;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        if (d + j < d1) cnt[(d + j) * QW + ql] = pack(make_uint2(w[j] >> 16, w[j] & 0xffffu), make_uint2(ra, rr));
+                        ra += t[j].x;
+                        rr += t[j].y;
+                    }
+                }
+            } else {                                                  // a bucket total did not fit it: the sums from pass 1's own words (see the last branch)
+                const uint32_t* __restrict__ ph = chunk_hist + q;
+                for (int d = d0; d < d1; ++d) {
+                    const int64_t at = (int64_t)d * a.qpad;
+                    uint2 x = make_uint2(0u, 0u);
+#pragma unroll 4
+                    for (int c = 0; c < chunk_id; ++c) {
+                        const uint2 n = chunk_counts(ph[((int64_t)c * a.nb) * a.qpad + at], rel_scale);
+                        x.x += n.x;
+                        x.y += n.y;
+                    }
+                    cnt[d * QW + ql] = pack(x, make_uint2(ra, rr));
+                    const uint2 t = pt[at];
+                    ra += t.x;
+                    rr += t.y;
+                }
+            }
+        } else if (wide == nullptr) {
             for (; e + 7 * 64 < ncell; e += 8 * 64) {
                 uint2 x[8], y[8];
 #pragma unroll
@@ -927,12 +991,12 @@ __global__ __launch_bounds__(64) void k_scan_ap_c(ScanArgs a, const uint2* __res
             }
         }
     }
-    // the argument the tail stores through, in SGPRs from here on: behind the three-way prologue hipcc otherwise loads it between the first
+    // the argument the tail stores through, in SGPRs from here on: behind the four-way prologue (round 11: the in-block bucket prefix is its first branch) hipcc otherwise loads it between the first
     // returning adds and their counted lgkmcnt wait, which a scalar load in flight makes inexact (tools/isa_hazards.py, rule R5).  This pins
     // what one hipcc does: whoever removes or moves the line, or changes compilers, re-runs tests/test_isa_hazards.py on the rebuilt library.
     asm volatile("" : "+s"(ap_part));
     const uint32_t cntbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)lds + ql * 8;
-    const float capf = CAPPED ? (float)min(cap_ws[q], kcap) : 0.0f;   // exact: below 2^23
+    const float capf = CAPPED ? (float)min(nrel_out ? nrel_q : cap_ws[q], kcap) : 0.0f;   // exact: below 2^23
     const int64_t lo = (int64_t)chunk_id * a.chunk;
     const int64_t hi = (lo + a.chunk < a.R) ? lo + a.chunk : a.R;
     float acc = 0.0f;
