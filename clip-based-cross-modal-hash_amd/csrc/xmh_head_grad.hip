@@ -344,6 +344,122 @@ void launch_tn(hipStream_t st, const float* dy, const float* x, int M, int N, in
                            K, M, o);
 }
 
+// ---- cross-rank BatchNorm: the column statistics of k_bn_train and k_norm_bwd_cols<true> split from their use, so that
+// the ranks of a distributed step can exchange them in between.  A statistics row is kStatsRow(E) doubles: [E] [E] count 0.
+__host__ __device__ constexpr int64_t kStatsRow(int E) { return 2 * (int64_t)E + 2; }
+
+// forward, first half: per column the LOCAL mean and M2 = sum (o - mean)^2, the two passes of k_bn_train, and the local row count
+__global__ __launch_bounds__(kThreads) void k_bn_stats(const float* __restrict__ o, int B, int E, double* __restrict__ row) {
+    __shared__ double sh[kGroups][kCols];
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    const bool live = e < E;
+    double a = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) a += (double)o[(int64_t)b * E + e];
+    const double mean = group_sum(a, sh, col, grp) / (double)B;
+    a = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) {
+            const double d = (double)o[(int64_t)b * E + e] - mean;
+            a += d * d;
+        }
+    const double m2 = group_sum(a, sh, col, grp);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        row[2 * (int64_t)E] = (double)B;
+        row[2 * (int64_t)E + 1] = 0.0;
+    }
+    if (!live || grp != 0) return;
+    row[e] = mean;
+    row[E + e] = m2;
+}
+
+// forward, second half: the rows of all W ranks combined IN RANK ORDER by the pairwise update (n, mean, M2) + (n_r, mean_r, M2_r) -- the
+// same chain of double operations in every thread of every rank, so all of them derive the same bits -- then k_bn_train's use of
+// them on this rank's rows: global mean and BIASED variance, the running statistics towards the global mean and the UNBIASED global
+// variance (n_total - 1).  One rank: the chain is empty and the numbers are k_bn_train's to the bit.
+__global__ __launch_bounds__(kThreads) void k_bn_apply(const float* __restrict__ o, int B, int E, const double* __restrict__ table, int W,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                       float momentum, float* run_mean, float* run_var, Saved s) {
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    if (e >= E) return;
+    const int64_t stride = kStatsRow(E);
+    double n = table[2 * (int64_t)E], mean = table[e], m2 = table[E + e];
+    for (int r = 1; r < W; ++r) {
+        const double* row = table + r * stride;
+        const double nr = row[2 * (int64_t)E];
+        if (!(nr > 0.0)) continue;
+        const double delta = row[e] - mean, nn = n + nr;
+        mean += delta * (nr / nn);
+        m2 += row[E + e] + delta * delta * (n * nr / nn);
+        n = nn;
+    }
+    const float var = (float)(m2 / n), fmean = (float)mean;
+    const float rstd = 1.0f / sqrtf(var + eps);
+    const float g = gamma[e], bt = beta[e];
+    for (int b = grp; b < B; b += kGroups) {
+        const int64_t at = (int64_t)b * E + e;
+        const float nh = (o[at] - fmean) * rstd;
+        s.nhat[at] = nh;
+        s.n[at] = fmaf(nh, g, bt);
+    }
+    if (grp == 0) {
+        s.rstd[e] = rstd;
+        if (run_mean) run_mean[e] = (1.0f - momentum) * run_mean[e] + momentum * fmean;
+        if (run_var) run_var[e] = (1.0f - momentum) * run_var[e] + momentum * (float)(m2 / (n - 1.0));
+    }
+}
+
+// backward, first half: the LOCAL column sums of k_norm_bwd_cols, sum_b dn nhat and sum_b dn, and the local row count
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_stats(const float* __restrict__ dn, const float* __restrict__ nhat, int B, int E,
+                                                           double* __restrict__ row) {
+    __shared__ double sh[kGroups][kCols];
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    const bool live = e < E;
+    double a = 0.0, c = 0.0;
+    if (live)
+        for (int b = grp; b < B; b += kGroups) {
+            const float d = dn[(int64_t)b * E + e];
+            a += (double)d * (double)nhat[(int64_t)b * E + e];
+            c += (double)d;
+        }
+    const double sg = group_sum(a, sh, col, grp), sb = group_sum(c, sh, col, grp);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        row[2 * (int64_t)E] = (double)B;
+        row[2 * (int64_t)E + 1] = 0.0;
+    }
+    if (!live || grp != 0) return;
+    row[e] = sg;
+    row[E + e] = sb;
+}
+
+// backward, second half: dgamma / dbeta from THIS rank's sums (the gradient all-reduce averages them like every other gradient), the
+// sums of all ranks added in rank order, do = gamma rstd (dn - mean(dn) - nhat mean(dn nhat)) with the means over n_total, in place
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(float* dn, const float* __restrict__ nhat, int B, int E,
+                                                           const double* __restrict__ table, int W, int rank,
+                                                           const float* __restrict__ gamma, const float* __restrict__ rstd, float* dgamma,
+                                                           float* dbeta, int accumulate) {
+    const int col = threadIdx.x % kCols, grp = threadIdx.x / kCols, e = blockIdx.x * kCols + col;
+    if (e >= E) return;
+    const int64_t stride = kStatsRow(E);
+    if (grp == 0) {
+        const double* own = table + rank * stride;
+        if (dgamma) dgamma[e] = accumulate ? dgamma[e] + (float)own[e] : (float)own[e];
+        if (dbeta) dbeta[e] = accumulate ? dbeta[e] + (float)own[E + e] : (float)own[E + e];
+    }
+    double sg = table[e], sb = table[E + e], n = table[2 * (int64_t)E];
+    for (int r = 1; r < W; ++r) {
+        const double* row = table + r * stride;
+        sg += row[e];
+        sb += row[E + e];
+        n += row[2 * (int64_t)E];
+    }
+    const float mg = (float)(sg / n), mb = (float)(sb / n), w = gamma[e] * rstd[e];
+    for (int b = grp; b < B; b += kGroups) {
+        const int64_t at = (int64_t)b * E + e;
+        dn[at] = w * (dn[at] - mb - nhat[at] * mg);
+    }
+}
+
 // bias gradient alone (its weight is frozen): column sums of dy [M, N] in double, row order
 __global__ __launch_bounds__(kThreads) void k_col_sum(const float* __restrict__ dy, int M, int N, float* db, int accumulate) {
     __shared__ double sh[kGroups][kCols];
@@ -470,6 +586,133 @@ extern "C" int xmh_head_dcmht_backward(const xmh_dcmht_train* h, const float* x,
         launch_nn(st, w.a, h->wo, M, E, E, w.b);                                  // dv
         weight_grads(st, w.b, x, M, E, E, g->d_wv, g->d_bv, accumulate);
         if (g->d_x) launch_nn(st, w.b, h->wv, M, E, E, g->d_x);               // an activation gradient: written, never added to
+    }
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+// ---- the same head with a cross-rank BatchNorm: each of the two calls above in two halves, the caller's all-gather of the statistics
+// rows in between.  The workspace carries o (forward) / dn and df (backward) from the first half to the second: the caller keeps it.
+namespace {
+
+int check_sync(const char* who, const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, const void* saved, size_t saved_bytes,
+               void* workspace, size_t workspace_bytes, const double* stats) {
+    if (int rc = check_dcmht(who, h, x, B, E, N)) return rc;
+    if (!h->norm_is_batchnorm) return xmh::fail(XMH_EINVAL, "%s: the head's norm is a LayerNorm (rows need no other rank)", who);
+    if (!stats) return xmh::fail(XMH_EINVAL, "%s: null statistics", who);
+    if (reinterpret_cast<uintptr_t>(stats) & 7u) return xmh::fail(XMH_EINVAL, "%s: statistics not 8-byte aligned", who);
+    if (int rc = check_buffer(who, "saved buffer", saved, saved_bytes, saved_layout(B, E, N, nullptr, nullptr))) return rc;
+    return check_buffer(who, "workspace", workspace, workspace_bytes, work_layout(B, E, N, nullptr, nullptr));
+}
+
+int check_world(const char* who, int64_t B, int world, int rank) {
+    if (world < 1 || world > 4096 || rank < 0 || rank >= world) return xmh::fail(XMH_EINVAL, "%s: rank %d of %d", who, rank, world);
+    // every rank has at least one row, so the global batch is a single row only when this rank is alone with one
+    if (world == 1 && B < 2) return xmh::fail(XMH_EINVAL, "%s: BatchNorm in training mode needs more than 1 row over all ranks", who);
+    return XMH_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t xmh_head_dcmht_stats_len(int E) { return E > 0 && E <= kMaxE ? kStatsRow(E) : 0; }
+
+extern "C" int xmh_head_dcmht_train_forward_stats(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, void* saved,
+                                                  size_t saved_bytes, void* workspace, size_t workspace_bytes, double* stats_row,
+                                                  xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_train_forward_stats");
+    const char* who = "xmh_head_dcmht_train_forward_stats";
+    if (int rc = check_sync(who, h, x, B, E, N, saved, saved_bytes, workspace, workspace_bytes, stats_row)) return rc;
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, saved, &s);
+    work_layout(B, E, N, workspace, &w);
+    hipStream_t st = xmh::as_stream(stream);
+    MmOut o = {};
+    o.C = s.v;
+    o.bias = h->bv;
+    launch_nt(st, x, h->wv, (int)B, E, E, o);
+    o.C = w.a;
+    o.bias = h->bo;
+    launch_nt(st, s.v, h->wo, (int)B, E, E, o);
+    hipLaunchKernelGGL(k_bn_stats, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, (int)B, E, stats_row);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dcmht_train_forward_apply(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, const double* table,
+                                                  int world, float* probs, void* saved, size_t saved_bytes, void* workspace,
+                                                  size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_train_forward_apply");
+    const char* who = "xmh_head_dcmht_train_forward_apply";
+    if (int rc = check_sync(who, h, x, B, E, N, saved, saved_bytes, workspace, workspace_bytes, table)) return rc;
+    if (!probs) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (int rc = check_world(who, B, world, 0)) return rc;
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, saved, &s);
+    work_layout(B, E, N, workspace, &w);
+    hipStream_t st = xmh::as_stream(stream);
+    hipLaunchKernelGGL(k_bn_apply, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, (int)B, E, table, world, h->norm_w, h->norm_b,
+                       h->eps, h->momentum, h->running_mean, h->running_var, s);
+    MmOut o = {};
+    o.C = probs;
+    o.bias = h->b2;
+    o.epi = EPI_RELU_PAIR;
+    o.aux = s.p;
+    o.f = s.f;
+    launch_nt(st, s.n, h->w2, (int)B, N, E, o);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dcmht_backward_stats(const xmh_dcmht_train* h, const float* x, const float* d_probs, int64_t B, int E, int N,
+                                             const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate,
+                                             void* workspace, size_t workspace_bytes, double* stats_row, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_backward_stats");
+    const char* who = "xmh_head_dcmht_backward_stats";
+    if (int rc = check_sync(who, h, x, B, E, N, saved, saved_bytes, workspace, workspace_bytes, stats_row)) return rc;
+    if (!d_probs || !g) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, const_cast<void*>(saved), &s);
+    work_layout(B, E, N, workspace, &w);
+    hipStream_t st = xmh::as_stream(stream);
+    const int M = (int)B;
+    const int64_t pairs = B * (N / 2);
+    // dn and its sums are formed whatever is frozen: the other ranks wait for this rank's row
+    hipLaunchKernelGGL(k_pair_relu_bwd, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_probs, s.p, s.f, pairs,
+                       w.c);
+    weight_grads(st, w.c, s.n, M, N, E, g->d_w2, g->d_b2, accumulate);
+    launch_nn(st, w.c, h->w2, M, N, E, w.a);                                      // dn
+    hipLaunchKernelGGL(k_bn_bwd_stats, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, s.nhat, M, E, stats_row);
+    XMH_LAUNCH_CHECK(who);
+    return XMH_OK;
+}
+
+extern "C" int xmh_head_dcmht_backward_apply(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, const double* table, int world,
+                                             int rank, const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate,
+                                             void* workspace, size_t workspace_bytes, xmh_stream_t stream) {
+    XMH_RANGE("xmh_head_dcmht_backward_apply");
+    const char* who = "xmh_head_dcmht_backward_apply";
+    if (int rc = check_sync(who, h, x, B, E, N, saved, saved_bytes, workspace, workspace_bytes, table)) return rc;
+    if (!g) return xmh::fail(XMH_EINVAL, "%s: null pointer", who);
+    if (int rc = check_world(who, B, world, rank)) return rc;
+    Saved s;
+    Work w;
+    saved_layout(B, E, N, const_cast<void*>(saved), &s);
+    work_layout(B, E, N, workspace, &w);
+    hipStream_t st = xmh::as_stream(stream);
+    const int M = (int)B;
+    const bool need_dv = g->d_wv || g->d_bv || g->d_x;
+    const bool need_do = need_dv || g->d_wo || g->d_bo;
+    if (!need_do && !g->d_norm_w && !g->d_norm_b) return XMH_OK;
+    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((E + kCols - 1) / kCols), dim3(kThreads), 0, st, w.a, s.nhat, M, E, table, world, rank, h->norm_w,
+                       s.rstd, g->d_norm_w, g->d_norm_b, accumulate);
+    if (need_do) weight_grads(st, w.a, s.v, M, E, E, g->d_wo, g->d_bo, accumulate);
+    if (need_dv) {
+        launch_nn(st, w.a, h->wo, M, E, E, w.b);                                  // dv
+        weight_grads(st, w.b, x, M, E, E, g->d_wv, g->d_bv, accumulate);
+        if (g->d_x) launch_nn(st, w.b, h->wv, M, E, E, g->d_x);
     }
     XMH_LAUNCH_CHECK(who);
     return XMH_OK;

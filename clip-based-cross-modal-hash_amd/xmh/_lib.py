@@ -263,6 +263,12 @@ PROTOTYPES = {
     "xmh_head_dcmht_train_bytes": (sz, [i64, i32, i32, C.POINTER(C.c_size_t)]),
     "xmh_head_dcmht_train_forward": (i32, [C.POINTER(DcmhtTrain), vp, i64, i32, i32, vp, vp, sz, vp, sz, vp]),
     "xmh_head_dcmht_backward": (i32, [C.POINTER(DcmhtTrain), vp, vp, i64, i32, i32, vp, sz, C.POINTER(DcmhtGrads), i32, vp, sz, vp]),
+    "xmh_head_dcmht_stats_len": (i64, [i32]),
+    "xmh_head_dcmht_train_forward_stats": (i32, [C.POINTER(DcmhtTrain), vp, i64, i32, i32, vp, sz, vp, sz, vp, vp]),
+    "xmh_head_dcmht_train_forward_apply": (i32, [C.POINTER(DcmhtTrain), vp, i64, i32, i32, vp, i32, vp, vp, sz, vp, sz, vp]),
+    "xmh_head_dcmht_backward_stats": (i32, [C.POINTER(DcmhtTrain), vp, vp, i64, i32, i32, vp, sz, C.POINTER(DcmhtGrads), i32, vp, sz, vp, vp]),
+    "xmh_head_dcmht_backward_apply": (i32, [C.POINTER(DcmhtTrain), vp, i64, i32, i32, vp, i32, i32, vp, sz, C.POINTER(DcmhtGrads), i32, vp, sz,
+                                            vp]),
     "xmh_head_dsph_train_forward": (i32, [vp, vp, vp, vp, C.c_float, i64, i32, i32, vp, vp]),
     "xmh_head_dsph_backward": (i32, [vp, vp, vp, vp, C.c_float, vp, i64, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
     "xmh_mith_train_saved_bytes": (sz, [i64, i32, i32, i32, i32, i32]),
@@ -272,6 +278,8 @@ PROTOTYPES = {
     "xmh_bertadam_chunk": (i64, []),
     "xmh_bertadam_ws_bytes": (sz, [i64, i64]),
     "xmh_bertadam_step": (i32, [vp, i64, vp, i64, vp, sz, vp]),
+    "xmh_bucket_pack": (i32, [vp, i64, vp, i64, C.c_float, vp, vp]),
+    "xmh_bucket_unpack": (i32, [vp, i64, vp, i64, vp, vp]),
     "xmh_topk_ws_bytes": (sz, [i64, i64, i32, i32]),
     "xmh_hamming_topk": (i32, [vp, vp, i64, i64, i32, i32, i64, vp, sz, vp, vp, vp]),
     "xmh_topk_ws_init": (i32, [i64, i64, i32, i32, vp, sz, vp]),

@@ -36,6 +36,20 @@ class DCMHTModalityHash(nn.Module):
         self.atten = nn.MultiheadAttention(inputDim, num_heads=num_heads, batch_first=True)
         self.norm = nn.LayerNorm(inputDim) if layernorm else nn.BatchNorm1d(inputDim)
         self.fc2 = nn.Linear(inputDim, outputDim * 2)
+        # distributed training: the process group over whose ranks a BatchNorm head takes its batch statistics, what the
+        # reference gets from convert_sync_batchnorm; None: the local batch, the fused calls
+        self.sync_group = None
+
+    def _synced(self) -> bool:
+        return getattr(self, "sync_group", None) is not None and isinstance(self.norm, nn.BatchNorm1d)
+
+    def _gather_stats(self, row: torch.Tensor):
+        """the statistics rows of all ranks in rank order [W, len] (one small all-gather), and this rank's index"""
+        from torch import distributed as dist
+        world, rank = dist.get_world_size(self.sync_group), dist.get_rank(self.sync_group)
+        table = torch.empty(world, row.numel(), dtype=row.dtype, device=row.device)
+        dist.all_gather(list(table.unbind(0)), row, group=self.sync_group)
+        return table, world, rank
 
     def _desc(self, precision: int, keep: list):
         E = self.atten.in_proj_weight.shape[1]
@@ -90,15 +104,24 @@ class DCMHTModalityHash(nn.Module):
         B, E = x.shape
         N = self.fc2.weight.shape[0]
         bn = isinstance(self.norm, nn.BatchNorm1d)
-        if bn and B == 1:
+        synced = self._synced()
+        if bn and B == 1 and not synced:                     # across ranks one local row is legal: the library refuses a global batch of one
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(data.shape),))
         h, keep = self._train_args()
         nws = ctypes.c_size_t(0)
         nsaved = lib.xmh_head_dcmht_train_bytes(B, E, N, ctypes.byref(nws))
         saved, ws = _clip._workspace(nsaved, x.device), _clip._workspace(nws.value, x.device)
         probs = torch.empty(B, N, dtype=torch.float32, device=x.device)
-        check(lib.xmh_head_dcmht_train_forward(ctypes.byref(h), ptr(x), B, E, N, ptr(probs), ptr(saved), nsaved, ptr(ws), nws.value,
-                                               current_stream()), "xmh_head_dcmht_train_forward")
+        if synced:                                           # statistics -> all-gather of one small double row per rank -> the rest
+            row = torch.empty(lib.xmh_head_dcmht_stats_len(E), dtype=torch.float64, device=x.device)
+            check(lib.xmh_head_dcmht_train_forward_stats(ctypes.byref(h), ptr(x), B, E, N, ptr(saved), nsaved, ptr(ws), nws.value, ptr(row),
+                                                         current_stream()), "xmh_head_dcmht_train_forward_stats")
+            table, world, _ = self._gather_stats(row)
+            check(lib.xmh_head_dcmht_train_forward_apply(ctypes.byref(h), ptr(x), B, E, N, ptr(table), world, ptr(probs), ptr(saved), nsaved,
+                                                         ptr(ws), nws.value, current_stream()), "xmh_head_dcmht_train_forward_apply")
+        else:
+            check(lib.xmh_head_dcmht_train_forward(ctypes.byref(h), ptr(x), B, E, N, ptr(probs), ptr(saved), nsaved, ptr(ws), nws.value,
+                                                   current_stream()), "xmh_head_dcmht_train_forward")
         if bn and self.norm.track_running_stats and self.norm.num_batches_tracked is not None:
             self.norm.num_batches_tracked.add_(1)
         del keep
@@ -170,8 +193,17 @@ class _DCMHTTrain(torch.autograd.Function):
         nws = ctypes.c_size_t(0)
         nsaved = lib.xmh_head_dcmht_train_bytes(B, E, N, ctypes.byref(nws))
         ws = _clip._workspace(nws.value, x.device)
-        check(lib.xmh_head_dcmht_backward(ctypes.byref(h), ptr(x), ptr(up), B, E, N, ptr(saved), nsaved, ctypes.byref(grads), 0, ptr(ws),
-                                          nws.value, current_stream()), "xmh_head_dcmht_backward")
+        if mod._synced():
+            row = torch.empty(lib.xmh_head_dcmht_stats_len(E), dtype=torch.float64, device=x.device)
+            check(lib.xmh_head_dcmht_backward_stats(ctypes.byref(h), ptr(x), ptr(up), B, E, N, ptr(saved), nsaved, ctypes.byref(grads), 0,
+                                                    ptr(ws), nws.value, ptr(row), current_stream()), "xmh_head_dcmht_backward_stats")
+            table, world, rank = mod._gather_stats(row)
+            check(lib.xmh_head_dcmht_backward_apply(ctypes.byref(h), ptr(x), B, E, N, ptr(table), world, rank, ptr(saved), nsaved,
+                                                    ctypes.byref(grads), 0, ptr(ws), nws.value, current_stream()),
+                  "xmh_head_dcmht_backward_apply")
+        else:
+            check(lib.xmh_head_dcmht_backward(ctypes.byref(h), ptr(x), ptr(up), B, E, N, ptr(saved), nsaved, ctypes.byref(grads), 0, ptr(ws),
+                                              nws.value, current_stream()), "xmh_head_dcmht_backward")
         if gx is not None:
             gx = gx.reshape(ctx.meta[0]).to(ctx.meta[1])
         return (None, gx, *gp)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 from torch import distributed as dist
 from torch.utils.data import DataLoader, Sampler
+from torch.utils.data.distributed import DistributedSampler
 
 from .. import _lib
 from .. import retrieval as R
@@ -192,14 +193,19 @@ class BaseTrainer:
         for nm, t in (("train", self.train_labels), ("query", self.query_labels), ("retrieval", self.retrieval_labels)):
             if t is not None:
                 self.logger.info(f"{nm} shape: {tuple(t.shape)}")
-        qs = rs = None
+        qs = rs = ts = None
         if self.distributed:
+            if train_data is not None:
+                # the reference's choice (runners/base.py:172-178); it never calls set_epoch, so every epoch draws the same order.  The
+                # sampler pads its share to ceil(n / world_size): every rank runs the same number of steps, which the one collective
+                # per step of xmh/ddp.py relies on
+                ts = DistributedSampler(train_data, num_replicas=self.world_size, rank=self.rank, shuffle=True)
             qs = ContiguousShardSampler(len(query_data), self.rank, self.world_size)
             rs = ContiguousShardSampler(len(retrieval_data), self.rank, self.world_size)
             batch_size = max(1, batch_size // self.world_size)
         mk = lambda d, s, sh: DataLoader(d, batch_size=batch_size, num_workers=num_workers, pin_memory=pin_memory, sampler=s,   # noqa: E731
                                          shuffle=sh, drop_last=False, collate_fn=getattr(d, "collate", None))
-        self.train_loader = mk(train_data, None, shuffle and not self.distributed) if train_data is not None else None
+        self.train_loader = mk(train_data, ts, shuffle and not self.distributed) if train_data is not None else None
         self.query_loader = mk(query_data, qs, False)
         self.retrieval_loader = mk(retrieval_data, rs, False)
 

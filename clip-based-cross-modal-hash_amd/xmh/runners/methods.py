@@ -48,6 +48,15 @@ class _MethodTrainer(BaseTrainer):
                    model_state=run.get("resume_model", ""), display_step=run.get("display_step", 20), top_k=run.get("top_k", None),
                    world_size=world_size, distributed=distributed, **extra)
 
+    def build_model(self, cfg_model, output_dim=16, **kwags):
+        """the base class's, and with distributed=True every BatchNorm head takes its batch statistics over all ranks:
+        what the reference gets from nn.SyncBatchNorm.convert_sync_batchnorm (runners/base.py:111)"""
+        super().build_model(cfg_model, output_dim=output_dim, **kwags)
+        if self.distributed:
+            from torch import distributed as dist
+            for head in _sync_heads(self.model):
+                head.sync_group = dist.group.WORLD
+
     def loss_extras(self, inputs, label):
         """further keywords of the model's object_function, made from the batch (MITH: label_sim)"""
         return {}
@@ -81,20 +90,57 @@ def _step(trainer, image, text, key_padding_mask, label, index, epoch, times):
                                 global_step=trainer.global_step)
 
 
-def _train_epoch(trainer, epoch: int, step=_step):
+# why an epoch does not run with distributed=True although the all-reduce of the gradients (xmh/ddp.py) exists
+_NO_DDP_STATE = ("%s is per-rank state that DistributedDataParallel reconciles by a per-forward buffer broadcast beside the all-reduce "
+                 "of the gradients; the buffer broadcast is not built")
+_NO_DDP_UNCHECKED = ("the all-reduce of the gradients (xmh/ddp.py) is built and checked for the epochs of DCMHT and DSPH; this method's "
+                     "distributed step has no float64 restatement yet")
+
+
+def _sync_heads(model):
+    """the BatchNorm heads of a model: the modules whose batch statistics must span the ranks of a distributed step"""
+    from ..models.heads import DCMHTModalityHash
+    return [m for m in model.modules() if isinstance(m, DCMHTModalityHash) and isinstance(m.norm, torch.nn.BatchNorm1d)]
+
+
+def _no_ddp_local_batchnorm(trainer):
+    """DCMHT: a reason unless every BatchNorm head of the model has its process group (build_model gives it with distributed=True)"""
+    model = getattr(trainer, "model", None)
+    if model is not None and all(m.sync_group is not None for m in _sync_heads(model)):
+        return None
+    return ("the image head's BatchNorm has no process group (build_model sets sync_group; the reference converts to SyncBatchNorm): "
+            "its statistics would be the local batch's, and the all-reduce of the gradients would average gradients of different functions")
+
+
+def _train_epoch(trainer, epoch: int, step=_step, no_ddp=None):
     """runners/DCMHT/runner.py:107-128 and runners/DSPH/runner.py:104-127 (the latter also steps the proxies' optimiser); with MITH's
     declaration, runners/MITH/runner.py:98-123.  `step(trainer, image, text, key_padding_mask, label, index, epoch, times)`
     returns the loss of one batch.  The optimiser is built on the first call, when the instance has none yet.  A batch of raw
     photos (uint8, stacked or a list of different sizes: the file layout's training split) goes through the GPU training
-    transform; a float batch goes on as it is."""
+    transform; a float batch goes on as it is.
+
+    distributed=True: every rank runs its share of the batch (build_loader's DistributedSampler, the same number of
+    steps on every rank), and between ``loss.backward()`` and the optimisers' steps the GradReducer averages every gradient of
+    ``model.parameters()`` -- DSPH's proxies among them -- over the ranks in one collective.  The reducer is built with the optimiser
+    on the first call and rank 0's parameters are broadcast once.  Each rank logs its own loss, as in the reference.  `no_ddp`: the
+    reason why the calling method's epoch does not run distributed, or a function of the trainer that gives it (None: it does)."""
     if trainer.distributed:
-        raise NotImplementedError("train_epoch with distributed=True: there is no all-reduce of the gradients")
+        reason = no_ddp(trainer) if callable(no_ddp) else no_ddp
+        if reason is not None:
+            raise NotImplementedError("train_epoch with distributed=True: " + reason)
     if getattr(trainer, "optimizer", None) is None:
         built = trainer.build_optimizer(trainer.cfg.get("optimizer"))
         trainer.optimizer, trainer.lr_schedu = built[0], built[-1]
         trainer.optimizer_loss = built[1] if len(built) == 3 else None
     optimizer_loss = getattr(trainer, "optimizer_loss", None)      # DSPH: the proxies' own optimiser
     trainer.change_state(mode="train")
+    reducer = None
+    if trainer.distributed:
+        reducer = getattr(trainer, "reducer", None)
+        if reducer is None:                                        # after change_state: requires_grad is what training sees
+            from ..ddp import GradReducer
+            reducer = trainer.reducer = GradReducer(trainer.model, trainer.world_size)
+            reducer.broadcast_parameters()
     trainer.logger.info(">>>>>> epochs: %d/%d" % (epoch, trainer.epochs))
     all_loss = 0
     times = 0
@@ -113,6 +159,8 @@ def _train_epoch(trainer, epoch: int, step=_step):
         if optimizer_loss is not None:
             optimizer_loss.zero_grad()
         loss.backward()
+        if reducer is not None:
+            reducer.reduce()
         trainer.optimizer.step()
         if optimizer_loss is not None:
             optimizer_loss.step()
@@ -147,7 +195,7 @@ class DCMHTTrainer(_MethodTrainer):
 
     def train_epoch(self, epoch: int):
         """runners/DCMHT/runner.py:107-128"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_no_ddp_local_batchnorm)
 
 
 @registry.register_runner("DSPHTrainer")
@@ -206,7 +254,7 @@ class MITHTrainer(_MethodTrainer):
 
     def train_epoch_towers(self, epoch: int):
         """runners/MITH/runner.py:98-123: the backbone at backbone_lr and the head at lr, the text tower with the key padding mask"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_NO_DDP_STATE % "MITH's feature bank")
 
     def generate_hash(self, image, text, key_padding_mask=None):
         _, img_cls_hash, tokens_hash_i, _, _, txt_cls_hash, tokens_hash_t, _ = self.model(image, text, key_padding_mask=key_padding_mask)
@@ -237,7 +285,7 @@ class TwDHTrainer(DCMHTTrainer):
 
     def train_epoch_codes(self, epoch: int):
         """runners/TwDH/runner.py:116-137: one BertAdam over the backbone and the hash layer; the transforms and centres are constants"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_NO_DDP_UNCHECKED)
 
     def build_model(self, cfg_model, output_dim=16):
         super().build_model(cfg_model, output_dim=output_dim)
@@ -352,7 +400,7 @@ class DNPHTrainer(_MethodTrainer):
     def train_epoch(self, epoch: int):
         """runners/DNPH/runner.py:113-136: the four outputs of the head over both towers into the objective; the proxies' SGD steps
         beside BertAdam"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_NO_DDP_STATE % "DNPH's noise assignment")
 
     def generate_hash(self, image, text, key_padding_mask=None):
         """runners/DNPH/runner.py:138-141: the codes alone; the class logits are a training signal"""
@@ -383,7 +431,7 @@ class DIMCHTrainer(_MethodTrainer):
 
     def train_epoch(self, epoch: int):
         """runners/DIMCH/runner.py:119-140"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_NO_DDP_UNCHECKED)
 
     def merge_hash(self, image_embed, text_embed):
         """runners/DIMCH/runner.py:142-145"""
@@ -439,7 +487,7 @@ class UMoEDTrainer(_MethodTrainer):
 
     def train_epoch_decoder(self, epoch: int):
         """runners/UMoED/runner.py:134-155: the backbone at backbone_lr and the hash layer at lr through UMoED.forward_train"""
-        _train_epoch(self, epoch)
+        _train_epoch(self, epoch, no_ddp=_NO_DDP_UNCHECKED)
 
     def train_decoder(self):
         """the reference's train() with this epoch: every epoch followed by valid(), then the FINISHED line"""

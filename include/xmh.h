@@ -851,6 +851,36 @@ int xmh_head_dcmht_train_forward(const xmh_dcmht_train* h, const float* x, int64
 int xmh_head_dcmht_backward(const xmh_dcmht_train* h, const float* x, const float* d_probs, int64_t B, int E, int N,
                             const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate, void* workspace,
                             size_t workspace_bytes, xmh_stream_t stream);
+/* The same head with a CROSS-RANK BatchNorm (distributed training; norm_is_batchnorm only, else XMH_EINVAL): each of
+ * the two calls above in two halves, and between the halves the caller gathers one statistics row per rank.  A row is
+ * xmh_head_dcmht_stats_len(E) = 2 E + 2 doubles on the device: a [E], b [E], the rank's row count, 0.  `table` is the rows of all
+ * `world` ranks in rank order, contiguous.  saved and workspace are those of xmh_head_dcmht_train_bytes for THIS rank's B; the
+ * workspace carries o (forward) / dn (backward) from the first half to the second and must be kept in between.
+ *   forward_stats   the products up to o; row = local column mean, local M2 = sum (o - mean)^2 (the two double passes of the fused
+ *                   call), B.
+ *   forward_apply   (n, mean, M2) of the ranks combined in rank order by the pairwise update -- every rank derives the same bits --,
+ *                   this rank's rows normalised with the global mean and biased variance, the running statistics moved by momentum
+ *                   towards the global mean and the UNBIASED global variance (n_total - 1), then fc2 / relu / pair softmax; fills
+ *                   the saved buffer as the fused call does (rstd is the same on every rank).
+ *   backward_stats  d_w2, d_b2 and dn; row = local column sums of dn nhat and of dn, B.  They are formed whatever g leaves out: the
+ *                   other ranks wait for this rank's row.
+ *   backward_apply  d_norm_w / d_norm_b from row `rank`, THIS rank's sums (the gradient all-reduce averages them like every other
+ *                   gradient); the rows added in rank order; do = gamma rstd (dn - mean(dn) - nhat mean(dn nhat)) with the means
+ *                   over n_total; the remaining products.
+ * B = 1 is legal when another rank brings rows; a global batch of one row (world == 1 and B == 1) is XMH_EINVAL.  With world == 1
+ * the two halves compute what the fused call computes, to the bit. */
+int64_t xmh_head_dcmht_stats_len(int E);
+int xmh_head_dcmht_train_forward_stats(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, void* saved, size_t saved_bytes,
+                                       void* workspace, size_t workspace_bytes, double* stats_row, xmh_stream_t stream);
+int xmh_head_dcmht_train_forward_apply(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, const double* table, int world,
+                                       float* probs, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
+                                       xmh_stream_t stream);
+int xmh_head_dcmht_backward_stats(const xmh_dcmht_train* h, const float* x, const float* d_probs, int64_t B, int E, int N,
+                                  const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate, void* workspace,
+                                  size_t workspace_bytes, double* stats_row, xmh_stream_t stream);
+int xmh_head_dcmht_backward_apply(const xmh_dcmht_train* h, const float* x, int64_t B, int E, int N, const double* table, int world,
+                                  int rank, const void* saved, size_t saved_bytes, const xmh_dcmht_grads* g, int accumulate,
+                                  void* workspace, size_t workspace_bytes, xmh_stream_t stream);
 /* y [B, K] = tanh(keep * (x w^T + b) / (1 - p)): w [K, E], b [K], keep [B, K] bytes (non-zero = kept) or NULL for no dropout.
  * The library draws no random numbers. */
 int xmh_head_dsph_train_forward(const float* w, const float* b, const float* x, const uint8_t* keep, float p, int64_t B, int E,
@@ -944,6 +974,35 @@ size_t xmh_bertadam_ws_bytes(int64_t n_tensors, int64_t total_chunks);
 /* n_tensors == 0 is a successful no-op; negative counts, null pointers, a short or misaligned workspace are XMH_EINVAL. */
 int xmh_bertadam_step(const xmh_bertadam_tensor* table, int64_t n_tensors, const xmh_bertadam_chunk_ref* chunk_map,
                       int64_t total_chunks, void* ws, size_t ws_bytes, xmh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Gradient bucket of distributed training (xmh/ddp.py): any number of fp32 tensors packed into, or scattered out of, ONE
+ * flat fp32 buffer in one launch.
+ *   pack:   flat[offset_i + j] = t_i[j] * scale for j < numel_i (one fp32 product, round to nearest); a row whose t is NULL writes
+ *           numel_i zeros; then flat[flag_at_i] = flag_i where flag_at_i >= 0 (the flag tail: one float per tensor behind the last one,
+ *           1.0 = this rank had a gradient, 0.0 = it had none, so that a SUM all-reduce of the bucket also counts the ranks that had one).
+ *   unpack: t_i[j] = flat[offset_i + j]; a row whose t is NULL is skipped; flag and flag_at are not read.
+ * Elements of flat between the tensors (padding) are neither read nor written.
+ * table [n_tensors] and chunk_map [total_chunks] are DEVICE arrays the caller fills; the chunk map is BertAdam's (above), over the
+ * rows' numel, with xmh_bertadam_chunk() elements per chunk.
+ * Limits: numel >= 1 per row; offset a multiple of 4 floats (the callers use 64) and flat 16-byte aligned, so the flat side moves in
+ * 16-byte accesses; a tensor needs 4-byte alignment only (16-byte accesses where it is 16-byte aligned, dword accesses otherwise, the
+ * last numel % 4 elements as dwords).  A tensor may be its own range of flat (pack in place).  total_chunks <= 2^31 - 1.
+ * No host synchronisation, no allocation, no atomics.  n_tensors == 0 is a successful no-op; negative counts, null pointers and a
+ * misaligned table, map or flat buffer are XMH_EINVAL.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xmh_bucket_tensor {
+    float* t;                                          /* the tensor: source of pack, destination of unpack; NULL: see above */
+    int64_t offset;                                    /* its first element in flat */
+    int64_t numel;
+    int64_t flag_at;                                   /* pack: the element of flat that receives flag, or -1 */
+    float flag;
+    int32_t reserved;                                  /* 0 */
+} xmh_bucket_tensor;                                   /* 40 bytes */
+int xmh_bucket_pack(const xmh_bucket_tensor* table, int64_t n_tensors, const xmh_bertadam_chunk_ref* chunk_map, int64_t total_chunks,
+                    float scale, float* flat, xmh_stream_t stream);
+int xmh_bucket_unpack(const xmh_bucket_tensor* table, int64_t n_tensors, const xmh_bertadam_chunk_ref* chunk_map, int64_t total_chunks,
+                      const float* flat, xmh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DNPH (reference models/DNPH): the proxy + class-prediction + noise objective, its gradients, the noise assignment, and the
